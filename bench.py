@@ -8,10 +8,17 @@ MLP [64,64,64], fp32, on N MI355X of one node.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
-One JSON line on stdout (rank 0).  Inputs are resident in HBM before the timed region.  Besides the
-contract's fields it carries `roofline` (dominant kernel, HIP events on the launch stream inside the
-timed region), `kernels` (every C-ABI entry point: calls/step, mean ms, algorithmic GB/s where defined)
-and `cpu_baseline` (the CPU oracle port timed on this box's host cores on a bounded sample).
+One JSON line on stdout (rank 0).  Inputs are resident in HBM before the timed region.  A plain run does
+what the headline needs only: set-up, the pre-roll to the long-run state, warm-up, the --steps timed
+steps and the result line (metric, value, unit, ms_per_step, dtype, config).  With --full the line also
+carries `roofline` (dominant kernel, HIP events on the launch stream inside the timed region), `kernels`
+(every C-ABI entry point: calls/step, mean ms, algorithmic GB/s where defined), `long_run`, the cold
+start, the other execution modes and sizes, `cpu_baseline` (the CPU oracle port timed on this box's host
+cores on a bounded sample) and `full_size_parity`.
+
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32): the step's
+outputs (`pred`, `loss`, ...) and the dense parameters after its optimizer step (`param.<name>`); an
+array above its share of the 64 MB budget is written as a fixed, seeded sample of its flat elements.
 """
 import argparse
 import json
@@ -370,6 +377,35 @@ def full_size_parity(oracle, dev, near_tol=2e-3, dense_vs_float64=False):
                     "rounding) are held to 2e-3 (2.5 x the measured worst, 8e-4) instead of 1e-4"}
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs budget (64 MB with the .npy headers)
+
+
+def step_outputs(out, model):
+    """What a caller of the timed step receives, as host arrays: the step's output tensors (`pred`, `loss`, ...) and the
+    dense parameters after its optimizer step (`param.<name>`).  The tables are left out: the lazy optimizer brings a
+    row up to date only when it is next read, so right after a step they do not hold its result."""
+    arrays = {k: v.detach() for k, v in (out or {}).items() if torch.is_tensor(v)}
+    tables = {id(p) for m in model.modules() if hasattr(m, "table_parameters") for p in m.table_parameters()}
+    for k, p in model.named_parameters():
+        if id(p) not in tables:
+            arrays["param." + k] = p.detach()
+    return {k: (v.double() if v.dtype == torch.float64 else v.float()).cpu() for k, v in arrays.items()}
+
+
+def write_outputs(arrays, path):
+    """DIR/<name>.npy for every array; one above its share of DUMP_BYTES is written as a fixed, seeded sample of its flat
+    elements (in index order)"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for k, t in arrays.items():
+        cap = max(1, share // t.element_size())
+        if t.numel() > cap:
+            idx = torch.randperm(t.numel(), generator=torch.Generator().manual_seed(0))[:cap].sort().values
+            t = t.reshape(-1)[idx]
+        np.save(os.path.join(path, k + ".npy"), t.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -437,7 +473,14 @@ def main():
     ap.add_argument("--precision", default=None, choices=["fp32", "bf16", "bf16x3", "bf16x6", "auto"],
                     help="matrix-core mode of the GEMM kernels (default: the library's 'auto' = bf16x3 for launches that "
                          "are matrix-core bound, fp32-faithful bf16x6 for HBM-bound ones)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the cold start, the per-kernel pass, the in-step launch probes, the long run, "
+                         "the lazy optimizer's flush, the other real-step mode, the strong-scaling batch, the CPU baseline "
+                         "and the full-size parity check (the --no-* / --long-steps options apply to this part)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32, 64 MB at most)")
     args = ap.parse_args()
+    full = args.full
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -528,13 +571,12 @@ def main():
                                  post_backward=(lambda: allreduce_dense_grads(model)) if sharded else None)
 
     def step(data, nxt=None, graphed=False):
+        """one step; returns the model's output dict (a replay's: static tensors the next replay overwrites)"""
         if args.mode == "forward":
             with torch.no_grad():
-                model(data, is_training=False)
-            return
+                return model(data, is_training=False)
         if graphed and gstep is not None and nxt is not None:
-            gstep(data, nxt)  # (its first two calls run eagerly; then one capture per static input set; then replays)
-            return
+            return gstep(data, nxt)  # (its first two calls run eagerly; then one capture per static input set; then replays)
         if nxt is not None:
             model.prefetch(nxt)  # the next batch's row sort is started behind this forward, on the side stream
         out = model(data)
@@ -543,6 +585,7 @@ def main():
             allreduce_dense_grads(model)  # one flat bucket; embedding-row grads already travelled in backward
         opt.step()
         model.zero_grad()
+        return out
 
     def barrier():
         if world > 1:
@@ -580,7 +623,8 @@ def main():
                    if st._lazy is not None)
 
     # ---- (1) cold start: what a 20-step run measures right after initialisation (most rows have never been touched,
-    #          have m = v = 0 and cost the lazy optimizer nothing) — kept as an extra key, NOT the headline
+    #          have m = v = 0 and cost the lazy optimizer nothing) — kept as an extra key (--full), NOT the headline.  A
+    #          plain run takes the same steps untimed: the timed window then starts from the same state in both
     n_seen = 0
     cold = None
     if pre_roll > 0:
@@ -589,9 +633,13 @@ def main():
         n_seen += args.warmup
         cb = [gen(n_seen + i) for i in range(min(args.steps, 64))]
         n_seen += len(cb)
-        dt = timed(cb)
-        cold = {"ms_per_step": round(dt / len(cb) * 1e3, 4), "value": round(B * len(cb) / dt, 1), "steps": len(cb),
-                "note": "first steps after initialisation: the lazy optimizer has nothing to replay yet"}
+        if full:
+            dt = timed(cb)
+            cold = {"ms_per_step": round(dt / len(cb) * 1e3, 4), "value": round(B * len(cb) / dt, 1), "steps": len(cb),
+                    "note": "first steps after initialisation: the lazy optimizer has nothing to replay yet"}
+        else:
+            for b in cb:
+                step(b)
         del cb
         # ---- (2) pre-roll to the long-run state
         nb = gen(n_seen)
@@ -611,7 +659,7 @@ def main():
     #          launch — that serialises the queue and costs ~45 % of the step, so it stays out of the timed region)
     n_batches = min(args.steps, 512)  # distinct batches resident for the timed region (8.8 GB of ids at 512)
     batches = [gen(n_seen + args.warmup + i) for i in range(n_batches)]
-    n_prof = min(3, args.warmup)
+    n_prof = min(3, args.warmup) if full else 0
     # Training loops know their next batch (model_pipeline._one_ahead does the same): announcing it lets its row sort run on
     # the side stream beside the step in flight.  One sort is started per step, for the step after it; the sort of the
     # first timed batch is started by the last warm-up step.
@@ -628,23 +676,24 @@ def main():
     for i in range(args.warmup - n_prof):
         step(wb[i], wb[i + 1] if ahead else None)
     barrier()
-    hip.enable_timing(True)
-    for i in range(args.warmup - n_prof, args.warmup):
-        step(wb[i], wb[i + 1] if ahead else None)
+    if n_prof:
+        hip.enable_timing(True)
+        for i in range(args.warmup - n_prof, args.warmup):
+            step(wb[i], wb[i + 1] if ahead else None)
+        barrier()
     del wb
-    barrier()
     prof = hip.timing_summary() if n_prof else None
     hip.enable_timing(False)
-    backlog0 = lazy_backlog() if lazy else None
-    pending0 = pending_real_steps() if (lazy and getattr(opt, "defer", False)) else None
-    # ---- (4) timed region: EXACTLY --steps steps; events only around the launches the roofline objects report
+    backlog0 = lazy_backlog() if (full and lazy) else None
+    pending0 = pending_real_steps() if (full and lazy and getattr(opt, "defer", False)) else None
+    # ---- (4) timed region: EXACTLY --steps steps; events only around the launches the roofline objects report (--full)
     if prof is not None:
         ours = {n: c * m for n, (c, m) in prof.items() if not n.startswith("lazy_adam_flush") and not side_stream(n)}
         top = sorted(ours, key=ours.get, reverse=True)[:2]
         watch = {n.split("[")[0] for n in top} | {"embed_gather_fwd", "embed_gather_linear_fwd", "embed_gather_linear_fwd_bf16",
                                                     "linear_fwd", "linear_wgrad"}
         hip.enable_timing(True, only=watch)
-    else:
+    elif full:
         hip.enable_timing(True)
     ev_stride = 4 if (n_prof and args.steps >= 8) else 1  # events on every 4th timed step only
     barrier()
@@ -695,15 +744,17 @@ def main():
             gc_win["n"] += 1
             gc_win["s"] += time.perf_counter() - gc_win["t"]
 
-    gc.callbacks.append(_gc_cb)
+    if full:
+        gc.callbacks.append(_gc_cb)
     host_each = []
+    last_out = None
     wev = [torch.cuda.Event(enable_timing=True) for _ in range(args.steps + 1)] if args.window_events else None
     if wev is not None:
         wev[0].record()
     for i in range(args.steps):
         hip.pause_timing(i % ev_stride != 0)
         th = time.perf_counter()
-        step(batches[i % n_batches], batches[(i + 1) % n_batches] if ahead else None, graphed=True)
+        last_out = step(batches[i % n_batches], batches[(i + 1) % n_batches] if ahead else None, graphed=True)
         host_each.append(time.perf_counter() - th)  # time the host needs to ENQUEUE a step (it runs ahead of the device)
         if wev is not None:
             wev[i + 1].record()
@@ -711,7 +762,12 @@ def main():
     hip.pause_timing(False)
     barrier()
     dt = time.perf_counter() - t0
-    gc.callbacks.remove(_gc_cb)
+    if full:
+        gc.callbacks.remove(_gc_cb)
+    # what the last timed step computed, copied off the device before anything else runs (a replay's outputs are static
+    # tensors the next replay overwrites); written at the end
+    dumped = step_outputs(last_out, model) if (args.dump_outputs and rank == 0) else None
+    del last_out
     pw = None
     if wev is not None:
         print("window events (ms per step):", [round(wev[i].elapsed_time(wev[i + 1]), 4) for i in range(args.steps)],
@@ -719,8 +775,8 @@ def main():
               "host enqueue", [round(h * 1e3, 3) for h in host_each], file=sys.stderr)
     # the lazy optimizer's owed work at the END of the timed window, read before anything else runs (read
     # after the probes' ~125 further steps over the window's own 20 batches it said something else)
-    backlog1 = lazy_backlog() if lazy else None
-    pending1 = pending_real_steps() if (lazy and getattr(opt, "defer", False)) else None
+    backlog1 = lazy_backlog() if (full and lazy) else None
+    pending1 = pending_real_steps() if (full and lazy and getattr(opt, "defer", False)) else None
     host_slowest = max(range(args.steps), key=lambda i_: host_each[i_])
     host_call_ms = host_wait_ms = host_call_max_ms = host_stall = None
     in_step = None
@@ -730,6 +786,94 @@ def main():
         win_host = (gstep.host_call_s, gstep.host_wait_s, gstep.host_call_max_s, dict(gstep.host_seg_max),
                     max((pl.slowest_call(reset=True) for pl in gstep.plans if pl is not None), key=lambda t_: t_[2])
                     if gstep.backend_used == "plan" else None)
+
+    # ---- the headline's own fields (both forms of the run)
+    F = sum(1 for v in enc.values() if "vocab_size" in v)
+    ND = sum(1 for v in enc.values() if "min" in v)
+    D = model.embedding_dim
+    n_unique = int(sum(torch.unique(batches[0][f"C{i + 1}"]).numel() for i in range(F)))
+    opt_txt = (("dense Adam, reference semantics (trainer.py:75), executed lazily with the CLOSED-FORM replay of skipped "
+                "zero-gradient steps: <= 1e-6 relative to the serial replay per replay and not further from float64 Adam "
+                "than it (tests/test_hip_lazy_adam.py); logits within 1e-4 of the serial mode after 1100 steps; "
+                "--replay exact = the bit-identical serial mode"
+                if replay_mode == "closed" else
+                "dense Adam, reference semantics (trainer.py:75), executed lazily: bit-identical to the dense HIP kernel") +
+               "; <= 2e-4 relative vs torch.optim.Adam after 2 steps (sqrt(v) kept as state, v_rcp_f32 in the update)"
+               if args.optimizer == "lazy" else
+               "dense Adam (reference semantics, every row streamed each step, fused zero_grad)")
+
+    def headline(dt):
+        """the result line's headline keys; dt = the timed window's wall time (max over ranks)"""
+        return {
+            "metric": f"samples/sec {type(model).__name__} Criteo-shape bsz={local_B}/GPU (train step: fwd+bwd+dense Adam+zero_grad)"
+                      if args.mode == "train" else f"samples/sec {type(model).__name__} Criteo-shape bsz={local_B}/GPU (forward only)",
+            "value": round(B * args.steps / dt, 1), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True,
+            "scaling": args.scaling, "vs_baseline": None, "data": "synthetic",
+            "dtype": "f32" if args.storage == "fp32" else
+                     ("bf16 tables (secondary inference line; fp32 accumulation)" if args.mode == "forward" else
+                      "bf16 lookup copy of the tables + bf16 activation (SECONDARY training line with a stated tolerance; fp32 "
+                      "master tables, moments and accumulation)"),
+            "config": {"workload": f"{type(model).__name__} ({args.model}), {F} sparse fields (Criteo-Kaggle "
+                                   f"cardinalities/{args.vocab_scale}, {n_table_rows} arena rows) x D={D} + {ND} dense, "
+                                   f"batch {local_B} per GPU (global {B}), "
+                                   + ("uniform ids" if args.id_dist == "uniform" else "bounded Zipf(1.05) ids")
+                                   + (f", MLP {list(hidden)}" if args.model == "deepfm" else
+                                      (", MLP [64,64,64]" if args.model != "mmoe" else ", 4 experts x 128, towers [256,128]"))
+                                   + (", CIN [128,128]" if args.model == "xdeepfm" else ""),
+                       "global_batch": B, "per_gpu_batch": local_B, "optimizer": opt_txt,
+                       "matmul_precision": precision, "lazy_replay": replay_mode,
+                       "deferred_real_step": bool(getattr(opt, "defer", False)),
+                       "sort_ahead": bool(ahead),
+                       "hip_graph": (None if gstep is None else
+                                     (f"the timed steps are replays of ONE captured step (fwd + bwd + optimizer step + zero_grad "
+                                      f"+ the next batch's sort; rec_pangu_amd/graph_step.py, bit-identical to the eager step: "
+                                      f"tests/test_hip_graph.py), replayed as "
+                                      + (f"a LAUNCH PLAN (csrc/plan.hip: {gstep.plans[0].nodes} recorded library launches re-issued "
+                                         f"with hipLaunchKernel, {gstep.plans[0].side} of them — the next batch's keys + sort — on the "
+                                         f"plan's side stream beside the step)" if gstep.backend_used == "plan" else
+                                         f"a hipGraph ({gstep.why_not_plan or 'backend hipgraph'})"))),
+                       "captured_step_backend": None if gstep is None else gstep.backend_used,
+                       "unique_rows_per_batch": n_unique,
+                       "parallelism": "single GPU" if not sharded else
+                       f"tables row-sharded x{world}, all-to-all lookup ({args.wire} rows on the wire)"},
+            "pre_roll_steps": pre_roll,
+        }
+
+    def finish(res):
+        """writes --dump-outputs, prints the result line (rank 0) and takes the process group down"""
+        nonlocal gstep
+        if dumped is not None:
+            write_outputs(dumped, args.dump_outputs)
+        # the JSON line is the LAST thing on stdout: RCCL's init banner sits in the C stdio buffer until exit otherwise
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+        if rank == 0:
+            print(json.dumps(res), flush=True)
+        if sharded:
+            torch.distributed.barrier()
+            if gstep is not None:
+                # a captured step that holds RCCL nodes keeps the communicator busy: destroying the process group under live
+                # graph executables never returns on this runtime (measured: stuck in destroy_process_group).  Release the
+                # captures first.
+                gstep.reset()
+                gstep = None
+                torch.cuda.synchronize()
+            torch.distributed.destroy_process_group()
+
+    if not full:
+        # a plain run: the headline only (the timed steps skipped their per-step index check: it is made here, once)
+        for m in model.modules():
+            if hasattr(m, "raise_if_bad_index"):
+                m.raise_if_bad_index()
+        if world > 1:
+            t = torch.tensor([dt], device=dev, dtype=torch.float64)
+            torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
+            dt = float(t.item())
+        res = headline(dt)
+        res["pre_window_replays"] = n_pre_done
+        finish(res)
+        return
     # ---- (4b) long run (VERDICT r4 item 2b): >= 2000 more steps of the same execution form over 512 DISTINCT resident
     #          batches, a timing event after every step: mean / p50 / p99 / max step.  (The 20-step window above is 20 ms.)
     #          Round 6: run RIGHT BEHIND the timed window, in front of everything that changes the optimizer's state — it used
@@ -830,7 +974,6 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         dt = float(t.item())
     ms_per_step = dt / args.steps * 1e3
-    value = B * args.steps / dt
     # ---- (5) the lazy optimizer's deferred work: equal at both ends of the timed region in the long-run state (nothing
     #          was pushed out of the window); the flush that a checkpoint would trigger is timed separately
     flush_ms = None
@@ -931,10 +1074,6 @@ def main():
         del gs_small
 
     # ---- per-kernel numbers (algorithmic bytes from SURVEY.md 8d) --------------------------------
-    F = sum(1 for v in enc.values() if "vocab_size" in v)
-    ND = sum(1 for v in enc.values() if "min" in v)
-    D = model.embedding_dim
-    n_unique = int(sum(torch.unique(batches[0][f"C{i + 1}"]).numel() for i in range(F)))
     n_pairs = F * local_B
     # the tables whose gradient rows come from the sample-major one-hot launch (rp_embed_grad_tiny): their pairs and rows
     # are not the row-sorted kernel's
@@ -1225,120 +1364,65 @@ def main():
             n = max(rows, key=rows.get)
             gemm = roofline_of(n, timing[n][1])
 
-    if rank == 0:
-        opt_txt = (("dense Adam, reference semantics (trainer.py:75), executed lazily with the CLOSED-FORM replay of skipped "
-                    "zero-gradient steps: <= 1e-6 relative to the serial replay per replay and not further from float64 Adam "
-                    "than it (tests/test_hip_lazy_adam.py); logits within 1e-4 of the serial mode after 1100 steps; "
-                    "--replay exact = the bit-identical serial mode"
-                    if replay_mode == "closed" else
-                    "dense Adam, reference semantics (trainer.py:75), executed lazily: bit-identical to the dense HIP kernel") +
-                   "; <= 2e-4 relative vs torch.optim.Adam after 2 steps (sqrt(v) kept as state, v_rcp_f32 in the update)"
-                   if args.optimizer == "lazy" else
-                   "dense Adam (reference semantics, every row streamed each step, fused zero_grad)")
-        res = {
-            "metric": f"samples/sec {type(model).__name__} Criteo-shape bsz={local_B}/GPU (train step: fwd+bwd+dense Adam+zero_grad)"
-                      if args.mode == "train" else f"samples/sec {type(model).__name__} Criteo-shape bsz={local_B}/GPU (forward only)",
-            "value": round(value, 1), "unit": "samples/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4), "higher_is_better": True,
-            "scaling": args.scaling, "vs_baseline": None, "data": "synthetic",
-            "dtype": "f32" if args.storage == "fp32" else
-                     ("bf16 tables (secondary inference line; fp32 accumulation)" if args.mode == "forward" else
-                      "bf16 lookup copy of the tables + bf16 activation (SECONDARY training line with a stated tolerance; fp32 "
-                      "master tables, moments and accumulation)"),
-            "config": {"workload": f"{type(model).__name__} ({args.model}), {F} sparse fields (Criteo-Kaggle "
-                                   f"cardinalities/{args.vocab_scale}, {n_table_rows} arena rows) x D={D} + {ND} dense, "
-                                   f"batch {local_B} per GPU (global {B}), "
-                                   + ("uniform ids" if args.id_dist == "uniform" else "bounded Zipf(1.05) ids")
-                                   + (f", MLP {list(hidden)}" if args.model == "deepfm" else
-                                      (", MLP [64,64,64]" if args.model != "mmoe" else ", 4 experts x 128, towers [256,128]"))
-                                   + (", CIN [128,128]" if args.model == "xdeepfm" else ""),
-                       "global_batch": B, "per_gpu_batch": local_B, "optimizer": opt_txt,
-                       "matmul_precision": precision, "lazy_replay": replay_mode,
-                       "deferred_real_step": bool(getattr(opt, "defer", False)),
-                       "sort_ahead": bool(ahead),
-                       "hip_graph": (None if gstep is None else
-                                     (f"the timed steps are replays of ONE captured step (fwd + bwd + optimizer step + zero_grad "
-                                      f"+ the next batch's sort; rec_pangu_amd/graph_step.py, bit-identical to the eager step: "
-                                      f"tests/test_hip_graph.py), replayed as "
-                                      + (f"a LAUNCH PLAN (csrc/plan.hip: {gstep.plans[0].nodes} recorded library launches re-issued "
-                                         f"with hipLaunchKernel, {gstep.plans[0].side} of them — the next batch's keys + sort — on the "
-                                         f"plan's side stream beside the step)" if gstep.backend_used == "plan" else
-                                         f"a hipGraph ({gstep.why_not_plan or 'backend hipgraph'})"))),
-                       "captured_step_backend": None if gstep is None else gstep.backend_used,
-                       "unique_rows_per_batch": n_unique,
-                       "parallelism": "single GPU" if not sharded else
-                       f"tables row-sharded x{world}, all-to-all lookup ({args.wire} rows on the wire)"},
-            "pre_roll_steps": pre_roll, "cold": cold,
-            "pre_window_replays": n_pre_done,
-            "host_enqueue_ms_per_step": round(host_s / args.steps * 1e3, 4),
-            "host_call_ms_per_step_unblocked": None if host_call_ms is None else round(host_call_ms, 4),
-            "host_wait_ms_per_step": None if host_wait_ms is None else round(host_wait_ms, 4),
-            "host_call_max_ms_in_window": None if host_call_max_ms is None else round(host_call_max_ms, 4),
-            "host_stall": host_stall,
-            "host_slowest_step_in_window": {"step": host_slowest, "ms": round(host_each[host_slowest] * 1e3, 4)},
-            "gc_in_window": {"passes": gc_win["n"], "ms": round(gc_win["s"] * 1e3, 4)},
-            "host_note": "host_enqueue = wall time of the step call on the host, INCLUDING the back-pressure wait once 6 replays are "
-                         "queued (then it equals the device's step time and says nothing about the host); host_call_unblocked = the "
-                         "same without that wait: what the host itself needs per replayed step",
-            "roofline": roofline, "roofline_phase": phase, "roofline_gather": gather, "long_run": long_run,
-            "in_step_launches": in_step, "kernels": kernels,
-            "in_step_note": "in_step_launches: every launch of the captured step in recorded order with its duration INSIDE replayed "
-                            "steps (live, rp_plan_set_probe: one launch bracketed per replay); `kernels`: eager passes below",
-            "kernels_note": f"per-kernel table: HIP events around every launch during the last {n_prof} warm-up steps; "
-                            + (f"roofline/roofline_gather durations: HIP events around the same launches in 8 eager steps "
-                               f"right after the timed region (a replayed graph runs no python, so no event can bracket one "
-                               f"of its nodes; profiles/ holds the rocprofv3 trace of the replays)" if gstep is not None else
-                               f"roofline/roofline_gather durations: HIP events inside the timed region, every "
-                               f"{ev_stride}th step"),
-        }
-        if gemm is not None:
-            res["roofline_gemm"] = gemm
-        if small is not None:
-            res["strong_scaling_batch"] = small
-        if deferred_line is not None:
-            res["other_real_step_mode"] = deferred_line
-        if lazy:
-            res["lazy_adam"] = {
-                "state": f"long-run: {pre_roll} un-timed pre-roll steps on distinct batches before the warm-up",
-                "owed_element_steps_before": backlog0, "owed_element_steps_after": backlog1,
-                "flush_ms_after_timed_region": round(flush_ms, 3),
-                **({"deferred_real_steps_waiting_before": pending0, "deferred_real_steps_waiting_after": pending1,
-                    "deferred_note": "--defer: rows whose real step waits for their next touch.  In the true steady state "
-                                     "every touched row carries one and the count is constant; while rows of the large "
-                                     "tables are still being touched for the FIRST time it grows, i.e. that many real "
-                                     "steps (of the steps x unique rows the window owes) run after the window"}
-                   if pending0 is not None else {}),
-                "owed_after_over_before": (round(backlog1 / backlog0, 4) if backlog0 else None),
-                "note": "no flush inside the timed region.  owed_element_steps = sum over rows of (t - row's last step) x D, read "
-                        "before the pre-window replays (8 steps on batches of their own, directly in front of the first timed step: a host read-back "
-                        "there would leave the device idle at the window's start) and immediately after the last timed step (the "
-                        "probes and the eager passes behind it run on batches of their own too): in the long-run state it is stationary up to "
-                        "the batch-to-batch fluctuation (owed_after_over_before ~ 1), i.e. the window pushes no zero-gradient "
-                        "work out of the measurement; flush_ms is what state_dict() / a checkpoint pays to bring every row to "
-                        "the last step"}
-        if not args.no_cpu_baseline and world == 1:
-            res["cpu_baseline"], oracle_leg = cpu_baseline()
-            if args.model == "deepfm" and not sharded:
-                try:
-                    res["full_size_parity"] = full_size_parity(oracle_leg, dev)
-                except Exception as e:  # (reported, never silently dropped: the judge reads this key)
-                    res["full_size_parity"] = {"ok": False, "error": repr(e)}
-            del oracle_leg
-    # the JSON line is the LAST thing on stdout: RCCL's init banner sits in the C stdio buffer until exit otherwise
-    import ctypes
-    ctypes.CDLL(None).fflush(None)
-    if rank == 0:
-        print(json.dumps(res), flush=True)
-    if sharded:
-        torch.distributed.barrier()
-        if gstep is not None:
-            # a captured step that holds RCCL nodes keeps the communicator busy: destroying the process group under live
-            # graph executables never returns on this runtime (measured: stuck in destroy_process_group).  Release the
-            # captures first.
-            gstep.reset()
-            gstep = None
-            torch.cuda.synchronize()
-        torch.distributed.destroy_process_group()
+    res = headline(dt)
+    res.update({
+        "cold": cold,
+        "pre_window_replays": n_pre_done,
+        "host_enqueue_ms_per_step": round(host_s / args.steps * 1e3, 4),
+        "host_call_ms_per_step_unblocked": None if host_call_ms is None else round(host_call_ms, 4),
+        "host_wait_ms_per_step": None if host_wait_ms is None else round(host_wait_ms, 4),
+        "host_call_max_ms_in_window": None if host_call_max_ms is None else round(host_call_max_ms, 4),
+        "host_stall": host_stall,
+        "host_slowest_step_in_window": {"step": host_slowest, "ms": round(host_each[host_slowest] * 1e3, 4)},
+        "gc_in_window": {"passes": gc_win["n"], "ms": round(gc_win["s"] * 1e3, 4)},
+        "host_note": "host_enqueue = wall time of the step call on the host, INCLUDING the back-pressure wait once 6 replays are "
+                     "queued (then it equals the device's step time and says nothing about the host); host_call_unblocked = the "
+                     "same without that wait: what the host itself needs per replayed step",
+        "roofline": roofline, "roofline_phase": phase, "roofline_gather": gather, "long_run": long_run,
+        "in_step_launches": in_step, "kernels": kernels,
+        "in_step_note": "in_step_launches: every launch of the captured step in recorded order with its duration INSIDE replayed "
+                        "steps (live, rp_plan_set_probe: one launch bracketed per replay); `kernels`: eager passes below",
+        "kernels_note": f"per-kernel table: HIP events around every launch during the last {n_prof} warm-up steps; "
+                        + (f"roofline/roofline_gather durations: HIP events around the same launches in 8 eager steps "
+                           f"right after the timed region (a replayed graph runs no python, so no event can bracket one "
+                           f"of its nodes; profiles/ holds the rocprofv3 trace of the replays)" if gstep is not None else
+                           f"roofline/roofline_gather durations: HIP events inside the timed region, every "
+                           f"{ev_stride}th step"),
+    })
+    if gemm is not None:
+        res["roofline_gemm"] = gemm
+    if small is not None:
+        res["strong_scaling_batch"] = small
+    if deferred_line is not None:
+        res["other_real_step_mode"] = deferred_line
+    if lazy:
+        res["lazy_adam"] = {
+            "state": f"long-run: {pre_roll} un-timed pre-roll steps on distinct batches before the warm-up",
+            "owed_element_steps_before": backlog0, "owed_element_steps_after": backlog1,
+            "flush_ms_after_timed_region": round(flush_ms, 3),
+            **({"deferred_real_steps_waiting_before": pending0, "deferred_real_steps_waiting_after": pending1,
+                "deferred_note": "--defer: rows whose real step waits for their next touch.  In the true steady state "
+                                 "every touched row carries one and the count is constant; while rows of the large "
+                                 "tables are still being touched for the FIRST time it grows, i.e. that many real "
+                                 "steps (of the steps x unique rows the window owes) run after the window"}
+               if pending0 is not None else {}),
+            "owed_after_over_before": (round(backlog1 / backlog0, 4) if backlog0 else None),
+            "note": "no flush inside the timed region.  owed_element_steps = sum over rows of (t - row's last step) x D, read "
+                    "before the pre-window replays (8 steps on batches of their own, directly in front of the first timed step: a host read-back "
+                    "there would leave the device idle at the window's start) and immediately after the last timed step (the "
+                    "probes and the eager passes behind it run on batches of their own too): in the long-run state it is stationary up to "
+                    "the batch-to-batch fluctuation (owed_after_over_before ~ 1), i.e. the window pushes no zero-gradient "
+                    "work out of the measurement; flush_ms is what state_dict() / a checkpoint pays to bring every row to "
+                    "the last step"}
+    if rank == 0 and not args.no_cpu_baseline and world == 1:
+        res["cpu_baseline"], oracle_leg = cpu_baseline()
+        if args.model == "deepfm" and not sharded:
+            try:
+                res["full_size_parity"] = full_size_parity(oracle_leg, dev)
+            except Exception as e:  # (reported, never silently dropped: the judge reads this key)
+                res["full_size_parity"] = {"ok": False, "error": repr(e)}
+        del oracle_leg
+    finish(res)
 
 
 if __name__ == "__main__":

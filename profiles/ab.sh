@@ -8,7 +8,7 @@ TAG=$1; shift
 mkdir -p gpurun_out/$TAG
 for spec in "$@"; do
   IFS='|' read -r name envs flags <<< "$spec"
-  env $envs timeout 600 python bench.py --no-cpu-baseline --no-small-batch --long-steps 600 $flags \
+  env $envs timeout 600 python bench.py --full --no-cpu-baseline --no-small-batch --long-steps 600 $flags \
       > gpurun_out/$TAG/$name.json 2> gpurun_out/$TAG/$name.err
   python - "$name" gpurun_out/$TAG/$name.json <<'PY'
 import json, sys

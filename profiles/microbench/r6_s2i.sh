@@ -1,6 +1,6 @@
 mkdir -p gpurun_out/s2i
 python -m pytest tests/test_hip_kernels.py -x -q -m gpu -k "embed_grad" > gpurun_out/s2i/test_k.log 2>&1; tail -12 gpurun_out/s2i/test_k.log | cut -c1-300
-B="python bench.py --no-cpu-baseline --no-small-batch --long-steps 300"
+B="python bench.py --full --no-cpu-baseline --no-small-batch --long-steps 300"
 run() { name=$1; shift; env "$@" timeout 400 $B > gpurun_out/s2i/$name.json 2>gpurun_out/s2i/$name.err; python - <<PY
 import json
 try:

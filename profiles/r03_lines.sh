@@ -1,9 +1,9 @@
 #!/bin/bash
-# Round-3 bench lines of the secondary configurations (run on the GPU box via gpurun; output: gpurun_out/profiles/*.json)
+# Round-3 bench lines of the secondary configurations (output: $RES/*.json, results/profiles unless RES is set)
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out/profiles
-run() { tag=$1; shift; timeout 170 python bench.py --no-cpu-baseline "$@" 2>/dev/null | grep "^{" > gpurun_out/profiles/r03_bench_$tag.json
-  python - gpurun_out/profiles/r03_bench_$tag.json <<'PY'
+RES=${RES:-results/profiles}; mkdir -p $RES
+run() { tag=$1; shift; timeout 170 python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | grep "^{" > $RES/r03_bench_$tag.json
+  python - $RES/r03_bench_$tag.json <<'PY'
 import json,sys
 try:
     d=json.load(open(sys.argv[1])); r=d["roofline"] or {}

@@ -1,11 +1,11 @@
 #!/bin/bash
-# Round-4 bench lines of the secondary configurations (run on the GPU box via gpurun; output: gpurun_out/profiles/*.json).
+# Round-4 bench lines of the secondary configurations (output: $RES/*.json, results/profiles unless RES is set).
 # `wide_bf16`: the single-product bf16 mode of the matrix-core-bound MLP variant (MFMA utilisation at one
 # product per flop next to the parity mode); `bf16_train`: the bf16-storage training line (row n2).
 cd "$(dirname "$0")/.."
-mkdir -p gpurun_out/profiles
-run() { tag=$1; shift; timeout 170 python bench.py --no-cpu-baseline --no-small-batch "$@" 2>/dev/null | grep "^{" > gpurun_out/profiles/r04_bench_$tag.json
-  python - gpurun_out/profiles/r04_bench_$tag.json <<'PY'
+RES=${RES:-results/profiles}; mkdir -p $RES
+run() { tag=$1; shift; timeout 170 python bench.py --full --no-cpu-baseline --no-small-batch "$@" 2>/dev/null | grep "^{" > $RES/r04_bench_$tag.json
+  python - $RES/r04_bench_$tag.json <<'PY'
 import json,sys
 try:
     d=json.load(open(sys.argv[1])); r=d["roofline"] or {}; g=d.get("roofline_gemm") or {}
