@@ -68,7 +68,7 @@ int rp_get_matmul_precision(void);
 typedef void *rp_stream_t;
 
 /* ---- library ------------------------------------------------------------------------------ */
-#define RP_ABI_VERSION 106 /* rp_version(): bumped with every change of an entry point's prototype (106 = round 6) */
+#define RP_ABI_VERSION 107 /* rp_version(): bumped with every change of an entry point's prototype (csrc/common.hip) */
 int rp_version(void);
 const char *rp_last_error(void);
 /* number of kernel launches issued through this library since load (tests use it to prove the
@@ -853,11 +853,7 @@ int rp_plan_bind_report(void *plan, const uint64_t *addrs, const uint64_t *nbyte
  * foreign work issued by the caller in between on the same stream (every launch of the segment on that one stream, in
  * recorded order, whatever section it was recorded under). */
 int rp_plan_host_mark(int *index_out);
-int rp_plan_host_marks(void *plan, int *n_marks);
 int rp_plan_replay_segment(void *plan, int seg, rp_stream_t stream);
-/* the main stream waits HERE for the side section (1) of the replay (default: at the end of the replay) — for a step that
- * itself consumes what the side section produces (the next batch's sorted keys: graph_step.py, catch-up ahead) */
-int rp_plan_join_side(void);
 /* the inline section (2) waits here for what the main stream holds at this point (a second dependency edge for a section
  * forked earlier; the fork mark while the section is not open yet) */
 int rp_plan_side2_sync(void);

@@ -165,24 +165,6 @@ extern "C" int rp_plan_fork2_mark(void) {
     return RP_OK;
 }
 
-// The main stream waits HERE for the side section (1) of the replay it is part of — for a step that consumes the next
-// batch's sort itself (the optimizer catch-up of the next batch's rows issued at the END of the step, graph_step.py
-// "catch-up ahead").  Without this marker the side section is joined at the end of the replay.  Marker node, section -4.
-extern "C" int rp_plan_join_side(void) {
-    std::lock_guard<std::mutex> lock(g_mu);
-    Plan *p = g_recording.load();
-    RP_REQUIRE(p != nullptr, "plan_join_side: no plan is being recorded");
-    PlanNode n;
-    n.func = nullptr;
-    n.grid = n.block = dim3(0, 0, 0);
-    n.shmem = 0;
-    n.section = -4;
-    n.rec_stream = nullptr;
-    n.blob_at = p->blob.size();
-    p->nodes.push_back(std::move(n));
-    return RP_OK;
-}
-
 // The inline section (2) waits HERE for what the main stream holds at this point — a second dependency edge for a section
 // that was forked earlier (round 6: the tiny tables' gradient is forked in front of the sample-major launch and runs beside
 // it; the launches behind the sample-major one follow on the same side stream and need that launch).  While the section is
@@ -223,13 +205,6 @@ extern "C" int rp_plan_host_mark(int *index_out) {
     p->nodes.push_back(std::move(n));
     if (index_out != nullptr) *index_out = p->n_marks;
     p->n_marks++;
-    return RP_OK;
-}
-
-extern "C" int rp_plan_host_marks(void *plan, int *n_marks) {
-    Plan *p = reinterpret_cast<Plan *>(plan);
-    RP_REQUIRE(p && n_marks, "plan_host_marks: null pointer");
-    *n_marks = p->n_marks;
     return RP_OK;
 }
 
@@ -545,7 +520,7 @@ extern "C" int rp_plan_replay(void *plan, rp_stream_t stream) {
         if (e == hipSuccess) e = hipEventCreateWithFlags(&p->ev_sync2, plan_event_flags());
         if (e != hipSuccess) return rp_fail(RP_ERR_LAUNCH, "plan_replay: second side stream: %s", hipGetErrorString(e));
     }
-    bool forked = false, open2 = false, main_since_fork2 = false, side_joined = false, marked2 = false;
+    bool forked = false, open2 = false, main_since_fork2 = false, marked2 = false;
     auto timed = [p](int kind, size_t node, auto &&call) -> hipError_t {
         const double t0 = plan_now_ms();
         const hipError_t r = call();
@@ -603,28 +578,12 @@ extern "C" int rp_plan_replay(void *plan, rp_stream_t stream) {
             }
             continue;
         }
-        if (n.func == nullptr && n.section == -4) {  // the main stream needs the side section's results from here on
-            if (forked && !side_joined) {
-                e = timed(2, i, [&] { return hipStreamWaitEvent(s, p->ev_join, 0); });
-                if (e != hipSuccess) return rp_fail(RP_ERR_LAUNCH, "plan_replay: join of the side section: %s", hipGetErrorString(e));
-                side_joined = true;
-            }
-            continue;
-        }
         if (n.func == nullptr) {  // join marker of the inline section
             marked2 = false;
             if (open2) {
-                // the side section (issued at its fork point, long done by now) is joined through the same wait: every
-                // event operation on the main stream is a packet its next launch queues behind
-                // (round 5: only on request — with the side streams at the lowest priority the sort is no longer "long done":
-                //  it ended 10 us AFTER the first layer's backward and held the optimizer up by 34 us, profiles/r05 trace; nothing
-                //  in the step needs it, so it is joined at the end of the replay below)
-                static const bool join_sort_early = getenv("RP_PLAN_JOIN_SORT") && strcmp(getenv("RP_PLAN_JOIN_SORT"), "early") == 0;
-                if (join_sort_early && forked && !side_joined) {
-                    e = timed(2, i, [&] { return hipStreamWaitEvent(p->side2, p->ev_join, 0); });
-                    if (e != hipSuccess) return rp_fail(RP_ERR_LAUNCH, "plan_replay: join of the side section: %s", hipGetErrorString(e));
-                    side_joined = true;
-                }
+                // (the side section is NOT joined here: with the side streams at the lowest priority the sort ended 10 us
+                //  AFTER the first layer's backward and held the optimizer up by 34 us, profiles/r05 trace; nothing in the
+                //  step needs it, so it is joined at the end of the replay below)
                 e = timed(1, i, [&] { return hipEventRecord(p->ev_join2, p->side2); });
                 if (e == hipSuccess) e = timed(2, i, [&] { return hipStreamWaitEvent(s, p->ev_join2, 0); });
                 if (e != hipSuccess) return rp_fail(RP_ERR_LAUNCH, "plan_replay: inline join: %s", hipGetErrorString(e));
@@ -669,7 +628,7 @@ extern "C" int rp_plan_replay(void *plan, rp_stream_t stream) {
         if (e == hipSuccess) e = timed(2, i, [&] { return hipStreamWaitEvent(s, p->ev_join2, 0); });
         if (e != hipSuccess) return rp_fail(RP_ERR_LAUNCH, "plan_replay: inline join: %s", hipGetErrorString(e));
     }
-    if (fork && !side_joined) {
+    if (fork) {
         e = timed(2, i, [&] { return hipStreamWaitEvent(s, p->ev_join, 0); });
         if (e != hipSuccess) return rp_fail(RP_ERR_LAUNCH, "plan_replay: join: %s", hipGetErrorString(e));
     }

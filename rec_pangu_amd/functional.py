@@ -1302,17 +1302,10 @@ class _EmbedGatherLinear(torch.autograd.Function):
         # time and the join comes later
         # (re-measured at the end of round 5, after the loss head moved into the MLP tail and the side streams went to the
         #  lowest priority: main launch first 0.8324 / 0.8375 ms against 0.8369 / 0.8384 in the 20-step window, 0.8086 / 0.8099
-        #  against 0.8152 / 0.8161 over 600 steps — ON by default now; RP_SEG_FIRST=0: the side launches first)
-        seg_first = (in_plan and seg is not None and need_t and not hip.LaunchPlan.ahead
-                     and os.environ.get("RP_SEG_FIRST", "1") == "1")
-        # catch-up ahead (graph_step): the step's last main-stream launch rewrites table rows, so only the tiny tables' gradient
-        # (which READS their rows) runs beside rp_embed_grad_seg and is joined behind it; the weight gradient's dense columns
-        # and the deferred side launches are issued after that join and run beside the catch-up, joined at the end of the replay
-        ahead = in_plan and hip.LaunchPlan.ahead and seg is not None and need_t and not seg_first
+        #  against 0.8152 / 0.8161 over 600 steps)
+        seg_first = in_plan and seg is not None and need_t
         if seg_first:
             pass  # (the fork is marked inside accumulate_grad, behind the sample-major launch: round 6)
-        elif ahead:
-            pass
         elif in_plan:
             hip.LaunchPlan.section(2)
             try:
@@ -1340,19 +1333,7 @@ class _EmbedGatherLinear(torch.autograd.Function):
                 hip.LaunchPlan.run_deferred()
             finally:
                 hip.LaunchPlan.section(0)
-        if ahead:
-            hip.LaunchPlan.join_only()
-            hip.LaunchPlan.section(2)
-            try:
-                dw, db = wgrad(keep)
-                hip.LaunchPlan.run_deferred()
-            finally:
-                hip.LaunchPlan.section(0)
-            # (the workspaces stay alive until the plan is finished: nothing joins them here.  NOT dw / db: a second reference
-            #  makes AccumulateGrad clone them — two memcpy nodes, and the step no longer replays as a plan; graph_step holds
-            #  the parameters' .grad across zero_grad() instead)
-            hip.LaunchPlan._ahead_keep.append(keep)
-        elif in_plan:
+        if in_plan:
             hip.LaunchPlan.join()
             del keep
         if wstream is not None:

@@ -12,7 +12,7 @@ from typing import List, Optional, Sequence
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 106  # csrc/common.hip: rp_version() — bumped with every change of the entry points' prototypes
+ABI_VERSION = 107  # csrc/common.hip: rp_version() — bumped with every change of the entry points' prototypes
 LIB_PATH = os.environ.get("RP_LIB_PATH") or os.path.join(_HERE, "lib", "librecpangu_hip.so")  # (override: A/B builds)
 MAX_FIELDS = 64
 
@@ -94,9 +94,7 @@ _SIGNATURES = {
     "rp_marker_destroy": (C.c_int, [_vp]),
     "rp_plan_slowest_call": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int]),
     "rp_plan_launch_name": (C.c_int, [_vp, _i32, C.c_char_p, _i32, C.POINTER(_i32)]),
-    "rp_plan_join_side": (C.c_int, []),
     "rp_plan_host_mark": (C.c_int, [C.POINTER(_i32)]),
-    "rp_plan_host_marks": (C.c_int, [_vp, C.POINTER(_i32)]),
     "rp_plan_replay_segment": (C.c_int, [_vp, _i32, _vp]),
     "rp_fill_words": (C.c_int, [_vp, _i64, C.c_uint32, _vp]),
     "rp_plan_side2_sync": (C.c_int, []),
@@ -1095,7 +1093,7 @@ class LaunchPlan:
         LaunchPlan._recording = None
         if LaunchPlan._deferred and LaunchPlan.is_recording():
             LaunchPlan.join()  # (nobody joined the inline section after the last deferred launch was queued)
-        LaunchPlan._deferred, LaunchPlan._kept, LaunchPlan._ahead_keep = [], [], []
+        LaunchPlan._deferred, LaunchPlan._kept = [], []
         _check(lib().rp_plan_end(self._h), "rp_plan_end")
         a, b, c = _i32(), _i32(), _i32()
         _check(lib().rp_plan_info(self._h, C.byref(a), C.byref(b), C.byref(c)), "rp_plan_info")
@@ -1159,26 +1157,10 @@ class LaunchPlan:
         _check(lib().rp_plan_join(), "rp_plan_join")
         cls._kept = []
 
-    @classmethod
-    def join_only(cls):
-        """join the inline section as it stands: deferred launches stay queued, what they keep alive stays alive"""
-        _check(lib().rp_plan_join(), "rp_plan_join")
-
     @staticmethod
     def side2_sync():
         """the inline section waits here for what the main stream holds at this point (rp_plan_side2_sync)"""
         _check(lib().rp_plan_side2_sync(), "rp_plan_side2_sync")
-
-    @staticmethod
-    def join_side():
-        """the main stream waits here for the side section (rp_plan_join_side)"""
-        _check(lib().rp_plan_join_side(), "rp_plan_join_side")
-
-    # "catch-up ahead" (graph_step.GraphedTrainStep, recording only): the step catches up the NEXT batch's rows at its end,
-    # beside the dense optimizer step — the first layer's backward then joins only what that launch must not overtake (the
-    # tiny tables' gradient, which reads their rows) and leaves the rest of its side work for the optimizer's side section
-    ahead = False
-    _ahead_keep: list = []
 
     @staticmethod
     def is_recording() -> bool:

@@ -483,11 +483,10 @@ class EmbeddingLayer(nn.Module):
                 seg_args = (sk, sp, B, D, fused[0], seg[0], gfm, ssum, self._arena, self._grad_arena)
                 seg_kw = dict(accumulate=acc, skip_fields=skip, field_rows=self._rows_sig(), dw=seg[1], keep=plan_keep)
                 smp_ws = None
-                # RP_TINY_EARLY=1 (a recorded plan only): the tiny tables' launches are forked IN FRONT of the sample-major
-                # launch and run beside it on the second stream; the launches behind the sample-major one follow them there
+                # (a recorded plan only) the tiny tables' launches are forked IN FRONT of the sample-major launch and run
+                # beside it on the second stream; the launches behind the sample-major one follow them there
                 # (rp_plan_side2_sync: that stream waits for the sample-major launch at that point)
-                tiny_early = bool(smp and tiny and seg_first and in_plan and fork2 is not None
-                                  and os.environ.get("RP_TINY_EARLY", "1") == "1")
+                tiny_early = bool(smp and tiny and seg_first and in_plan and fork2 is not None)
                 if tiny_early:
                     fork2()
                 if smp:
@@ -514,15 +513,12 @@ class EmbeddingLayer(nn.Module):
                     # forked at the mark above (behind the sample-major launch), beside the launches of the row-sorted form; in
                     # ISSUE order behind those: issued in front of them, the 4096 short workgroups of the duplicate reduce held
                     # the segment-sum launch up by 56 us (profiles/r06 trace notes)
-                    # (RP_SMP_BEHIND=main: on the main stream behind everything else of this phase — with the tiny tables'
-                    #  launches in front of them the second stream is the longer one, the main stream idles at the join)
-                    side = in_plan and os.environ.get("RP_SMP_BEHIND", "side") != "main"
-                    if side:
+                    if in_plan:
                         hip.LaunchPlan.section(2)
                     try:
                         hip.embed_grad_smp(*smp_args, accumulate=acc, dw=seg[1], phases=2, ws=smp_ws)
                     finally:
-                        if side:
+                        if in_plan:
                             hip.LaunchPlan.section(0)
             else:
                 if fork2 is not None:
@@ -530,15 +526,8 @@ class EmbeddingLayer(nn.Module):
                 hip.embed_grad_gemm(sk, sp, B, D, fused[0], fused[1], dx, gfm, ssum, self._arena, self._grad_arena,
                                     accumulate=not self._grad_clean, skip_fields=skip)
             if tiny and seg_first:
-                # (behind the long main-stream launch in issue order: see rp_plan_fork2_mark.  Round 6, with the sample-major
-                #  launch in front: on the MAIN stream — the second stream's launches cannot run beside rp_embed_grad_smp /
-                #  _seg, whose workgroups hold all of every CU's LDS, so whatever sits there runs in the step's tail one short
-                #  launch after another while the main stream idles at the join: the tail is split over both streams)
-                if smp and os.environ.get("RP_TINY_MAIN", "1") == "1":
-                    hip.embed_grad_tiny(keys, B, tiny, fused[0], fused[1], gfm, ssum, self._arena, self._grad_arena,
-                                        accumulate=not self._grad_clean, keep=plan_keep, dw=None if seg is None else seg[1])
-                else:
-                    run_tiny()
+                # (no sample-major launch: behind the long main-stream launch in issue order, see rp_plan_fork2_mark)
+                run_tiny()
         else:
             hip.embed_grad_reduce(sk, sp, B, D, dx, gfm, ssum, self._arena, self._grad_arena,
                                   accumulate=not self._grad_clean)
@@ -682,7 +671,7 @@ class EmbeddingLayer(nn.Module):
         shadow = self._shadow_for_training()  # (before the replay below: a rebuild flushes)
         if self._lazy is not None and self._lazy.t > 0:
             keys, sk, sp = self._sorted_keys(idx, self.row_base, self.row_count, src)
-            self._replay_rows(sk)
+            self._lazy.replay(self, sk)
             self._presorted = (keys, sk, sp)
         elif torch.is_grad_enabled():
             self._presorted = self._sorted_keys(idx, self.row_base, self.row_count, src, lookup_only=True)
@@ -691,27 +680,6 @@ class EmbeddingLayer(nn.Module):
         if self.check_indices == "sync":
             self.raise_if_bad_index()
         return out
-
-    def _replay_rows(self, sk) -> None:
-        """the rows of this batch are brought up to date before they are read (LazyAdamRows.replay) — unless the step before
-        this one already did that for exactly this key list (catch_up_ahead)"""
-        done, self._ahead_done = self.__dict__.get("_ahead_done"), None
-        if done is not None and done is sk:
-            return
-        self._lazy.replay(self, sk)
-
-    def catch_up_ahead(self, sk) -> bool:
-        """graph_step's "catch-up ahead": the optimizer catch-up of the NEXT batch's rows (`sk`: its sorted keys, the very
-        tensor its forward will find), issued at the end of the step in progress — after the optimizer step, beside the dense
-        Adam launch.  Same launch, same inputs, earlier: a second catch-up of rows that are already stamped leaves them alone
-        (csrc/adam.hip "DEFERRED execution"), so a forward that does not find this promise just runs its own."""
-        lz = self._lazy
-        if lz is None or not lz.defer or lz.t <= 0:
-            return False
-        with torch.enable_grad():  # (stamps the rows for the step whose backward will write their gradients)
-            lz.replay(self, sk)
-        self._ahead_done = sk
-        return True
 
     def _sorted_keys(self, idx, row_base, row_count, src, lookup_only: bool = False):
         """(keys, sorted keys, positions) of this batch's row requests.  Two layers with the same vocabularies fed the
@@ -891,7 +859,7 @@ class EmbeddingLayer(nn.Module):
             # exact lazy dense Adam: the rows this batch reads must first replay the zero-gradient steps they
             # skipped.  The (row, position) sort the backward needs anyway is done here and reused there.
             keys, sk, sp = self._sorted_keys(idx, row_base, row_count, src if meta is None else None)
-            self._replay_rows(sk)
+            self._lazy.replay(self, sk)
             self._presorted = (keys, sk, sp)
         elif src is not None and meta is None and torch.is_grad_enabled():
             # no replay to do (dense Adam / first step): the backward sorts — unless another layer already has

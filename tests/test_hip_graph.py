@@ -235,23 +235,21 @@ def test_graphed_step_with_a_loader_that_refills_its_buffers_in_place():
 
 
 @pytest.mark.parametrize("kind", ["deepfm64", "deepfm16", "dcn"])
-def test_catch_up_ahead_with_everything_that_can_come_between_two_steps(kind, monkeypatch):
-    """RP_CATCHUP_AHEAD=1: a replayed step ends with the optimizer catch-up of the NEXT batch's rows (graph_step.py) — the
-    rows are then stamped 'gradient coming' across the step boundary.  Everything a training loop does between two steps
-    must leave the run bit-identical to the eager loop: an unannounced batch (the promise is dropped: the stamped rows must
-    read as zero gradients), the last batch of an epoch (no next batch: an eager step), an evaluation forward of other rows,
-    a state_dict() (flushes the lazy state), a change of the learning rate."""
+def test_replayed_step_with_everything_that_can_come_between_two_steps(kind, monkeypatch):
+    """A replayed step (launch plan, deferred lazy table optimizer) next to everything a training loop does between two
+    steps must leave the run bit-identical to the eager loop: an unannounced batch (staged and sorted on the spot), the last
+    batch of an epoch (no next batch: an eager step), an evaluation forward of other rows, a state_dict() (flushes the lazy
+    state), a change of the learning rate."""
     from rec_pangu_amd.graph_step import GraphedTrainStep
     from rec_pangu_amd.optim import FusedAdam
     from rec_pangu_amd.models.layers.embedding import EmbeddingLayer
-    monkeypatch.setenv("RP_CATCHUP_AHEAD", "1")
     monkeypatch.setenv("RP_GRAPH_BACKEND", "plan")
     enc = _enc(3, [500, 9, 4000, 30, 12000])
     batches = _batches(enc, 320, 40, seed=11)
     # (current, announced next, what happens AFTER the step)
     order = [(i, i + 1, None) for i in range(6)] + [(6, 7, "eval"), (7, 8, None), (8, 9, "state_dict"), (9, 10, None),
              (10, 30, None),        # announces 30 ...
-             (11, 12, None),        # ... but 11 arrives: the promise for 30's rows is dropped
+             (11, 12, None),        # ... but 11 arrives: it is staged and sorted on the spot
              (12, 13, "lr"), (13, 14, None), (14, None, None),  # end of an epoch
              (20, 21, None), (21, 22, "eval"), (22, 23, None), (23, 24, None)]
     finals, preds = {}, {}
@@ -286,7 +284,7 @@ def test_catch_up_ahead_with_everything_that_can_come_between_two_steps(kind, mo
             finals[mode] = {k: v.clone() for k, v in model.state_dict().items()}
             preds[mode] = seen
             if gstep is not None:
-                assert gstep._ahead_used and gstep.backend_used == "plan", (gstep._ahead_used, gstep.backend_used, gstep.why_not_plan)
+                assert gstep.backend_used == "plan", (gstep.backend_used, gstep.why_not_plan)
                 assert gstep.replays >= len(order) - 2 - 3
     finally:
         EmbeddingLayer.unpin_sorts()
