@@ -40,8 +40,8 @@ cur, nxt = bs[200], bs[201]
 model.prefetch(cur); step(bs[199], None)  # cur's sort is in the cache now
 torch.cuda.synchronize()
 for e in E._SORT_CACHE:
-    e[4] = None
-side = E._SIDE_STREAMS[dev]
+    e.event = None
+side = E._side_stream(dev)
 g = torch.cuda.CUDAGraph()
 try:
     with torch.cuda.graph(g):

@@ -1115,7 +1115,7 @@ class _EmbedGather(torch.autograd.Function):
     def forward(ctx, store, idx: List[torch.Tensor], dense: List[torch.Tensor], ldx: int, want_fm: bool, meta,
                 *tables):
         need_grad = any(ctx.needs_input_grad[6:])
-        pre = store._presorted  # set by the lazy-Adam replay: keys already computed and sorted for this batch
+        pre = store._presorted  # the batch's SortedLookup where the lazy-Adam replay (or another layer) already sorted it
         store._presorted = None
         row_base, row_count = meta if meta is not None else (store.row_base, store.row_count)
         x, fm, ssum, keys = hip.embed_gather_fwd(store.arena, row_base, row_count, idx, dense, ldx,
@@ -1125,9 +1125,9 @@ class _EmbedGather(torch.autograd.Function):
         # link to the first Linear that consumes x (DeepFM passes it on as `fm_link`): FM fold / fused dgrad
         ctx.link = store._fm_link = FMFold(ssum, len(idx) * store.embedding_dim, store.embedding_dim) \
             if (need_grad and meta is None) else None
-        ctx.presorted = None if (pre is None or not need_grad) else (pre[1], pre[2])
+        ctx.presorted = pre if need_grad else None
         if pre is not None:
-            keys = pre[0] if need_grad else None
+            keys = pre.keys if need_grad else None
         ctx.save_for_backward(keys, ssum)
         if want_fm:
             return x, fm
@@ -1165,15 +1165,19 @@ class _EmbedGather(torch.autograd.Function):
 _WGRAD_STREAMS: dict = {}
 
 
+def _side2_stream(device):
+    st = _WGRAD_STREAMS.get(device)
+    if st is None:
+        st = _WGRAD_STREAMS[device] = hip.make_side_stream(device, "inline")
+    return st
+
+
 def _wgrad_stream(device):
     """the stream the first layer's weight gradient runs on beside the gather backward (RP_WGRAD_OVERLAP=0: none); never
     inside a stream capture (a fork inside a captured graph is replayed without overlap anyway)"""
     if os.environ.get("RP_WGRAD_OVERLAP", "1") == "0" or torch.cuda.is_current_stream_capturing():
         return None
-    st = _WGRAD_STREAMS.get(device)
-    if st is None:
-        st = _WGRAD_STREAMS[device] = hip.make_side_stream(device, "inline")
-    return st
+    return _side2_stream(device)
 
 
 class _EmbedGatherLinear(torch.autograd.Function):
@@ -1213,9 +1217,9 @@ class _EmbedGatherLinear(torch.autograd.Function):
                                                                      dense_only=seg16)
             ctx.store, ctx.B, ctx.K, ctx.out_link, ctx.has_bias = store, B, K, out_link, bias is not None
             ctx.ldx, ctx.x_mode, ctx.Kg, ctx.need_tables = ldx, ("seg" if seg16 else "bf16"), Kg, need_grad
-            ctx.presorted = None if (pre is None or not need_grad) else (pre[1], pre[2])
+            ctx.presorted = pre if need_grad else None
             if pre is not None:
-                keys = pre[0]
+                keys = pre.keys
             ctx.save_for_backward(keys, ssum, x, h1, weight)
             store._fm_link = None
             return h1, fm
@@ -1242,9 +1246,9 @@ class _EmbedGatherLinear(torch.autograd.Function):
                                                             x_mode="dense" if x_mode == "seg" else x_mode)
         ctx.store, ctx.B, ctx.K, ctx.out_link, ctx.has_bias = store, B, K, out_link, bias is not None
         ctx.ldx, ctx.x_mode, ctx.Kg, ctx.need_tables = ldx, x_mode, Kg, need_grad
-        ctx.presorted = None if (pre is None or not need_grad) else (pre[1], pre[2])
+        ctx.presorted = pre if need_grad else None
         if pre is not None:
-            keys = pre[0] if (need_grad or x_mode == "dense") else None
+            keys = pre.keys if (need_grad or x_mode == "dense") else None
         ctx.save_for_backward(keys, ssum, x, h1, weight)
         store._fm_link = None
         return h1, fm

@@ -291,7 +291,7 @@ class GraphedTrainStep:
                     if plan is not None:
                         plan.section(1)
                     if not self._sharded:
-                        self.model.embedding_layer._sort_into(self.X[1 - P], self._pinned(1 - P), on_side_stream=False)
+                        self.model.embedding_layer._sort_into(self.X[1 - P], self._pinned(1 - P))
                     if plan is not None:
                         plan.section(0)
             finally:
@@ -335,13 +335,7 @@ class GraphedTrainStep:
                 # a stream of the plan's own may share the main stream's hardware queue (csrc/plan.hip)
                 from . import functional as _Fh
                 dev = next(iter(self.X[0].values())).device
-                side = _emb._SIDE_STREAMS.get(dev)
-                if side is None:
-                    side = _emb._SIDE_STREAMS[dev] = hip.make_side_stream(dev)
-                side2 = _Fh._WGRAD_STREAMS.get(dev)
-                if side2 is None:
-                    side2 = _Fh._WGRAD_STREAMS[dev] = hip.make_side_stream(dev, "inline")
-                plan.set_streams(side, side2)
+                plan.set_streams(_emb._side_stream(dev), _Fh._side2_stream(dev))
                 if self.rebind:
                     # an argument that points INSIDE a static input (a derived pointer: an offset view, a column of
                     # a packed buffer) cannot be re-pointed — such a step keeps the staging copy.  (An input no launch reads
@@ -381,11 +375,10 @@ class GraphedTrainStep:
         return emb.check_indices == "deferred" and emb._capacity is not None and n <= emb._capacity_n
 
     def _pinned(self, Q):
-        src = tuple(self.X[Q][c] for c in self.model.embedding_layer.emb_feature)
-        for c_src, _, c_out in _emb._SORT_PINNED:
-            if len(c_src) == len(src) and all(a is b for a, b in zip(c_src, src)):
-                return c_out
-        raise RuntimeError("GraphedTrainStep: the static batch lost its pinned sort buffers")
+        look = self.model.embedding_layer.pinned_sort(self.X[Q])
+        if look is None:
+            raise RuntimeError("GraphedTrainStep: the static batch lost its pinned sort buffers")
+        return look
 
     def _lazy_states(self):
         return [st._lazy for st in getattr(self.opt, "_stores", {}).values() if getattr(st, "_lazy", None) is not None]

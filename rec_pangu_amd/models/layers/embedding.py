@@ -25,25 +25,79 @@ from torch import nn
 
 from ... import functional as Fh
 
-# the last two (id tensors, versions, arena signature) -> (keys, sorted keys, positions)[, side-stream event]: the batch in
-# flight and the one whose sort was started ahead (EmbeddingLayer._sorted_keys / prefetch_sort)
+
+class SortedLookup:
+    """The sorted lookup of one batch and everything made from it: `keys` (arena row of every (field, sample) pair), their
+    sort (`sk` sorted keys, `sp` positions), what identifies the batch (`src` id tensors, their `versions` at sort time,
+    `sig` = (rows per table, device)), the side-stream `event` of a sort started ahead, and the marks the three-form backward
+    wants: `smp` (rp_embed_grad_smp's duplicate marks, made for `smp_sig` = (B, big tables)) and `ss` = (skip mask,
+    rp_embed_grad_ss's unique-row lists).  The marks live and die with the sort they describe.
+
+    A PINNED lookup (graph_step.GraphedTrainStep) belongs to STATIC id tensors that are refilled in place: its tensors are
+    persistent and re-sorted / re-marked IN PLACE (a recorded step holds all their addresses), it is matched by identity
+    only (a refill bumps the versions) and carries no event (the order is the capture's).  `workspace`: its persistent sort
+    workspace — a captured step's re-sort must not allocate (its launches may be re-issued on a side stream, where memory
+    of the capture's pool could alias the step's temporaries); `want_marks`: whether a re-sort also re-makes the marks."""
+    __slots__ = ("keys", "sk", "sp", "src", "versions", "sig", "event", "pinned", "workspace", "want_marks",
+                 "smp_sig", "smp", "ss")
+
+    def __init__(self, keys, sk, sp, src=None, sig=None, event=None, pinned=False, workspace=None, want_marks=True):
+        self.keys, self.sk, self.sp, self.src, self.sig, self.event = keys, sk, sp, src, sig, event
+        self.versions = None if src is None else tuple(t._version for t in src)
+        self.pinned, self.workspace, self.want_marks = pinned, workspace, want_marks
+        self.smp_sig = self.smp = self.ss = None
+
+    def matches(self, src, sig) -> bool:
+        """the sort of these very id tensors (identity) for this arena — and, unless pinned, of their current content"""
+        return (self.sig == sig and len(self.src) == len(src) and all(a is b for a, b in zip(self.src, src))
+                and (self.pinned or self.versions == tuple(t._version for t in src)))
+
+    def wait_on(self, stream) -> None:
+        """sorted ahead on the side stream: order `stream` behind it and tell the allocator who uses the tensors now"""
+        if self.event is None:
+            return
+        stream.wait_event(self.event)
+        for t in (self.keys, self.sk, self.sp) + (self.smp or ()) + (self.ss[1] if self.ss else ()):
+            t.record_stream(stream)
+        self.event = None
+
+    def mark(self, B: int, smp, skip) -> None:
+        """(re-)make the marks behind the sort, on the current stream: the duplicate marks of the big tables `smp` and — `skip`
+        not None — the unique-row lists of the fields outside `skip`; in place where buffers of that signature are held"""
+        from ... import hip
+        sig = (B, tuple(smp))
+        same = self.smp_sig == sig
+        self.smp = hip.embed_grad_smp_mark(self.sk, self.sp, B, [t[0] for t in smp], out=self.smp if same else None)
+        self.smp_sig = sig
+        if skip is None:
+            self.ss = None
+        else:
+            out = self.ss[1] if (same and self.ss is not None and self.ss[0] == skip) else None
+            self.ss = (skip, hip.embed_grad_ss_mark(self.sk, B, skip, out=out))
+
+    def ss_lists(self, skip: int):
+        """the unique-row lists made with the sort for exactly these kept fields, or None (rp_embed_grad_ss makes its own)"""
+        return self.ss[1] if (self.ss is not None and self.ss[0] == skip) else None
+
+
+# the unpinned lookups of the last four batches (the batch in flight, the one whose sort was started ahead): two layers with
+# the same vocabularies share one sort through it (EmbeddingLayer._sorted_keys / prefetch_sort)
 _SORT_CACHE: list = []
+_SORT_PINNED: list = []   # the pinned lookups (EmbeddingLayer.pin_sort): never evicted, dropped by unpin_sorts
 _SIDE_STREAMS: dict = {}  # device -> the stream sorts started ahead run on
-# PINNED entries (graph_step.GraphedTrainStep): the id tensors are STATIC input buffers that are refilled in place, the
-# (keys, sorted keys, positions) tensors are persistent and re-sorted IN PLACE by prefetch_sort — a captured hipGraph
-# holds all their addresses.  Matched by identity only (a refill bumps the versions), never evicted, no events (the
-# order is the capture's: the side stream is joined before the capture ends).
-_SORT_PINNED: list = []
-# id(keys tensor of a pinned entry) -> its persistent sort workspace: a captured step's re-sort must not allocate (its
-# launches may be re-issued on a side stream, where memory of the capture's pool could alias the step's temporaries)
-_PINNED_WS: dict = {}
-_PINNED_MARKS: dict = {}  # id(pinned key buffer) -> the duplicate marks / unique-row lists are made with its sort
 
-# id(sorted-keys tensor) -> [weakref(sorted keys), (B, fields), (dupq, dupkeys)]: the marks rp_embed_grad_smp wants, made
-# right behind the sort that made the keys (EmbeddingLayer._mark_sorted: on the sort's stream, one step ahead when the sort
-# is) and re-made in place when a pinned entry is re-sorted in place
-_SMP_MARKS: dict = {}
 
+def _side_stream(dev):
+    from ... import hip
+    side = _SIDE_STREAMS.get(dev)
+    if side is None:
+        side = _SIDE_STREAMS[dev] = hip.make_side_stream(dev)  # (a high-priority stream measured no better)
+    return side
+
+
+def _find_sort(src, sig, cached: bool = True):
+    """the pinned lookup of these id tensors, else (`cached`) the cached one of their current content, else None"""
+    return next((look for look in (_SORT_PINNED + _SORT_CACHE if cached else _SORT_PINNED) if look.matches(src, sig)), None)
 
 
 class DeferredGradView(torch.Tensor):
@@ -134,7 +188,7 @@ class EmbeddingLayer(nn.Module):
         self._noclear_ok = True  # every gradient launch of this layer writes ALL rows of its key list (LazyAdamRows.replay)
         self._dev_meta = None
         self._lazy = None        # optim.LazyAdamRows when the optimiser runs the exact lazy dense Adam
-        self._presorted = None   # (keys, sorted keys, sorted positions) of the batch being looked up
+        self._presorted = None   # the SortedLookup of the batch being looked up
         self._fm_link = None     # functional.FMFold of the last gather that produced an FM term
         self._tag_tables()
         self.register_state_dict_pre_hook(lambda module, prefix, keep_vars: module.flush_lazy())
@@ -350,55 +404,28 @@ class EmbeddingLayer(nn.Module):
         self.__dict__["_smp_cache"] = (sig, B, out)
         return out
 
-    def _mark_sorted(self, sk, sp, force: bool = False) -> None:
+    def _mark_sorted(self, look: SortedLookup, force: bool = False) -> None:
         """behind a sort of this layer's pairs (on the stream that sorted them): the duplicate marks of the big tables.  Only for
         a layer whose backward has taken the three-form path before (`_marks_wanted`, set by accumulate_grad) — DCN, xDeepFM,
         AutoInt and MMOE reduce through rp_embed_grad_reduce and made six launches' worth of marks per step for nobody."""
-        from ... import hip
         if not (force or getattr(self, "_marks_wanted", False)):
             return
-        F = len(self.emb_feature)
-        if sk.numel() == 0 or sk.numel() % F:
-            return
-        B = sk.numel() // F
-        smp = self._smp_tables(B)
+        F, n = len(self.emb_feature), look.sk.numel()
+        smp = self._smp_tables(n // F) if (n > 0 and n % F == 0) else None
         if smp is None:
             return
-        ent = _SMP_MARKS.get(id(sk))
-        sig = (B, tuple(smp))
-        same = ent is not None and ent[0]() is sk and ent[1] == sig
-        out = ent[2] if same else None
-        marks = hip.embed_grad_smp_mark(sk, sp, B, [t[0] for t in smp], out=out)
         # ... and the unique-row lists of the mid-size tables (every field that is neither tiny nor big: rp_embed_grad_ss)
         skip = 0
         for f, _, _ in list(self._tiny_tables() or ()) + list(smp):
             skip |= 1 << f
-        ss = None
-        if skip != (1 << F) - 1 and os.environ.get("RP_GRAD_SS", "1") != "0" and os.environ.get("RP_SS_MARK_AHEAD", "1") != "0":
-            ss_out = ent[3][1] if (same and len(ent) > 3 and ent[3] is not None and ent[3][0] == skip) else None
-            ss = (skip, hip.embed_grad_ss_mark(sk, B, skip, out=ss_out))
-        if out is None:
-            if len(_SMP_MARKS) >= 8:
-                for k in [k for k, e in _SMP_MARKS.items() if e[0]() is None] or list(_SMP_MARKS)[:4]:
-                    _SMP_MARKS.pop(k, None)
-            _SMP_MARKS[id(sk)] = [weakref.ref(sk), sig, marks, ss]
-        else:
-            ent[3:] = [ss]
+        ss = skip != (1 << F) - 1 and os.environ.get("RP_GRAD_SS", "1") != "0" and os.environ.get("RP_SS_MARK_AHEAD", "1") != "0"
+        look.mark(n // F, smp, skip if ss else None)
 
-    def _marks_of(self, sk, sp, smp, B: int):
-        ent = _SMP_MARKS.get(id(sk))
+    def _marks_of(self, look: SortedLookup, smp, B: int):
         self._marks_wanted = True
-        if ent is None or ent[0]() is not sk or ent[1] != (B, tuple(smp)):
-            self._mark_sorted(sk, sp, force=True)  # (a sort nobody marked: an eager backward that sorted for itself)
-            ent = _SMP_MARKS[id(sk)]
-        return ent[2]
-
-    def _ss_marks_of(self, sk, skip: int):
-        """the unique-row lists made with the sort for exactly these kept fields, or None (rp_embed_grad_ss makes its own)"""
-        ent = _SMP_MARKS.get(id(sk))
-        if ent is None or ent[0]() is not sk or len(ent) < 4 or ent[3] is None or ent[3][0] != skip:
-            return None
-        return ent[3][1]
+        if look.smp_sig != (B, tuple(smp)):
+            self._mark_sorted(look, force=True)  # (a sort nobody marked: an eager backward that sorted for itself)
+        return look.smp
 
     def accumulate_grad(self, keys, B: int, dx, gfm, ssum, presorted=None, fused=None, pool=None, plan_keep=None, seg=None,
                         seg_first: bool = False, fork2=None):
@@ -423,10 +450,8 @@ class EmbeddingLayer(nn.Module):
         if pool is not None and presorted is None:  # pooled multi-id lookup of one table: keys of its flat id list
             f = pool[4]
             keys = hip.embed_keys(self.row_base[f:f + 1], self.row_count[f:f + 1], [pool[5]], self.err_flag)
-        if presorted is not None:
-            sk, sp = presorted
-        else:
-            sk, sp = hip.sort_pairs(keys, end_bit=self._meta()[3])
+        look = presorted if presorted is not None else SortedLookup(keys, *hip.sort_pairs(keys, end_bit=self._meta()[3]))
+        sk, sp = look.sk, look.sp
         if self._lazy is not None and self._lazy._noclear is not None:
             # the catch-up launch in front of this step's forward left its applied gradient rows uncleared, counting on
             # THIS launch to overwrite them (LazyAdamRows.replay): kept if it writes that key list without accumulating
@@ -490,12 +515,12 @@ class EmbeddingLayer(nn.Module):
                 if tiny_early:
                     fork2()
                 if smp:
-                    marks = self._marks_of(sk, sp, smp, B)
+                    marks = self._marks_of(look, smp, B)
                     smp_args = (keys, marks, B, len(self.emb_feature), smp, fused[0], seg[0], gfm, ssum, self._arena,
                                 self._grad_arena)
                     smp_ws = hip.embed_grad_smp(*smp_args, accumulate=acc, dw=seg[1], keep=plan_keep, phases=1)
                 if ss:  # (the unique-row lists made with the sort — or just now, by _marks_of, for a sort nobody had marked)
-                    seg_kw["marks"] = self._ss_marks_of(sk, skip)
+                    seg_kw["marks"] = look.ss_lists(skip)
                 if tiny_early:
                     run_tiny()
                     hip.LaunchPlan.side2_sync()
@@ -670,9 +695,8 @@ class EmbeddingLayer(nn.Module):
         self._presorted = None
         shadow = self._shadow_for_training()  # (before the replay below: a rebuild flushes)
         if self._lazy is not None and self._lazy.t > 0:
-            keys, sk, sp = self._sorted_keys(idx, self.row_base, self.row_count, src)
-            self._lazy.replay(self, sk)
-            self._presorted = (keys, sk, sp)
+            self._presorted = self._sorted_keys(idx, self.row_base, self.row_count, src)
+            self._lazy.replay(self, self._presorted.sk)
         elif torch.is_grad_enabled():
             self._presorted = self._sorted_keys(idx, self.row_base, self.row_count, src, lookup_only=True)
         out = Fh.embed_gather_linear(self, idx, dense, ldx, linear.weight, linear.bias, out_link, shadow=shadow)
@@ -682,40 +706,33 @@ class EmbeddingLayer(nn.Module):
         return out
 
     def _sorted_keys(self, idx, row_base, row_count, src, lookup_only: bool = False):
-        """(keys, sorted keys, positions) of this batch's row requests.  Two layers with the same vocabularies fed the
-        same batch (a model's D-wide tables and its LR_Layer's 1-wide ones) ask for the same arena rows: the second one
-        reuses the first one's sort.  The cache entry keeps the id tensors alive, so `is` + `_version` identify them."""
+        """The SortedLookup of this batch's row requests.  Two layers with the same vocabularies fed the same batch (a
+        model's D-wide tables and its LR_Layer's 1-wide ones) ask for the same arena rows: the second one reuses the first
+        one's sort.  The cache entry keeps the id tensors alive, so `is` + `_version` identify them."""
         from ... import hip
-        sig = (self._rows_sig(), str(self._arena.device))
-        if src is not None:
-            for c_src, c_sig, c_out in _SORT_PINNED:
-                if c_sig == sig and len(c_src) == len(src) and all(a is b for a, b in zip(c_src, src)):
-                    return c_out
-            for entry in _SORT_CACHE:
-                c_src, c_ver, c_sig, c_out, c_event = entry
-                if c_sig == sig and len(c_src) == len(src) and all(a is b for a, b in zip(c_src, src)) \
-                        and c_ver == tuple(t._version for t in src):
-                    if c_event is not None:  # sorted ahead on the side stream: order this stream behind it
-                        cur = torch.cuda.current_stream(self._arena.device)
-                        cur.wait_event(c_event)
-                        for t in c_out:
-                            t.record_stream(cur)
-                        entry[4] = None
-                    return c_out
+        sig = self._sort_sig()
+        look = _find_sort(src, sig) if src is not None else None
+        if look is not None:
+            if look.event is not None:
+                look.wait_on(torch.cuda.current_stream(self._arena.device))
+            return look
         if lookup_only:
             return None
         keys = hip.embed_keys(row_base, row_count, idx, self.err_flag)
         sk, sp = self._sort_pairs(keys) if row_base is self.row_base else hip.sort_pairs(keys, end_bit=self._meta()[3])
+        look = SortedLookup(keys, sk, sp, src, sig)
         if row_base is self.row_base and torch.is_grad_enabled():
-            self._mark_sorted(sk, sp)
-        out = (keys, sk, sp)
+            self._mark_sorted(look)
         if src is not None:
-            self._cache_sort(src, sig, out, None)
-        return out
+            self._cache_sort(look)
+        return look
+
+    def _sort_sig(self):
+        return (self._rows_sig(), str(self._arena.device))
 
     @staticmethod
-    def _cache_sort(src, sig, out, event):
-        _SORT_CACHE.append([src, tuple(t._version for t in src), sig, out, event])
+    def _cache_sort(look: SortedLookup) -> None:
+        _SORT_CACHE.append(look)
         del _SORT_CACHE[:-4]
 
     def prefetch_sort(self, X) -> None:
@@ -733,23 +750,16 @@ class EmbeddingLayer(nn.Module):
         if X is None:
             return
         src = tuple(X[c] for c in self.emb_feature)
-        sig = (self._rows_sig(), str(self._arena.device))
-        pinned = next((c_out for c_src, c_sig, c_out in _SORT_PINNED
-                       if c_sig == sig and len(c_src) == len(src) and all(a is b for a, b in zip(c_src, src))), None)
-        if pinned is not None:
-            # static input buffers of a graphed step: re-sort into the persistent tensors, ON THIS STREAM — their readers
-            # (a captured step's launches, eager forwards that match the pinned entry by identity) take no event from a
-            # side stream (the side-stream form had no join back)
-            self._sort_into(X, pinned, on_side_stream=False)
+        look = _find_sort(src, self._sort_sig())
+        if look is not None:
+            if look.pinned:
+                # static input buffers of a graphed step: re-sort into the persistent tensors, ON THIS STREAM — their readers
+                # (a captured step's launches, eager forwards that match the pinned entry by identity) take no event from a
+                # side stream (the side-stream form had no join back)
+                self._sort_into(X, look)
             return
-        for c_src, c_ver, c_sig, _, _ in _SORT_CACHE:
-            if c_sig == sig and len(c_src) == len(src) and all(a is b for a, b in zip(c_src, src)) \
-                    and c_ver == tuple(t._version for t in src):
-                return
         dev = self._arena.device
-        side = _SIDE_STREAMS.get(dev)
-        if side is None:
-            side = _SIDE_STREAMS[dev] = hip.make_side_stream(dev)  # (a high-priority stream measured no better)
+        side = _side_stream(dev)
         main = torch.cuda.current_stream(dev)
         side.wait_stream(main)  # the id tensors (and whatever produced them) are ordered on the caller's stream
         with torch.cuda.stream(side):
@@ -757,13 +767,13 @@ class EmbeddingLayer(nn.Module):
             # 'sync' mode raises at the step that finds a bad id: the keys of the NEXT batch must not set this step's flag
             # (its own gather checks the same ids again when its turn comes) — they get a scratch flag
             keys = hip.embed_keys(self.row_base, self.row_count, idx, self._ahead_flag())
-            sk, sp = self._sort_pairs(keys)
-            self._mark_sorted(sk, sp)
-            event = torch.cuda.Event()
-            event.record(side)
+            look = SortedLookup(keys, *self._sort_pairs(keys), src, self._sort_sig())
+            self._mark_sorted(look)
+            look.event = torch.cuda.Event()
+            look.event.record(side)
         for t in src:
             t.record_stream(side)
-        self._cache_sort(src, sig, (keys, sk, sp), event)
+        self._cache_sort(look)
 
     def _ahead_flag(self):
         if self.check_indices != "sync":
@@ -784,62 +794,43 @@ class EmbeddingLayer(nn.Module):
             return hip.sort_pairs_fields(keys, n // F, self._rows_sig(), out=out, workspace=workspace)
         return hip.sort_pairs(keys, end_bit=self._meta()[3], out=out, workspace=workspace)
 
-    def _sort_into(self, X, out, on_side_stream: bool) -> None:
+    def _sort_into(self, X, look: SortedLookup) -> None:
+        """re-sort a pinned lookup in place from the current content of its static id tensors, on the current stream"""
         from ... import hip
-        keys, sk, sp = out
-        dev = self._arena.device
-        if not on_side_stream:
-            hip.embed_keys(self.row_base, self.row_count, self._idx_list(X), self.err_flag, out=keys)
-            self._sort_pairs(keys, out=(sk, sp), workspace=_PINNED_WS.get(id(keys)))
-            # (a pinned entry keeps the choice made when it was pinned: marks that first appear inside a recorded step's side
-            #  section would be allocated by the capture behind the step's temporaries and run beside them)
-            if _PINNED_MARKS.get(id(keys), True):
-                self._mark_sorted(sk, sp, force=True)
-            return
-        side = _SIDE_STREAMS.get(dev)
-        if side is None:
-            side = _SIDE_STREAMS[dev] = hip.make_side_stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            hip.embed_keys(self.row_base, self.row_count, self._idx_list(X), self.err_flag, out=keys)
-            self._sort_pairs(keys, out=(sk, sp))
-            self._mark_sorted(sk, sp)
+        hip.embed_keys(self.row_base, self.row_count, self._idx_list(X), self.err_flag, out=look.keys)
+        self._sort_pairs(look.keys, out=(look.sk, look.sp), workspace=look.workspace)
+        # (a pinned entry keeps the choice made when it was pinned: marks that first appear inside a recorded step's side
+        #  section would be allocated by the capture behind the step's temporaries and run beside them)
+        if look.want_marks:
+            self._mark_sorted(look, force=True)
+
+    def pinned_sort(self, X) -> Optional[SortedLookup]:
+        """the pinned lookup of the static batch X, or None"""
+        return _find_sort(tuple(X[c] for c in self.emb_feature), self._sort_sig(), cached=False)
 
     def pin_sort(self, X) -> None:
         """graph_step: X holds STATIC id tensors (refilled in place from now on).  Sort their current content into
         persistent tensors on the current stream and pin the cache entry; later prefetch_sort(X) calls re-sort in place."""
         from ... import hip
-        src = tuple(X[c] for c in self.emb_feature)
-        sig = (self._rows_sig(), str(self._arena.device))
-        for c_src, c_sig, c_out in _SORT_PINNED:
-            if c_sig == sig and len(c_src) == len(src) and all(a is b for a, b in zip(c_src, src)):
-                self._sort_into(X, c_out, on_side_stream=False)
-                return
-        n = sum(t.numel() for t in src)
-        out = tuple(torch.empty((n,), dtype=torch.int32, device=self._arena.device) for _ in range(3))
-        ws = hip.sort_workspace(n, self._arena.device)
-        if n % len(src) == 0 and n > 0:  # (the field-segmented sort's histograms are per field: a few KB more)
-            ws2 = hip.sort_fields_workspace(n // len(src), len(src), self._arena.device)
-            ws = ws2 if ws2.numel() > ws.numel() else ws
-        _PINNED_WS[id(out[0])] = ws
-        _PINNED_MARKS[id(out[0])] = bool(getattr(self, "_marks_wanted", False))
-        self._sort_into(X, out, on_side_stream=False)
-        _SORT_PINNED.append((src, sig, out))
+        look = self.pinned_sort(X)
+        if look is None:
+            src = tuple(X[c] for c in self.emb_feature)
+            n = sum(t.numel() for t in src)
+            ws = hip.sort_workspace(n, self._arena.device)
+            if n % len(src) == 0 and n > 0:  # (the field-segmented sort's histograms are per field: a few KB more)
+                ws2 = hip.sort_fields_workspace(n // len(src), len(src), self._arena.device)
+                ws = ws2 if ws2.numel() > ws.numel() else ws
+            look = SortedLookup(*(torch.empty((n,), dtype=torch.int32, device=self._arena.device) for _ in range(3)),
+                                src, self._sort_sig(), pinned=True, workspace=ws,
+                                want_marks=bool(getattr(self, "_marks_wanted", False)))
+        self._sort_into(X, look)
+        if look not in _SORT_PINNED:
+            _SORT_PINNED.append(look)
 
     @staticmethod
     def unpin_sorts(X=None) -> None:
         """drop the pinned entries of the static batch X (all of them when X is None)"""
-        if X is None:
-            del _SORT_PINNED[:]
-            _PINNED_WS.clear()
-            _PINNED_MARKS.clear()
-        else:
-            ids = {id(t) for t in X.values()}
-            for e in _SORT_PINNED:
-                if any(id(t) in ids for t in e[0]):
-                    _PINNED_WS.pop(id(e[2][0]), None)
-                    _PINNED_MARKS.pop(id(e[2][0]), None)
-            _SORT_PINNED[:] = [e for e in _SORT_PINNED if not any(id(t) in ids for t in e[0])]
+        _SORT_PINNED[:] = [] if X is None else [e for e in _SORT_PINNED if not any(t is x for t in e.src for x in X.values())]
 
     def _rows_sig(self):
         if getattr(self, "_rows_sig_cache", None) is None:
@@ -858,9 +849,8 @@ class EmbeddingLayer(nn.Module):
         if self._lazy is not None and self._lazy.t > 0:
             # exact lazy dense Adam: the rows this batch reads must first replay the zero-gradient steps they
             # skipped.  The (row, position) sort the backward needs anyway is done here and reused there.
-            keys, sk, sp = self._sorted_keys(idx, row_base, row_count, src if meta is None else None)
-            self._lazy.replay(self, sk)
-            self._presorted = (keys, sk, sp)
+            self._presorted = self._sorted_keys(idx, row_base, row_count, src if meta is None else None)
+            self._lazy.replay(self, self._presorted.sk)
         elif src is not None and meta is None and torch.is_grad_enabled():
             # no replay to do (dense Adam / first step): the backward sorts — unless another layer already has
             self._presorted = self._sorted_keys(idx, row_base, row_count, src, lookup_only=True)
@@ -919,7 +909,7 @@ class EmbeddingLayer(nn.Module):
             keys = hip.embed_keys(self.row_base[f:f + 1], self.row_count[f:f + 1], [flat], self.err_flag)
             sk, sp = hip.sort_pairs(keys, end_bit=self._meta()[3])
             self._lazy.replay(self, sk)
-            presorted = (sk, sp)
+            presorted = SortedLookup(keys, sk, sp)
         out = Fh.embed_gather_pool(self, f, flat, offsets, L, B, pooling, presorted)
         if self.check_indices == "sync":
             self.raise_if_bad_index()

@@ -431,3 +431,76 @@ def test_graphed_step_with_row_sharded_tables_single_rank(force_a2a, ahead, back
     finally:
         torch.cuda.synchronize()
         dist.destroy_process_group()
+
+
+def _defined_marks(smp, ss, B, n_smp, n_kept):
+    """what the mark launches define of their buffers: the duplicate marks and list entirely, the block offsets up to their
+    total, and of each kept field's unique-row list as many entries as the field has unique rows (the rest is never read)"""
+    nbk = -(-B // 256)
+    offs = ss[2][:n_kept * nbk + 1].tolist()
+    out = [smp[0], smp[1], smp[2][:n_smp * nbk + 1], ss[2][:n_kept * nbk + 1]]
+    for r in range(n_kept):
+        u = offs[(r + 1) * nbk] - offs[r * nbk]
+        assert 0 < u <= B
+        out += [ss[0][r * B:r * B + u], ss[1][r * B:r * B + u]]
+    return out
+
+
+def test_marks_of_a_pinned_sort_stay_where_a_recorded_step_expects_them():
+    """The duplicate marks / unique-row lists of a PINNED sort are read by recorded launches at fixed addresses: they must live
+    exactly as long as the pinned sort, however many other marked sorts come and go (a cache of its own used to
+    evict them at eight entries), and a re-sort in place must re-make them in the same buffers."""
+    from rec_pangu_amd import hip
+    from rec_pangu_amd.models.layers.embedding import EmbeddingLayer
+    B, vocabs = 512, [5000, 300, 3000, 40, 5, 2000]  # three big tables (rows >= B), one mid-size (the streaming form), two tiny
+    enc = _enc(0, vocabs)
+    torch.manual_seed(0)
+    layer = EmbeddingLayer(enc_dict=enc, embedding_dim=64).to(DEV)
+    layer.check_indices = "deferred"
+    layer._marks_wanted = True  # (what the first three-form backward sets)
+    smp = layer._smp_tables(B)
+    assert [t[0] for t in smp] == [0, 2, 5] and [t[0] for t in layer._tiny_tables()] == [3, 4]
+    skip = sum(1 << f for f in (0, 2, 3, 4, 5))
+
+    def ids(seed):
+        gen = torch.Generator().manual_seed(seed)
+        return {f"C{i}": torch.randint(0, v + 1, (B,), generator=gen).to(DEV) for i, v in enumerate(vocabs)}
+
+    def ptrs(look):
+        return [t.data_ptr() for t in look.smp + look.ss[1]]
+
+    keep = []
+    try:
+        X0 = ids(100)
+        layer.pin_sort(X0)
+        first = layer.pinned_sort(X0)
+        assert first.pinned and first.smp_sig == (B, tuple(smp)) and first.ss[0] == skip
+        before = ptrs(first)
+        for i in range(8):  # eight more static batches ...
+            X = ids(200 + i)
+            layer.pin_sort(X)
+            keep.append((X, layer.pinned_sort(X)))
+            assert keep[-1][1] is not first and keep[-1][1].smp is not None
+        for i in range(9):  # ... and marked eager sorts, all kept alive
+            X = ids(300 + i)
+            look = layer._sorted_keys(layer._idx_list(X), layer.row_base, layer.row_count, tuple(X[c] for c in layer.emb_feature))
+            assert not look.pinned and look.smp is not None and look.ss is not None
+            keep.append((X, look))
+        assert len({p for _, look in keep for p in ptrs(look)} | set(before)) == 6 * (1 + len(keep))
+        new = ids(101)
+        for k in X0:  # the static batch is refilled in place and re-sorted in place
+            X0[k].copy_(new[k])
+        layer.pin_sort(X0)
+        assert layer.pinned_sort(X0) is first
+        assert ptrs(first) == before
+        want_sk, want_sp = hip.sort_pairs(hip.embed_keys(layer.row_base, layer.row_count, layer._idx_list(new), layer.err_flag),
+                                          end_bit=layer._meta()[3])
+        assert torch.equal(first.sk, want_sk) and torch.equal(first.sp, want_sp)
+        fresh = _defined_marks(hip.embed_grad_smp_mark(first.sk, first.sp, B, [t[0] for t in smp]),
+                               hip.embed_grad_ss_mark(first.sk, B, skip), B, len(smp), 1)
+        held = _defined_marks(first.smp, first.ss[1], B, len(smp), 1)
+        assert len(fresh) == len(held) == 6
+        for a, b in zip(held, fresh):
+            assert a.shape == b.shape and torch.equal(a, b)
+    finally:
+        EmbeddingLayer.unpin_sorts()
