@@ -1158,7 +1158,14 @@ class _EmbedGather(torch.autograd.Function):
         gfm = dfm.contiguous() if (ctx.want_fm and dfm is not None) else None
         if ctx.link is not None and ctx.link.folded:
             ssum = None  # g_fm * S is already inside dx (rp_linear_fwd_rowadd)
-        store.accumulate_grad(keys, ctx.B, dx, gfm, ssum, presorted=ctx.presorted, fused=fused)
+        if fused is None:
+            store.accumulate_grad(keys, ctx.B, dx, gfm, ssum, presorted=ctx.presorted)
+        else:  # (dH, W^T) of the Linear that consumes x: its dgrad is formed inside the reduce
+            g = store.first_layer_grad(keys, ctx.B, *fused, gfm, ssum, presorted=ctx.presorted, dx=dx)
+            if g.forms.tiny:
+                g.tiny()
+            g.gemm()
+            g.done()
         return (None,) * (6 + len(store.emb_feature))
 
 
@@ -1170,6 +1177,15 @@ def _side2_stream(device):
     if st is None:
         st = _WGRAD_STREAMS[device] = hip.make_side_stream(device, "inline")
     return st
+
+
+def _masked_by_consumer(lk, dy) -> bool:
+    """does dy already carry the ReLU mask of the activation it belongs to — is it the very gradient the consumer of that
+    activation left in the ReluLink `lk`?  (The link's gradient is used up either way.)"""
+    masked = lk is not None and lk.dx is not None and lk.dx.data_ptr() == dy.data_ptr() and lk.dx.shape == dy.shape
+    if lk is not None:
+        lk.dx = None
+    return masked
 
 
 def _wgrad_stream(device):
@@ -1258,25 +1274,18 @@ class _EmbedGatherLinear(torch.autograd.Function):
         keys, ssum, x, h1, weight = ctx.saved_tensors
         store = ctx.store
         dh1 = _unit_inner(dh1)
-        lk = ctx.out_link
-        masked = lk is not None and lk.dx is not None and lk.dx.data_ptr() == dh1.data_ptr() and lk.dx.shape == dh1.shape
-        if lk is not None:
-            lk.dx = None
-        dpre = dh1 if masked else hip.relu_bwd(dh1, h1)
+        dpre = dh1 if _masked_by_consumer(ctx.out_link, dh1) else hip.relu_bwd(dh1, h1)
         dw = db = None
         need_w = ctx.needs_input_grad[4] or (ctx.has_bias and ctx.needs_input_grad[5])
         need_t = keys is not None and ctx.need_tables
         if need_w and ctx.x_mode == "none":
             raise RuntimeError("the fused lookup + first layer stored no activation (the forward ran without gradients for the "
                                "layer's weight)")
-
-        seg = None
-        if need_w and ctx.x_mode == "seg":
-            # the weight gradient's three column groups come from three launches: the dense columns (+ the bias gradient)
-            # from rp_linear_wgrad over xd below, the tiny tables' from rp_embed_grad_tiny and the other tables' from
-            # rp_embed_grad_seg (both inside store.accumulate_grad)
-            dw_seg = torch.empty((64, ctx.K), dtype=torch.float32, device=dpre.device)
-            seg = (weight, dw_seg)
+        # "seg": the weight gradient's three column groups come from three launches: the dense columns (+ the bias gradient)
+        # from rp_linear_wgrad over xd, the tiny tables' from rp_embed_grad_tiny and the other tables' from the big / rest
+        # launches of the gather backward (store.first_layer_grad), all into dw_seg
+        seg = need_w and ctx.x_mode == "seg"
+        dw_seg = torch.empty((64, ctx.K), dtype=torch.float32, device=dpre.device) if seg else None
 
         def wgrad(keep=None):
             if ctx.x_mode == "seg":    # x holds the dense columns only (xd [B, 64]); their columns of dw and the bias gradient
@@ -1292,54 +1301,93 @@ class _EmbedGatherLinear(torch.autograd.Function):
         # gathers, ~1 TB/s of HBM: 0.30 ms) both depend only on dpre and are independent of each other: the weight gradient
         # runs on a second stream BESIDE the gather backward instead of in front of it.  Same kernels, same inputs: bit-identical.
         wstream = _wgrad_stream(dpre.device) if (need_w and need_t) else None
-        # ... and while a LAUNCH PLAN is being recorded (a captured step: one stream), the weight gradient's launches are
-        # marked as an inline section: the replay issues them on the plan's second side stream, joined after the gather
-        # backward.  Their workspace stays referenced until the join (the capture's allocator would reuse it at once).
+        # ... and while a LAUNCH PLAN is being recorded (a captured step: one stream), the side launches are marked as an
+        # inline section (plan.side2): the replay issues them on the plan's second side stream, joined after the gather
+        # backward.  Their workspaces stay referenced (`keep`) until the join: the side launches run beside the ones issued
+        # behind them, and the capture's one-stream allocator would hand those their memory at once.
+        plan = hip.LaunchPlan
         in_plan = (wstream is None and need_w and need_t and ctx.x_mode != "dense"
-                   and os.environ.get("RP_WGRAD_OVERLAP", "1") != "0" and hip.LaunchPlan.is_recording())
-        keep = []
-        # (round 5) in a plan, with the segment-sum-first backward: the LONG main-stream launch is issued first and the short
-        # side launches behind it, all forked from the same point (rp_plan_fork2_mark) — issued the other way round the side
-        # launches filled every CU and rp_embed_grad_seg (77 KB of LDS per workgroup) started 58 us late (profiles/r05_trace_step.txt)
-        # Measured (profiles/r05 lines, alternating runs on one box): 0.946 / 0.947 ms with the main launch first against
-        # 0.929 / 0.932 the other way round (long-run means equal, 0.906-0.916): the side launches then stretch to twice their
-        # time and the join comes later
-        # (re-measured at the end of round 5, after the loss head moved into the MLP tail and the side streams went to the
-        #  lowest priority: main launch first 0.8324 / 0.8375 ms against 0.8369 / 0.8384 in the 20-step window, 0.8086 / 0.8099
-        #  against 0.8152 / 0.8161 over 600 steps)
-        seg_first = in_plan and seg is not None and need_t
-        if seg_first:
-            pass  # (the fork is marked inside accumulate_grad, behind the sample-major launch: round 6)
-        elif in_plan:
-            hip.LaunchPlan.section(2)
-            try:
-                dw, db = wgrad(keep)
-                hip.LaunchPlan.run_deferred()  # (e.g. the MLP tail's second stage: behind the weight gradient, not in front)
-            finally:
-                hip.LaunchPlan.section(0)
-        elif wstream is not None:
+                   and os.environ.get("RP_WGRAD_OVERLAP", "1") != "0" and plan.is_recording())
+        keep = [] if in_plan else None
+
+        def side_wgrad():
+            with plan.side2(in_plan):
+                out = wgrad(keep)
+                if in_plan:
+                    plan.run_deferred()  # (e.g. the MLP tail's second stage: behind the weight gradient, not in front)
+            return out
+
+        # THE ISSUE ORDER of the first layer's backward: {a plan is recording} x {dw's embedding columns come from the gather
+        # backward (seg)}.  Except when both hold, the weight gradient goes first: in front, or beside on the second stream.
+        if wstream is not None:
             main = torch.cuda.current_stream(dpre.device)
             wstream.wait_stream(main)
             with torch.cuda.stream(wstream):
                 dw, db = wgrad()
-        elif need_w:
-            dw, db = wgrad()
+        elif need_w and not (in_plan and seg):
+            dw, db = side_wgrad()
         if need_t:
             wt = ctx.wt if ctx.wt is not None else hip.transpose(weight, rows_out=ctx.ldx)
             gfm = dfm.contiguous() if dfm is not None else None
-            store.accumulate_grad(keys, ctx.B, None, gfm, ssum if gfm is not None else None, presorted=ctx.presorted,
-                                  fused=(dpre, wt), plan_keep=keep if in_plan else None, seg=seg, seg_first=seg_first,
-                                  fork2=hip.LaunchPlan.fork2_mark if seg_first else None)
-        if seg_first:
-            hip.LaunchPlan.section(2)
-            try:
-                dw, db = wgrad(keep)
-                hip.LaunchPlan.run_deferred()
-            finally:
-                hip.LaunchPlan.section(0)
+            g = store.first_layer_grad(keys, ctx.B, dpre, wt, gfm, ssum if gfm is not None else None, presorted=ctx.presorted,
+                                       w=weight if seg else None, dw=dw_seg, keep=keep)
+            f = g.forms
+            if not seg:  # (recording or not) the tiny tables on the side, one row-sorted launch for all others
+                if f.tiny:
+                    with plan.side2(in_plan):
+                        g.tiny()
+                g.gemm()
+            elif not in_plan:  # the caller's stream: tiny, sample-major, row-sorted, the launches behind the sample-major one
+                if f.tiny:
+                    g.tiny()
+                ws = g.big(1) if f.big else None
+                if f.rest:
+                    g.rest()
+                if f.big:
+                    g.big(2, ws)
+            else:
+                # (round 5) the LONG main-stream launch is issued first and the short side launches behind it, all forked from
+                # the same point (plan.fork2_mark) — issued the other way round the side launches filled every CU and
+                # rp_embed_grad_seg (77 KB of LDS per workgroup) started 58 us late (profiles/r05_trace_step.txt)
+                # Measured (profiles/r05 lines, alternating runs on one box): 0.946 / 0.947 ms with the main launch first against
+                # 0.929 / 0.932 the other way round (long-run means equal, 0.906-0.916): the side launches then stretch to twice
+                # their time and the join comes later
+                # (re-measured at the end of round 5, after the loss head moved into the MLP tail and the side streams went to
+                #  the lowest priority: main launch first 0.8324 / 0.8375 ms against 0.8369 / 0.8384 in the 20-step window,
+                #  0.8086 / 0.8099 against 0.8152 / 0.8161 over 600 steps)
+                # (round 6) with big tables the sample-major launch is that long launch; the tiny tables' launches are forked IN
+                # FRONT of it and run beside it on the second stream, and the launches behind the sample-major one follow them
+                # there (plan.side2_sync: that stream waits for the sample-major launch at that point); without tiny tables the
+                # fork is marked behind the sample-major launch
+                if f.tiny or not f.big:
+                    plan.fork2_mark()
+                if f.big:
+                    ws = g.big(1)
+                    if f.tiny:
+                        with plan.side2():
+                            g.tiny()
+                        plan.side2_sync()
+                    else:
+                        plan.fork2_mark()
+                # (the streaming segment-sum launch uses no LDS, but it cannot run BESIDE the sample-major launch on a second
+                #  stream: 4 x 112 and 2 x 240 registers per SIMD lane do not fit the file of 512 together — one after the other
+                #  on the main stream)
+                if f.rest:
+                    g.rest()
+                if f.big:
+                    # on the second stream beside the row-sorted form's launches; in ISSUE order behind those: issued in front of
+                    # them, the 4096 short workgroups of the duplicate reduce held the segment-sum launch up by 56 us
+                    # (profiles/r06 trace notes)
+                    with plan.side2():
+                        g.big(2, ws)
+                elif f.tiny:  # (no sample-major launch: behind the long main-stream launch in issue order)
+                    with plan.side2():
+                        g.tiny()
+            g.done()
         if in_plan:
-            hip.LaunchPlan.join()
-            del keep
+            if seg:
+                dw, db = side_wgrad()
+            plan.join()
         if wstream is not None:
             main.wait_stream(wstream)  # whoever consumes dw / db (AccumulateGrad, the optimizer) is ordered behind them
             dw.record_stream(main)     # (allocated under the second stream, consumed and freed on the main one)
@@ -1379,8 +1427,7 @@ class _EmbedGatherPool(torch.autograd.Function):
     def backward(ctx, g):
         ids, inv, bag = ctx.saved_tensors
         store = ctx.store
-        store.accumulate_grad(None, 0, None, None, None, presorted=ctx.presorted,
-                              pool=(g.contiguous(), inv, bag, ctx.L, ctx.field, ids))
+        store.pool_grad(ctx.field, ids, g.contiguous(), inv, bag, ctx.L, presorted=ctx.presorted)
         return (None,) * (8 + len(store.emb_feature))
 
 

@@ -5,6 +5,7 @@ memory (`tensor.data_ptr()`), and the current HIP stream (`torch.cuda.current_st
 torch type crosses the ABI.  There is NO fallback: if the shared object is missing or a call
 fails, a RuntimeError is raised — a CUDA(HIP)-resident tensor never silently takes another path.
 """
+import contextlib
 import ctypes as C
 import os
 from typing import List, Optional, Sequence
@@ -1111,6 +1112,20 @@ class LaunchPlan:
     def section(k: int):
         _check(lib().rp_plan_section(k), "rp_plan_section")
 
+    @classmethod
+    @contextlib.contextmanager
+    def side2(cls, enabled: bool = True):
+        """with LaunchPlan.side2(): the launches issued inside are recorded on the inline section (2: the replay issues them
+        on the plan's second side stream); back on the main section afterwards, also behind an exception.  enabled=False
+        (no plan is recording): nothing"""
+        if enabled:
+            cls.section(2)
+        try:
+            yield
+        finally:
+            if enabled:
+                cls.section(0)
+
     @staticmethod
     def fork_here():
         _check(lib().rp_plan_fork_here(), "rp_plan_fork_here")
@@ -1137,12 +1152,9 @@ class LaunchPlan:
         if not cls._deferred:
             return
         todo, cls._deferred = cls._deferred, []
-        _check(lib().rp_plan_section(2), "rp_plan_section")
-        try:
+        with cls.side2():
             for fn in todo:
                 fn()
-        finally:
-            _check(lib().rp_plan_section(0), "rp_plan_section")
 
     @classmethod
     def settle(cls):

@@ -18,7 +18,8 @@ BASELINE.json config 0 ("plumbing, no GPU") and uses plain torch ops.
 import copy
 import os
 import weakref
-from typing import Dict, List, Optional, Union
+from types import SimpleNamespace
+from typing import Dict, List, NamedTuple, Optional, Union
 
 import torch
 from torch import nn
@@ -78,6 +79,16 @@ class SortedLookup:
     def ss_lists(self, skip: int):
         """the unique-row lists made with the sort for exactly these kept fields, or None (rp_embed_grad_ss makes its own)"""
         return self.ss[1] if (self.ss is not None and self.ss[0] == skip) else None
+
+
+class GradForms(NamedTuple):
+    """which form of the first layer's backward every table of a layer takes at one batch size (EmbeddingLayer._forms)"""
+    tiny: Optional[list]  # [(field, first arena row, rows), ...] of rp_embed_grad_tiny's tables, or None
+    big: Optional[list]   # ... of rp_embed_grad_smp's, or None
+    skip: int             # bit f set: field f is one of those — the row-sorted form leaves its pairs out
+    rest: bool            # mid-size fields remain for the row-sorted form ...
+    ss: bool              # ... which is rp_embed_grad_ss (streaming) rather than rp_embed_grad_seg ...
+    ss_ahead: bool        # ... with its unique-row lists made behind the sort
 
 
 # the unpinned lookups of the last four batches (the batch in flight, the one whose sort was started ahead): two layers with
@@ -363,78 +374,74 @@ class EmbeddingLayer(nn.Module):
             self._lazy.flush(self)
 
     def _tiny_tables(self):
-        """[(field, first arena row, rows), ...] of the tables rp_embed_grad_tiny takes (D = 64; each <= 254 rows, the
-        smallest first while they fit 224 accumulator rows, at most 16), or None; RP_GRAD_TINY=0 turns the path off"""
-        hit = self.__dict__.get("_tiny_cache")
+        """[(field, first arena row, rows), ...] of the tables rp_embed_grad_tiny takes (whatever the batch size), or None"""
+        return self._forms(0, big=False).tiny
+
+    def _smp_tables(self, B: int):
+        """[(field, first arena row, rows), ...] of the BIG tables rp_embed_grad_smp takes at batch size B, or None"""
+        return self._forms(B).big
+
+    def _forms(self, B: int, tiny: bool = True, big: bool = True) -> GradForms:
+        """The form every table takes in the first layer's backward at batch size B: the ONE classification, read by the marks
+        made behind a sort (_mark_sorted, possibly a step ahead on a side stream) and by the backward that consumes them
+        (first_layer_grad).  tiny / big = False: for a call that form does not cover — its tables fall to the row-sorted form.
+        Cached per (row signature, D, B); the switches are read when the record is made.
+        TINY (rp_embed_grad_tiny): D = 64; each <= 254 rows, the smallest first while they fit 224 accumulator rows, at most
+        16; RP_GRAD_TINY=0 turns the form off.
+        BIG (round 6, rp_embed_grad_smp: the sample-major form): tables of at least RP_SMP_MIN x B rows, where most runs of the
+        sorted pair list are single pairs; not the tiny ones; < 2^24 rows each; the 16 largest; RP_GRAD_SMP=0 turns it off."""
         sig = self._rows_sig()
-        if hit is not None and hit[0] is sig:
-            return hit[1]
-        out = None
-        if self.embedding_dim == 64 and os.environ.get("RP_GRAD_TINY", "1") != "0" and len(sig) <= 64:
-            order = sorted(range(len(sig)), key=lambda f: sig[f])
+        key = (sig, self.embedding_dim, B, tiny, big)
+        cache = self.__dict__.setdefault("_forms_cache", {})
+        forms = cache.get(key)
+        if forms is not None:
+            return forms
+        env, F = os.environ.get, len(sig)
+        fits = self.embedding_dim == 64 and F <= 64
+        t = b = None
+        if fits and env("RP_GRAD_TINY", "1") != "0":
             pick, total = [], 0
-            for f in order:
+            for f in sorted(range(F), key=lambda f: sig[f]):
                 if sig[f] <= 254 and total + sig[f] <= 224 and len(pick) < 16:
                     pick.append(f)
                     total += sig[f]
             if total >= 1 and len(pick) >= 2:  # (a single tiny table is not worth two extra launches)
-                out = [(f, sum(sig[:f]), sig[f]) for f in sorted(pick)]
-        self.__dict__["_tiny_cache"] = (sig, out)
-        return out
-
-    def _smp_tables(self, B: int):
-        """[(field, first arena row, rows), ...] of the BIG tables rp_embed_grad_smp takes (round 6: the sample-major form of
-        the first layer's backward — tables of at least RP_SMP_MIN x B rows, where most runs of the sorted pair list are
-        single pairs; not rp_embed_grad_tiny's; < 2^24 rows each; the 16 largest), or None; RP_GRAD_SMP=0 turns the path off"""
-        hit = self.__dict__.get("_smp_cache")
-        sig = self._rows_sig()
-        if hit is not None and hit[0] is sig and hit[1] == B:
-            return hit[2]
-        out = None
+                t = [(f, sum(sig[:f]), sig[f]) for f in sorted(pick)]
         # (batches below RP_SMP_MIN_BATCH keep round 5's single row-sorted launch: the three-form backward is 16 launches more,
         #  and a b = 8192 step — the per-GPU batch of a strong-scaling run — is bound by launches: 0.50 ms against 0.43)
-        if self.embedding_dim == 64 and os.environ.get("RP_GRAD_SMP", "1") != "0" and len(sig) <= 64 \
-                and B >= int(os.environ.get("RP_SMP_MIN_BATCH", "32768")):
-            tiny = {t[0] for t in (self._tiny_tables() or ())}
-            need = float(os.environ.get("RP_SMP_MIN", "1.0")) * B
-            pick = sorted((f for f in range(len(sig)) if f not in tiny and need <= sig[f] < (1 << 24)),
-                          key=lambda f: -sig[f])[:16]
+        if big and fits and env("RP_GRAD_SMP", "1") != "0" and B >= int(env("RP_SMP_MIN_BATCH", "32768")):
+            taken = {x[0] for x in t or ()}
+            need = float(env("RP_SMP_MIN", "1.0")) * B
+            pick = sorted((f for f in range(F) if f not in taken and need <= sig[f] < (1 << 24)), key=lambda f: -sig[f])[:16]
             if pick and len(pick) * B < (1 << 24) and sum(sig) < (1 << 31):
-                out = [(f, sum(sig[:f]), sig[f]) for f in sorted(pick)]
-        self.__dict__["_smp_cache"] = (sig, B, out)
-        return out
+                b = [(f, sum(sig[:f]), sig[f]) for f in sorted(pick)]
+        t = t if tiny else None
+        skip = sum(1 << x[0] for x in (t or []) + (b or []))
+        rest = skip != (1 << F) - 1
+        # the streaming form (rp_embed_grad_ss) only beside the sample-major one; its unique-row lists are made with the sort
+        # unless RP_SS_MARK_AHEAD=0 (then rp_embed_grad_ss makes its own)
+        ss = bool(b) and rest and env("RP_GRAD_SS", "1") != "0"
+        forms = cache[key] = GradForms(t, b, skip, rest, ss, ss and env("RP_SS_MARK_AHEAD", "1") != "0")
+        return forms
 
     def _mark_sorted(self, look: SortedLookup, force: bool = False) -> None:
-        """behind a sort of this layer's pairs (on the stream that sorted them): the duplicate marks of the big tables.  Only for
-        a layer whose backward has taken the three-form path before (`_marks_wanted`, set by accumulate_grad) — DCN, xDeepFM,
-        AutoInt and MMOE reduce through rp_embed_grad_reduce and made six launches' worth of marks per step for nobody."""
+        """behind a sort of this layer's pairs (on the stream that sorted them): the duplicate marks of the big tables and the
+        unique-row lists of the mid-size ones (every field that is neither tiny nor big: rp_embed_grad_ss).  Only for a layer
+        whose backward has taken the three-form path before (`_marks_wanted`, set by first_layer_grad) — DCN, xDeepFM, AutoInt and
+        MMOE reduce through rp_embed_grad_reduce and made six launches' worth of marks per step for nobody."""
         if not (force or getattr(self, "_marks_wanted", False)):
             return
         F, n = len(self.emb_feature), look.sk.numel()
-        smp = self._smp_tables(n // F) if (n > 0 and n % F == 0) else None
-        if smp is None:
-            return
-        # ... and the unique-row lists of the mid-size tables (every field that is neither tiny nor big: rp_embed_grad_ss)
-        skip = 0
-        for f, _, _ in list(self._tiny_tables() or ()) + list(smp):
-            skip |= 1 << f
-        ss = skip != (1 << F) - 1 and os.environ.get("RP_GRAD_SS", "1") != "0" and os.environ.get("RP_SS_MARK_AHEAD", "1") != "0"
-        look.mark(n // F, smp, skip if ss else None)
+        forms = self._forms(n // F) if (n > 0 and n % F == 0) else None
+        if forms is not None and forms.big:
+            look.mark(n // F, forms.big, forms.skip if forms.ss_ahead else None)
 
-    def _marks_of(self, look: SortedLookup, smp, B: int):
-        self._marks_wanted = True
-        if look.smp_sig != (B, tuple(smp)):
-            self._mark_sorted(look, force=True)  # (a sort nobody marked: an eager backward that sorted for itself)
-        return look.smp
-
-    def accumulate_grad(self, keys, B: int, dx, gfm, ssum, presorted=None, fused=None, pool=None, plan_keep=None, seg=None,
-                        seg_first: bool = False, fork2=None):
-        """Called from the autograd node of the gather: dense table gradients, reference semantics
-        (aten::embedding_dense_backward: every table gets a full [V+1, D] gradient, zeros where no
-        sample looked).  Invariant kept between steps: the gradient arena is zero everywhere except
-        the rows listed in `_touched`, so a fresh gradient costs a sparse re-zero, not an 8.6 GB fill."""
+    # The three backward passes below share their opening and closing.  Invariant kept between steps: the gradient arena is
+    # zero everywhere except the rows listed in `_touched`, so a fresh gradient costs a sparse re-zero, not an 8.6 GB fill.
+    def _grad_begin(self, keys, presorted):
+        """the gradient arena allocated or sparsely re-zeroed, the sort taken or made -> (the SortedLookup, whether the tables'
+        .grad views have to be attached at the end)"""
         from ... import hip
-        D = self.embedding_dim
         fresh = not self._grads_are_ours()
         if self._grad_arena is None or self._grad_arena.shape != self._arena.shape \
                 or self._grad_arena.device != self._arena.device:
@@ -443,119 +450,18 @@ class EmbeddingLayer(nn.Module):
         elif fresh and not self._grad_clean:
             # zero_grad() dropped the .grad views: clear the rows the previous backward wrote
             if self._touched is not None:
-                hip.zero_rows(self._touched, D, self._grad_arena)
+                hip.zero_rows(self._touched, self.embedding_dim, self._grad_arena)
             else:
                 self._grad_arena.zero_()
             self._touched, self._grad_clean = None, True
-        if pool is not None and presorted is None:  # pooled multi-id lookup of one table: keys of its flat id list
-            f = pool[4]
-            keys = hip.embed_keys(self.row_base[f:f + 1], self.row_count[f:f + 1], [pool[5]], self.err_flag)
         look = presorted if presorted is not None else SortedLookup(keys, *hip.sort_pairs(keys, end_bit=self._meta()[3]))
-        sk, sp = look.sk, look.sp
         if self._lazy is not None and self._lazy._noclear is not None:
             # the catch-up launch in front of this step's forward left its applied gradient rows uncleared, counting on
             # THIS launch to overwrite them (LazyAdamRows.replay): kept if it writes that key list without accumulating
-            self._lazy.resolve_noclear(self, sk if self._grad_clean else None)
-        if pool is not None:  # (g [B, D], 1 / count or None, bag of every id or None, ids per dense bag, field, ids)
-            hip.embed_pool_bwd(sk, sp, D, pool[0], pool[1], pool[2], pool[3], self._grad_arena,
-                               accumulate=not self._grad_clean)
-        elif fused is not None:  # (dH, W^T) of the Linear that consumes x: its dgrad is formed inside the reduce
-            skip = 0
-            smp = None
-            tiny = self._tiny_tables() if (keys is not None and dx is None and keys.numel() == len(self.emb_feature) * B) else None
-            for f, _, _ in (tiny or ()):
-                skip |= 1 << f
+            self._lazy.resolve_noclear(self, look.sk if self._grad_clean else None)
+        return look, fresh
 
-            def run_tiny():
-                # the tables of a few rows (Criteo: 8 fields, 31 % of the pairs) take the sample-major one-hot path; the
-                # row-sorted kernel leaves their fields out.  Inside a recorded launch plan these launches join the first
-                # layer's side work on the plan's second side stream (functional._EmbedGatherLinear.backward)
-                in_plan = plan_keep is not None
-                if in_plan:
-                    hip.LaunchPlan.section(2)
-                try:
-                    hip.embed_grad_tiny(keys, B, tiny, fused[0], fused[1], gfm, ssum, self._arena, self._grad_arena,
-                                        accumulate=not self._grad_clean, keep=plan_keep, dw=None if seg is None else seg[1])
-                finally:
-                    if in_plan:
-                        hip.LaunchPlan.section(0)
-
-            if tiny and not seg_first:
-                run_tiny()
-            if seg is not None:
-                # (weight [64, K], dw [64, K]) of the consuming Linear: segment sums first, one matrix pass per run that also
-                # yields the embedding columns of dw — the forward stored no activation (functional._EmbedGatherLinear)
-                if keys is None or dx is not None or keys.numel() != len(self.emb_feature) * B:
-                    raise RuntimeError("the fused first layer stored no activation, but its backward is not the field-major "
-                                       "single-device form rp_embed_grad_seg covers")
-                # round 6: the BIG tables (runs of the sorted list are mostly single pairs: the sort buys nothing and the
-                # (field, row) order re-gathers every dH / S row once per field) go through the batch in sample order
-                # instead (rp_embed_grad_smp); its main launch first, then — forked from that point inside a recorded plan —
-                # rp_embed_grad_seg over the remaining fields with the launches behind the sample-major one (the weight
-                # gradient's partial sums, the duplicate runs: other rows than anything beside them) on the second stream
-                smp = self._smp_tables(B) if hip.embed_grad_smp_fits(D, 64, fused[0]) else None
-                in_plan = plan_keep is not None
-                acc = not self._grad_clean
-                if smp:
-                    for f, _, _ in smp:
-                        skip |= 1 << f
-                rest = skip != (1 << len(self.emb_feature)) - 1   # fields left for the row-sorted form
-                # ... and the row-sorted form for the remaining (mid-size) tables in two launches (rp_embed_grad_ss: a streaming
-                # segment-sum launch, then the matrix launch over the unique rows).  (The segment-sum launch uses no LDS, but it
-                # cannot run BESIDE the sample-major launch on a second stream: 4 x 112 and 2 x 240 registers per SIMD lane do
-                # not fit the file of 512 together — one after the other on the main stream.)
-                ss = bool(smp) and rest and os.environ.get("RP_GRAD_SS", "1") != "0"
-                seg_args = (sk, sp, B, D, fused[0], seg[0], gfm, ssum, self._arena, self._grad_arena)
-                seg_kw = dict(accumulate=acc, skip_fields=skip, field_rows=self._rows_sig(), dw=seg[1], keep=plan_keep)
-                smp_ws = None
-                # (a recorded plan only) the tiny tables' launches are forked IN FRONT of the sample-major launch and run
-                # beside it on the second stream; the launches behind the sample-major one follow them there
-                # (rp_plan_side2_sync: that stream waits for the sample-major launch at that point)
-                tiny_early = bool(smp and tiny and seg_first and in_plan and fork2 is not None)
-                if tiny_early:
-                    fork2()
-                if smp:
-                    marks = self._marks_of(look, smp, B)
-                    smp_args = (keys, marks, B, len(self.emb_feature), smp, fused[0], seg[0], gfm, ssum, self._arena,
-                                self._grad_arena)
-                    smp_ws = hip.embed_grad_smp(*smp_args, accumulate=acc, dw=seg[1], keep=plan_keep, phases=1)
-                if ss:  # (the unique-row lists made with the sort — or just now, by _marks_of, for a sort nobody had marked)
-                    seg_kw["marks"] = look.ss_lists(skip)
-                if tiny_early:
-                    run_tiny()
-                    hip.LaunchPlan.side2_sync()
-                    tiny = None
-                elif fork2 is not None:
-                    fork2()
-                # (inside a recorded plan the workspaces stay referenced until the join: the side launches issued BEHIND these
-                #  run beside them on another stream, and the capture's one-stream allocator would hand them their memory)
-                if ss:
-                    hip.embed_grad_ss(*seg_args, **seg_kw)
-                elif rest:
-                    hip.embed_grad_seg(*seg_args, **seg_kw)
-                if smp:
-                    # the launches behind the sample-major one: other rows than anything beside them — on the second stream,
-                    # forked at the mark above (behind the sample-major launch), beside the launches of the row-sorted form; in
-                    # ISSUE order behind those: issued in front of them, the 4096 short workgroups of the duplicate reduce held
-                    # the segment-sum launch up by 56 us (profiles/r06 trace notes)
-                    if in_plan:
-                        hip.LaunchPlan.section(2)
-                    try:
-                        hip.embed_grad_smp(*smp_args, accumulate=acc, dw=seg[1], phases=2, ws=smp_ws)
-                    finally:
-                        if in_plan:
-                            hip.LaunchPlan.section(0)
-            else:
-                if fork2 is not None:
-                    fork2()
-                hip.embed_grad_gemm(sk, sp, B, D, fused[0], fused[1], dx, gfm, ssum, self._arena, self._grad_arena,
-                                    accumulate=not self._grad_clean, skip_fields=skip)
-            if tiny and seg_first:
-                # (no sample-major launch: behind the long main-stream launch in issue order, see rp_plan_fork2_mark)
-                run_tiny()
-        else:
-            hip.embed_grad_reduce(sk, sp, B, D, dx, gfm, ssum, self._arena, self._grad_arena,
-                                  accumulate=not self._grad_clean)
+    def _grad_end(self, sk, fresh: bool) -> None:
         if self._touched is None:
             self._touched, self._touched_unsorted = sk, False
         else:  # several backward passes before one optimiser step: the union is no longer sorted
@@ -563,6 +469,78 @@ class EmbeddingLayer(nn.Module):
         self._grad_clean = False
         if fresh:
             self._attach_grads()
+
+    def accumulate_grad(self, keys, B: int, dx, gfm, ssum, presorted=None):
+        """Called from the autograd node of the gather: dense table gradients, reference semantics
+        (aten::embedding_dense_backward: every table gets a full [V+1, D] gradient, zeros where no
+        sample looked) — the plain segmented reduce of dx [B, ldx]."""
+        from ... import hip
+        look, fresh = self._grad_begin(keys, presorted)
+        hip.embed_grad_reduce(look.sk, look.sp, B, self.embedding_dim, dx, gfm, ssum, self._arena, self._grad_arena,
+                              accumulate=not self._grad_clean)
+        self._grad_end(look.sk, fresh)
+
+    def pool_grad(self, field: int, ids, g, inv, bag, L: int, presorted=None):
+        """the backward of the pooled multi-id lookup of table `field`: g [B, D], inv = 1 / count or None, bag = the bag of
+        every id or None, L ids per dense bag; the keys of its flat id list are made here unless their sort came along"""
+        from ... import hip
+        keys = None if presorted is not None else \
+            hip.embed_keys(self.row_base[field:field + 1], self.row_count[field:field + 1], [ids], self.err_flag)
+        look, fresh = self._grad_begin(keys, presorted)
+        hip.embed_pool_bwd(look.sk, look.sp, self.embedding_dim, g, inv, bag, L, self._grad_arena,
+                           accumulate=not self._grad_clean)
+        self._grad_end(look.sk, fresh)
+
+    def first_layer_grad(self, keys, B: int, dh, wt, gfm, ssum, presorted=None, dx=None, w=None, dw=None, keep=None):
+        """The backward of the lookup fused with the Linear that consumes x — its dgrad is formed inside the reduce from
+        (dh, wt = W^T) — as NAMED LAUNCHES: this call only opens the pass (gradient arena, sort, the tables' forms); the autograd
+        node issues `tiny`, `big`, `rest` or `gemm` in the order and on the plan section it wants and then `done`
+        (functional._EmbedGatherLinear.backward: the one place that order is written down).
+        w, dw ([64, K] each, both or neither): segment sums first, one matrix pass per run that also yields the embedding columns
+        of the weight gradient dw — the forward stored no activation.  keep: the list that holds the workspaces of launches
+        other launches run beside (a recording plan), or None.  -> .forms (GradForms) and the launches:
+          tiny    the tables of a few rows (Criteo: 8 fields, 31 % of the pairs): the sample-major one-hot path
+          big(1)  round 6: the BIG tables (runs of the sorted list are mostly single pairs: the sort buys nothing and the
+                  (field, row) order re-gathers every dH / S row once per field) go through the batch in sample order instead
+                  (rp_embed_grad_smp): the marks if the sort had none, then its main launch -> the workspace `ws`
+          big(2, ws)  the launches behind the sample-major one (the weight gradient's partial sums, the duplicate runs): other
+                  rows than anything beside them
+          rest    the row-sorted form over the remaining (mid-size) fields: rp_embed_grad_seg, or in two launches
+                  rp_embed_grad_ss (a streaming segment-sum launch, then the matrix launch over the unique rows) with the
+                  unique-row lists made with the sort — or just now, by big(1), for a sort nobody had marked
+          gemm    (no w, dw) rp_embed_grad_gemm over every field that is not tiny, dx [B, ldx] added if given"""
+        from ... import hip
+        F, D = len(self.emb_feature), self.embedding_dim
+        field_major = keys is not None and dx is None and keys.numel() == F * B
+        if dw is not None and not field_major:
+            raise RuntimeError("the fused first layer stored no activation, but its backward is not the field-major "
+                               "single-device form rp_embed_grad_seg covers")
+        look, fresh = self._grad_begin(keys, presorted)
+        # the tiny form only for the field-major all-fields call; the big one only with (w, dw) and where dh suits the kernel
+        forms = self._forms(B, tiny=field_major, big=dw is not None and hip.embed_grad_smp_fits(D, 64, dh))
+        acc = not self._grad_clean
+        to = (gfm, ssum, self._arena, self._grad_arena)
+
+        def tiny():
+            hip.embed_grad_tiny(keys, B, forms.tiny, dh, wt, *to, accumulate=acc, keep=keep, dw=dw)
+
+        def big(phase, ws=None):
+            if phase == 1:
+                self._marks_wanted = True
+                if look.smp_sig != (B, tuple(forms.big)):
+                    self._mark_sorted(look, force=True)  # (a sort nobody marked: an eager backward that sorted for itself)
+            return hip.embed_grad_smp(keys, look.smp, B, F, forms.big, dh, w, *to, accumulate=acc, dw=dw,
+                                      keep=keep if phase == 1 else None, phases=phase, ws=ws)
+
+        def rest():
+            launch, marks = (hip.embed_grad_ss, {"marks": look.ss_lists(forms.skip)}) if forms.ss else (hip.embed_grad_seg, {})
+            launch(look.sk, look.sp, B, D, dh, w, *to, accumulate=acc, skip_fields=forms.skip, field_rows=self._rows_sig(),
+                   dw=dw, keep=keep, **marks)
+
+        def gemm():
+            hip.embed_grad_gemm(look.sk, look.sp, B, D, dh, wt, dx, *to, accumulate=acc, skip_fields=forms.skip)
+
+        return SimpleNamespace(forms=forms, tiny=tiny, big=big, rest=rest, gemm=gemm, done=lambda: self._grad_end(look.sk, fresh))
 
     # ------------------------------------------------------------------ reference API
     def set_weights(self, col_name: str, embedding_matrix: torch.Tensor, trainable: Optional[bool] = True) -> None:

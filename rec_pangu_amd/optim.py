@@ -162,7 +162,7 @@ class LazyAdamRows:
         self._marked_for = -1  # the step whose gradient rows the last catch-up launch stamped pending
         # (step, sorted keys) of a stamping launch that left the applied gradient rows UNCLEARED because the backward it
         # precedes overwrites them (rp_lazy_adam_catchup mark = 2): resolved by that backward (EmbeddingLayer.
-        # accumulate_grad), or — when a second lookup or the optimizer step arrives first — by clearing those rows
+        # _grad_begin), or — when a second lookup or the optimizer step arrives first — by clearing those rows
         self._noclear = None
         self.m, self.v = torch.zeros_like(a), torch.zeros_like(a)
         self.last = torch.zeros((a.shape[0],), dtype=torch.int32, device=a.device)

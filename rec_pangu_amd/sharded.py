@@ -419,10 +419,7 @@ class _RowsToLinear(torch.autograd.Function):
         rows, slot_sorted, pos_sorted, ssum, x, h1, weight = ctx.saved_tensors
         b, D, K, has_bias, lk, scale, scaled, seg, F = ctx.cfg
         dh1 = Fh._unit_inner(dh1)
-        masked = lk is not None and lk.dx is not None and lk.dx.data_ptr() == dh1.data_ptr() and lk.dx.shape == dh1.shape
-        if lk is not None:
-            lk.dx = None
-        dpre = dh1 if masked else hip.relu_bwd(dh1, h1)
+        dpre = dh1 if Fh._masked_by_consumer(lk, dh1) else hip.relu_bwd(dh1, h1)
         dw = db = None
         if seg:
             # x = xd [b, 64] (the dense columns); slot_sorted / pos_sorted = the route's field-major lists.  dw's dense columns
