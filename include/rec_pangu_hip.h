@@ -68,7 +68,7 @@ int rp_get_matmul_precision(void);
 typedef void *rp_stream_t;
 
 /* ---- library ------------------------------------------------------------------------------ */
-#define RP_ABI_VERSION 107 /* rp_version(): bumped with every change of an entry point's prototype (csrc/common.hip) */
+#define RP_ABI_VERSION 108 /* rp_version(): bumped with every change of an entry point's prototype (csrc/common.hip) */
 int rp_version(void);
 const char *rp_last_error(void);
 /* number of kernel launches issued through this library since load (tests use it to prove the
@@ -575,6 +575,33 @@ int rp_batchnorm_bwd_sums(const float *x, int64_t ldx, const float *dy, int64_t 
 int rp_batchnorm_bwd_apply(const float *x, int64_t ldx, const float *dy, int64_t lddy, const float *mean,
                            const float *rstd, const float *gamma, const float *mean_dy, const float *mean_dyx,
                            float *dx, int64_t lddx, int64_t M, int N, rp_stream_t stream);
+
+/* ---- row-wise LayerNorm with a fused elementwise multiplier (csrc/layernorm.hip) --------------------------------------
+ * replaces torch.nn.LayerNorm over the last dimension and the `net * mask` behind it in layers/interaction.py:269-283
+ * (MaskBlock: _input_layer_norm, _layer_norm) and the stack + mean over parallel blocks of ranking/masknet.py:70-75.
+ * x [M, ldx], gamma / beta [N], biased variance, two-pass statistics in registers (a wave64 per row up to N = 2048, a looped
+ * path above: any N >= 1).  dwordx4 accesses where a pointer is 16-byte aligned and its leading dimension a multiple of 4.
+ *   rp_layernorm_fwd   y = out_scale * ((gamma * (x - mu) * r + beta) [* mul])    (accumulate != 0: added to y)
+ *                      mu = mean(x), r = 1 / sqrt(var(x) + eps) per row;  mul [M, ldmul] or NULL.
+ *                      stats [M, 2] = (mu, r) per row: written (NULL: not kept), or READ when stats_given != 0 (several
+ *                      LayerNorms over the same x: the parallel MaskBlocks).  Columns N .. N_pad-1 of y (N <= N_pad <= ldy)
+ *                      are written as zeros.  out_scale / accumulate: the mean over K blocks is K launches with
+ *                      out_scale = 1/K into one y, the first writing, the others adding, in the order they are issued.
+ *   rp_layernorm_bwd   dn = dy_scale * dy [* mul],  g = gamma * dn,  nh = (x - mu) * r  from the saved stats:
+ *                      dx (+)= r * (g - mean(g) - nh * mean(g * nh))    (accumulate != 0: added; columns N .. N_pad-1 zeros)
+ *                      dmul = dy_scale * dy * (gamma * nh + beta)       (with mul only: the normalised row is recomputed,
+ *                                                                        so the forward keeps x and mul, not their product)
+ *                      dgamma[n] = sum_m dn * nh,  dbeta[n] = sum_m dn — per-wave partial rows in `workspace` over a
+ *                      grid-stride walk of the rows, summed in a fixed order by a second launch (deterministic, no atomics).
+ *                      workspace: rp_layernorm_bwd_workspace_bytes(N), independent of M. */
+int rp_layernorm_fwd(const float *x, int64_t ldx, const float *gamma, const float *beta, float eps, const float *mul,
+                     int64_t ldmul, float *y, int64_t ldy, int N_pad, float out_scale, int accumulate, float *stats,
+                     int stats_given, int64_t M, int N, rp_stream_t stream);
+int rp_layernorm_bwd_workspace_bytes(int N, size_t *bytes);
+int rp_layernorm_bwd(const float *dy, int64_t lddy, float dy_scale, const float *x, int64_t ldx, const float *stats,
+                     const float *gamma, const float *beta, const float *mul, int64_t ldmul, float *dx, int64_t lddx,
+                     int N_pad, int accumulate, float *dmul, int64_t lddmul, float *dgamma, float *dbeta, int64_t M, int N,
+                     void *workspace, size_t workspace_bytes, rp_stream_t stream);
 
 /* ---- the narrow tail of the MLP as one launch each way (layers/deep.py:62-72 with hidden_units [.., 64, 64], output_dim 1:
  * DeepFM's dnn.net.{2,4,6}) --------------------------------------------------------------------------------------------

@@ -961,6 +961,130 @@ def batch_norm(x, bn: torch.nn.BatchNorm1d):
 # ----------------------------------------------------------------------------------------------
 # Dice   — layers/activation.py:10-34:  p = sigmoid(bn(x)),  y = p x + (1 - p) alpha x
 # ----------------------------------------------------------------------------------------------
+class _LayerNorm(torch.autograd.Function):
+    """nn.LayerNorm over the last dimension of a 2-D x, optionally times `mul` (rp_layernorm_fwd / _bwd)"""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, eps: float, mul):
+        x = _unit_inner(x)
+        mul = _unit_inner(mul) if mul is not None else None
+        y, stats = hip.layernorm_fwd(x, gamma, beta, eps, mul=mul)
+        ctx.save_for_backward(x, gamma, beta, mul, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, gamma, beta, mul, stats = ctx.saved_tensors
+        dx, dmul, dg, db = hip.layernorm_bwd(_unit_inner(dy), x, stats, gamma, beta, mul=mul)
+        return dx, dg, db, None, dmul
+
+
+def layer_norm(x, ln: torch.nn.LayerNorm, mul=None):
+    """ln(x) [* mul] for an affine nn.LayerNorm over the last dimension, as one launch each way; with `mul` (same shape as
+    x) the product is formed inside the launch and the normalised tensor is never stored."""
+    N = x.shape[-1]
+    if tuple(ln.normalized_shape) != (N,) or ln.weight is None or ln.bias is None:
+        raise RuntimeError(f"layer_norm: an affine LayerNorm over the last dimension ({N}), got {ln}")
+    if mul is not None and mul.shape != x.shape:
+        raise RuntimeError(f"layer_norm: mul {tuple(mul.shape)} against x {tuple(x.shape)}")
+    y = _LayerNorm.apply(x.reshape(-1, N), ln.weight, ln.bias, float(ln.eps), mul.reshape(-1, N) if mul is not None else None)
+    return y.reshape(x.shape)
+
+
+class _MaskBlockStack(torch.autograd.Function):
+    """MaskNet's whole stack of MaskBlocks (ranking/masknet.py:70-79 over layers/interaction.py:279-283) on one autograd node.
+        block_k(net, x) = LN_out_k(Wh_k (LN_in_k(net) * (W2_k relu(W1_k x + c1_k) + c2_k)) + ch_k)
+        parallel: v = mean_k block_k(x, x);   serial: v_0 = x, v_{k+1} = block_k(v_k, x), v = v_K
+    x [B, W] (d = the blocks' width, columns beyond d are padding); params: per block (LN_in weight, bias, W1, c1, W2, c2, Wh,
+    ch, LN_out weight, bias).  Returns v [B, ceil4(W)] with zeros beyond d.  Per block the forward is 5 launches (Linear+ReLU,
+    Linear, LN_in * mask, Linear, LN_out — in parallel mode LN_out adds 1/K of its result into v, so the mean needs no launch)
+    and keeps h = relu(.), the mask m, the hidden pre-norm z and the row statistics; LN_in(net) * m is recomputed in the
+    backward.  x feeds every block's mask layer and (parallel) every LN_in: those gradients are summed here, in block
+    order, by the LayerNorm backward's accumulate flag and rp_accumulate — autograd sees ONE gradient of x."""
+
+    @staticmethod
+    def forward(ctx, x, parallel: bool, eps_in, eps_out, *params):
+        x = _unit_inner(x)
+        nb = len(params) // 10
+        d, agg = params[0].numel(), params[2].shape[0]
+        B, dev = x.shape[0], x.device
+        Wx, ag4 = (max(x.shape[1], d) + 3) // 4 * 4, (agg + 3) // 4 * 4
+
+        def buf(w=Wx):
+            return torch.empty((B, w), dtype=torch.float32, device=dev)
+
+        v, net, st_in, kept = buf(), x, None, []
+        for k in range(nb):
+            g_in, b_in, W1, c1, W2, c2, Wh, ch, g_o, b_o = params[10 * k:10 * k + 10]
+            h = buf(ag4)[:, :agg]
+            hip.linear_fwd(x, _rows16(W1), c1, ACT_RELU, K=d, out=h)
+            m = buf()
+            hip.linear_fwd(h, _rows16(W2), c2, ACT_NONE, K=agg, out=m[:, :d])
+            shared = parallel and k > 0  # every parallel block normalises the same x: one set of statistics
+            nm, st_in = hip.layernorm_fwd(net, g_in, b_in, eps_in[k], mul=m, out=buf(), stats=st_in if shared else None,
+                                          stats_given=shared)
+            z = buf()
+            hip.linear_fwd(nm, _rows16(Wh), ch, ACT_NONE, K=d, out=z[:, :d])
+            if parallel:
+                _, st_o = hip.layernorm_fwd(z, g_o, b_o, eps_out[k], out=v, out_scale=1.0 / nb, accumulate=k > 0)
+                kept += [h, m, z, st_o]
+            else:
+                nxt = v if k == nb - 1 else buf()
+                _, st_o = hip.layernorm_fwd(z, g_o, b_o, eps_out[k], out=nxt)
+                kept += [h, m, z, st_o, net, st_in]
+                net = nxt
+        if parallel:
+            kept.append(st_in)
+        ctx.parallel, ctx.nb, ctx.eps_in, ctx.Wx = parallel, nb, eps_in, Wx
+        ctx.save_for_backward(x, *params, *kept)
+        return v
+
+    @staticmethod
+    def backward(ctx, dv):
+        parallel, nb, Wx = ctx.parallel, ctx.nb, ctx.Wx
+        saved = ctx.saved_tensors
+        x, params, kept = saved[0], saved[1:1 + 10 * nb], saved[1 + 10 * nb:]
+        d, agg = params[0].numel(), params[2].shape[0]
+        B, dev = x.shape[0], x.device
+        ag4 = (agg + 3) // 4 * 4
+        grads = [None] * (10 * nb)
+        g, dx = _unit_inner(dv), None
+        per = 4 if parallel else 6
+        for k in (range(nb) if parallel else reversed(range(nb))):
+            g_in, b_in, W1, c1, W2, c2, Wh, ch, g_o, b_o = params[10 * k:10 * k + 10]
+            h, m, z, st_o = kept[per * k:per * k + 4]
+            net, st_in = (x, kept[-1]) if parallel else kept[per * k + 4:per * k + 6]
+            dz, _, dgo, dbo = hip.layernorm_bwd(g, z, st_o, g_o, b_o, dy_scale=1.0 / nb if parallel else 1.0)
+            nm, _ = hip.layernorm_fwd(net, g_in, b_in, ctx.eps_in[k], mul=m, stats=st_in, stats_given=True,
+                                      out=torch.empty((B, Wx), dtype=torch.float32, device=dev))
+            dWh, dch = hip.linear_wgrad(dz[:, :d], nm, d)
+            dnm = hip.linear_fwd(dz, hip.transpose(Wh, rows_out=Wx), None, ACT_NONE)
+            if parallel or k == 0:  # LN_in normalised x itself: its gradient joins the others' in dx
+                dx, dm, dgi, dbi = hip.layernorm_bwd(dnm, net, st_in, g_in, b_in, mul=m, dx=dx, accumulate=dx is not None)
+            else:
+                g, dm, dgi, dbi = hip.layernorm_bwd(dnm, net, st_in, g_in, b_in, mul=m)
+            dW2, dc2 = hip.linear_wgrad(dm[:, :d], h, agg)
+            dh = torch.empty((B, ag4), dtype=torch.float32, device=dev)[:, :agg]
+            hip.linear_fwd(dm, hip.transpose(W2), None, ACT_MASK, aux=h, out=dh)
+            dW1, dc1 = hip.linear_wgrad(dh, x, d)
+            dxm = hip.linear_fwd(dh, hip.transpose(W1, rows_out=x.shape[1]), None, ACT_NONE)
+            dx = dxm if dx is None else hip.accumulate(dx, dxm)
+            grads[10 * k:10 * k + 10] = [dgi, dbi, dW1, dc1, dW2, dc2, dWh, dch, dgo, dbo]
+        return (dx if ctx.needs_input_grad[0] else None, None, None, None, *grads)
+
+
+def mask_block_stack(x, blocks, parallel: bool):
+    """the stack of MaskBlock modules `blocks` applied to the padded row buffer x (see _MaskBlockStack); -> [B, ceil4(W)]"""
+    params = []
+    for b in blocks:
+        params += [b._input_layer_norm.weight, b._input_layer_norm.bias, b._mask_layer[0].weight, b._mask_layer[0].bias,
+                   b._mask_layer[2].weight, b._mask_layer[2].bias, b._hidden_layer.weight, b._hidden_layer.bias,
+                   b._layer_norm.weight, b._layer_norm.bias]
+    eps_in = tuple(float(b._input_layer_norm.eps) for b in blocks)
+    eps_out = tuple(float(b._layer_norm.eps) for b in blocks)
+    return _MaskBlockStack.apply(x, bool(parallel), eps_in, eps_out, *params)
+
+
 class _DiceGate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, xhat, alpha):

@@ -13,7 +13,7 @@ from typing import List, Optional, Sequence
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 107  # csrc/common.hip: rp_version() — bumped with every change of the entry points' prototypes
+ABI_VERSION = 108  # csrc/common.hip: rp_version() — bumped with every change of the entry points' prototypes
 LIB_PATH = os.environ.get("RP_LIB_PATH") or os.path.join(_HERE, "lib", "librecpangu_hip.so")  # (override: A/B builds)
 MAX_FIELDS = 64
 
@@ -163,6 +163,10 @@ _SIGNATURES = {
     "rp_batchnorm_colsum": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
     "rp_batchnorm_bwd_sums": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
     "rp_batchnorm_bwd_apply": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
+    "rp_layernorm_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp, _i64, _i32, _f32, _i32, _vp, _i32, _i64, _i32, _vp]),
+    "rp_layernorm_bwd_workspace_bytes": (C.c_int, [_i32, C.POINTER(_sz)]),
+    "rp_layernorm_bwd": (C.c_int, [_vp, _i64, _f32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp,
+                                   _vp, _i64, _i32, _vp, _sz, _vp]),
     "rp_dice_gate_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp]),
     "rp_dice_gate_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
     "rp_mlp_tail_fits": (C.c_int, [_i32, _i32, _i64]),
@@ -1952,6 +1956,65 @@ def batchnorm_apply(x, mean, rstd, gamma, beta):
         _check(lib().rp_batchnorm_apply(x.data_ptr(), _rowmajor(x, "x"), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma),
                                         _ptr(beta), y.data_ptr(), N, M, N, _stream()), "rp_batchnorm_apply")
     return y
+
+
+def layernorm_fwd(x, gamma, beta, eps: float, mul=None, out=None, out_scale: float = 1.0, accumulate: bool = False,
+                  stats=None, stats_given: bool = False):
+    """-> (y, stats).  y = out_scale * (LayerNorm(x[:, :N]) [* mul[:, :N]]) over the N = gamma.numel() leading columns of the
+    2-D x, written (accumulate: added) into `out` [M, >= N] (default: a fresh [M, N]); out's columns from N on are written
+    as zeros.  stats [M, 2] = (mean, 1 / sqrt(var + eps)) per row: made here or, with stats_given, read."""
+    _req(x, torch.float32, "x")
+    _req(gamma, torch.float32, "gamma")
+    _req(beta, torch.float32, "beta")
+    M, N = x.shape[0], gamma.numel()
+    if x.dim() != 2 or x.shape[1] < N or beta.numel() != N or (mul is not None and (mul.shape[0] != M or mul.shape[1] < N)):
+        raise RuntimeError(f"layernorm_fwd: x {tuple(x.shape)} / mul against {N} normalised columns")
+    if out is None:
+        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    if out.shape[0] != M or out.shape[1] < N:
+        raise RuntimeError(f"layernorm_fwd: out {tuple(out.shape)} for [{M}, >= {N}]")
+    if stats is None:
+        if stats_given:
+            raise RuntimeError("layernorm_fwd: stats_given without stats")
+        stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
+    ldmul = _rowmajor(mul, "mul") if mul is not None else 0
+    with _Timed("layernorm_fwd", f"{M}x{N}" + ("*mul" if mul is not None else "") + ("+=" if accumulate else ""),
+                4 * M * N * (2 + (mul is not None) + bool(accumulate))):
+        _check(lib().rp_layernorm_fwd(x.data_ptr(), _rowmajor(x, "x"), gamma.data_ptr(), beta.data_ptr(), eps, _ptr(mul), ldmul,
+                                      out.data_ptr(), _rowmajor(out, "out"), out.shape[1], out_scale, int(accumulate),
+                                      _ptr(stats), int(stats_given), M, N, _stream()), "rp_layernorm_fwd")
+    return out, stats
+
+
+def layernorm_bwd(dy, x, stats, gamma, beta, mul=None, dy_scale: float = 1.0, dx=None, accumulate: bool = False):
+    """-> (dx, dmul, dgamma, dbeta) of layernorm_fwd for the incoming dy [M, >= N] (times dy_scale).  dx [M, x.shape[1]]
+    (fresh, or the given one; accumulate: added to it), zeros in its columns from N on; dmul [M, mul.shape[1]] (columns
+    from N on are not written) or None."""
+    _req(dy, torch.float32, "dy")
+    _req(x, torch.float32, "x")
+    M, N = x.shape[0], gamma.numel()
+    dev = x.device
+    if dx is None:
+        if accumulate:
+            raise RuntimeError("layernorm_bwd: accumulate without dx")
+        dx = torch.empty((M, x.shape[1]), dtype=torch.float32, device=dev)
+    dmul = torch.empty((M, mul.shape[1]), dtype=torch.float32, device=dev) if mul is not None else None
+    dgamma, dbeta = (torch.empty((N,), dtype=torch.float32, device=dev) for _ in range(2))
+    if M == 0:
+        return dx, dmul, dgamma.zero_(), dbeta.zero_()
+    nbytes = _sz(0)
+    _check(lib().rp_layernorm_bwd_workspace_bytes(N, C.byref(nbytes)), "rp_layernorm_bwd_workspace_bytes")
+    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+    _held(ws)
+    with _Timed("layernorm_bwd", f"{M}x{N}" + ("*mul" if mul is not None else "") + ("+=" if accumulate else ""),
+                4 * M * N * (3 + 2 * (mul is not None) + bool(accumulate))):
+        _check(lib().rp_layernorm_bwd(dy.data_ptr(), _rowmajor(dy, "dy"), dy_scale, x.data_ptr(), _rowmajor(x, "x"),
+                                      stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(mul),
+                                      _rowmajor(mul, "mul") if mul is not None else 0, dx.data_ptr(), _rowmajor(dx, "dx"),
+                                      dx.shape[1], int(accumulate), _ptr(dmul), _rowmajor(dmul, "dmul") if dmul is not None else 0,
+                                      dgamma.data_ptr(), dbeta.data_ptr(), M, N, ws.data_ptr(), nbytes.value, _stream()),
+               "rp_layernorm_bwd")
+    return dx, dmul, dgamma, dbeta
 
 
 def dice_gate_fwd(x, xhat, alpha):

@@ -3,10 +3,10 @@ from .embedding import EmbeddingLayer
 from .deep import MLP
 from .shallow import LR_Layer
 from .interaction import (InnerProductLayer, FM_Layer, CrossInteractionLayer, CrossNet,
-                          CompressedInteractionNet)
+                          CompressedInteractionNet, MaskBlock)
 from .attention import ScaledDotProductAttention, MultiHeadAttention, MultiHeadSelfAttention
 from .sequence import MaskedAveragePooling, MaskedSumPooling
 
 __all__ = ["Dice", "get_activation", "EmbeddingLayer", "MLP", "LR_Layer", "InnerProductLayer", "FM_Layer",
-           "CrossInteractionLayer", "CrossNet", "CompressedInteractionNet", "ScaledDotProductAttention",
+           "CrossInteractionLayer", "CrossNet", "CompressedInteractionNet", "MaskBlock", "ScaledDotProductAttention",
            "MultiHeadAttention", "MultiHeadSelfAttention", "MaskedAveragePooling", "MaskedSumPooling"]

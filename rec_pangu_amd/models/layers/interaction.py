@@ -1,6 +1,6 @@
 """Feature-interaction blocks of the hot path — drop-ins for rec_pangu/models/layers/interaction.py:
 InnerProductLayer (:12-52, the two pooling outputs the ranking models use), FM_Layer (:225-235),
-CrossInteractionLayer / CrossNet (:119-141), CompressedInteractionNet (:144-171).
+CrossInteractionLayer / CrossNet (:119-141), CompressedInteractionNet (:144-171), MaskBlock (:254-283).
 Parameter names/shapes follow the reference so its checkpoints load.
 """
 import torch
@@ -200,3 +200,36 @@ class CompressedInteractionNet(nn.Module):
             pooled.append(X_i.sum(dim=-1))
         out = self.fc(torch.cat(pooled, dim=-1))
         return [out] if as_list else out
+
+
+class MaskBlock(nn.Module):
+    """LN_out(hidden(LN_in(net) * mask(mask_input)))  (interaction.py:254-283): the instance-guided mask is a two-layer
+    bottleneck (mask_input_dim -> int(mask_input_dim * reduction_factor) -> input_dim, ReLU between) that multiplies the
+    normalised input elementwise.  Module names are the reference's (`_input_layer_norm`, `_mask_layer.{0,2}`,
+    `_hidden_layer`, `_layer_norm`).
+
+    On a HIP device: the mask's Linears and the hidden Linear are matrix-core launches, each LayerNorm one launch
+    (rp_layernorm_fwd; the first one multiplies by the mask inside, so LN_in(net) is never stored).  MaskNet does not call
+    its blocks one by one: it runs the whole stack on one autograd node (functional.mask_block_stack)."""
+
+    def __init__(self, input_dim: int, mask_input_dim: int, output_size: int, reduction_factor: float) -> None:
+        super(MaskBlock, self).__init__()
+        self._input_layer_norm = nn.LayerNorm(input_dim)
+        aggregation_size = int(mask_input_dim * reduction_factor)
+        self._mask_layer = nn.Sequential(nn.Linear(mask_input_dim, aggregation_size), nn.ReLU(),
+                                         nn.Linear(aggregation_size, input_dim))
+        self._hidden_layer = nn.Linear(input_dim, output_size)
+        self._layer_norm = nn.LayerNorm(output_size)
+
+    def forward(self, net, mask_input):
+        if net.is_cuda and net.dtype == torch.float32:
+            from ... import functional as Fh
+            lead = net.shape[:-1]
+            net, mask_input = net.reshape(-1, net.shape[-1]), mask_input.reshape(-1, mask_input.shape[-1])
+            h = Fh.linear_act(mask_input, self._mask_layer[0].weight, self._mask_layer[0].bias, Fh.ACT_RELU)
+            mask = Fh.linear_act(h, self._mask_layer[2].weight, self._mask_layer[2].bias)
+            hidden = Fh.linear_act(Fh.layer_norm(net, self._input_layer_norm, mul=mask), self._hidden_layer.weight,
+                                   self._hidden_layer.bias)
+            return Fh.layer_norm(hidden, self._layer_norm).reshape(*lead, -1)
+        masked = self._input_layer_norm(net) * self._mask_layer(mask_input)
+        return self._layer_norm(self._hidden_layer(masked))

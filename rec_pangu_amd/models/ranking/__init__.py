@@ -6,5 +6,6 @@ from .fm import FM
 from .wdl import WDL
 from .nfm import NFM
 from .lr import LR
+from .masknet import MaskNet
 
-__all__ = ["DeepFM", "xDeepFM", "DCN", "AutoInt", "FM", "WDL", "NFM", "LR"]
+__all__ = ["DeepFM", "xDeepFM", "DCN", "AutoInt", "FM", "WDL", "NFM", "LR", "MaskNet"]
