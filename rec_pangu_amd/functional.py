@@ -3,6 +3,7 @@
 Everything here takes HIP-device fp32 tensors; nothing in this module computes on the CPU and
 nothing falls back: a missing librecpangu_hip.so raises from hip.lib().
 """
+import contextlib
 import os
 from typing import List, Sequence
 
@@ -1411,15 +1412,14 @@ class _EmbedGatherLinear(torch.autograd.Function):
         seg = need_w and ctx.x_mode == "seg"
         dw_seg = torch.empty((64, ctx.K), dtype=torch.float32, device=dpre.device) if seg else None
 
-        def wgrad(keep=None):
+        def wgrad():
             if ctx.x_mode == "seg":    # x holds the dense columns only (xd [B, 64]); their columns of dw and the bias gradient
-                _, db_ = hip.linear_wgrad(dpre, x, ctx.K - ctx.Kg, dw=dw_seg[:, ctx.Kg:], want_bias=ctx.has_bias, keep=keep)
-                return dw_seg, db_
+                return dw_seg, hip.linear_wgrad(dpre, x, ctx.K - ctx.Kg, dw=dw_seg[:, ctx.Kg:], want_bias=ctx.has_bias)[1]
             if ctx.x_mode == "bf16":   # the activation was stored as bf16 (bf16-storage training)
-                return hip.linear_wgrad_xbf16(dpre, x, ctx.K, want_bias=ctx.has_bias, keep=keep)
+                return hip.linear_wgrad_xbf16(dpre, x, ctx.K, want_bias=ctx.has_bias)
             if ctx.x_mode == "dense":  # x holds the dense columns only: the embedding columns are gathered from the arena
                 return hip.linear_wgrad_gather(dpre, store.arena, keys, ctx.Kg, x, ctx.K, want_bias=ctx.has_bias)
-            return hip.linear_wgrad(dpre, x, ctx.K, want_bias=ctx.has_bias, keep=keep)
+            return hip.linear_wgrad(dpre, x, ctx.K, want_bias=ctx.has_bias)
 
         # The weight gradient (streams x: 0.15 ms at Criteo shape) and the fused gather backward (bound by its random row
         # gathers, ~1 TB/s of HBM: 0.30 ms) both depend only on dpre and are independent of each other: the weight gradient
@@ -1427,91 +1427,90 @@ class _EmbedGatherLinear(torch.autograd.Function):
         wstream = _wgrad_stream(dpre.device) if (need_w and need_t) else None
         # ... and while a LAUNCH PLAN is being recorded (a captured step: one stream), the side launches are marked as an
         # inline section (plan.side2): the replay issues them on the plan's second side stream, joined after the gather
-        # backward.  Their workspaces stay referenced (`keep`) until the join: the side launches run beside the ones issued
-        # behind them, and the capture's one-stream allocator would hand those their memory at once.
+        # backward; until that join hip.holding() keeps every tensor hip allocates (launches that run BESIDE others: hip.py).
         plan = hip.LaunchPlan
         in_plan = (wstream is None and need_w and need_t and ctx.x_mode != "dense"
                    and os.environ.get("RP_WGRAD_OVERLAP", "1") != "0" and plan.is_recording())
-        keep = [] if in_plan else None
 
         def side_wgrad():
             with plan.side2(in_plan):
-                out = wgrad(keep)
+                out = wgrad()
                 if in_plan:
                     plan.run_deferred()  # (e.g. the MLP tail's second stage: behind the weight gradient, not in front)
             return out
 
         # THE ISSUE ORDER of the first layer's backward: {a plan is recording} x {dw's embedding columns come from the gather
         # backward (seg)}.  Except when both hold, the weight gradient goes first: in front, or beside on the second stream.
-        if wstream is not None:
-            main = torch.cuda.current_stream(dpre.device)
-            wstream.wait_stream(main)
-            with torch.cuda.stream(wstream):
-                dw, db = wgrad()
-        elif need_w and not (in_plan and seg):
-            dw, db = side_wgrad()
-        if need_t:
-            wt = ctx.wt if ctx.wt is not None else hip.transpose(weight, rows_out=ctx.ldx)
-            gfm = dfm.contiguous() if dfm is not None else None
-            g = store.first_layer_grad(keys, ctx.B, dpre, wt, gfm, ssum if gfm is not None else None, presorted=ctx.presorted,
-                                       w=weight if seg else None, dw=dw_seg, keep=keep)
-            f = g.forms
-            if not seg:  # (recording or not) the tiny tables on the side, one row-sorted launch for all others
-                if f.tiny:
-                    with plan.side2(in_plan):
-                        g.tiny()
-                g.gemm()
-            elif not in_plan:  # the caller's stream: tiny, sample-major, row-sorted, the launches behind the sample-major one
-                if f.tiny:
-                    g.tiny()
-                ws = g.big(1) if f.big else None
-                if f.rest:
-                    g.rest()
-                if f.big:
-                    g.big(2, ws)
-            else:
-                # (round 5) the LONG main-stream launch is issued first and the short side launches behind it, all forked from
-                # the same point (plan.fork2_mark) — issued the other way round the side launches filled every CU and
-                # rp_embed_grad_seg (77 KB of LDS per workgroup) started 58 us late (profiles/r05_trace_step.txt)
-                # Measured (profiles/r05 lines, alternating runs on one box): 0.946 / 0.947 ms with the main launch first against
-                # 0.929 / 0.932 the other way round (long-run means equal, 0.906-0.916): the side launches then stretch to twice
-                # their time and the join comes later
-                # (re-measured at the end of round 5, after the loss head moved into the MLP tail and the side streams went to
-                #  the lowest priority: main launch first 0.8324 / 0.8375 ms against 0.8369 / 0.8384 in the 20-step window,
-                #  0.8086 / 0.8099 against 0.8152 / 0.8161 over 600 steps)
-                # (round 6) with big tables the sample-major launch is that long launch; the tiny tables' launches are forked IN
-                # FRONT of it and run beside it on the second stream, and the launches behind the sample-major one follow them
-                # there (plan.side2_sync: that stream waits for the sample-major launch at that point); without tiny tables the
-                # fork is marked behind the sample-major launch
-                if f.tiny or not f.big:
-                    plan.fork2_mark()
-                if f.big:
-                    ws = g.big(1)
+        with hip.holding() if in_plan else contextlib.nullcontext():
+            if wstream is not None:
+                main = torch.cuda.current_stream(dpre.device)
+                wstream.wait_stream(main)
+                with torch.cuda.stream(wstream):
+                    dw, db = wgrad()
+            elif need_w and not (in_plan and seg):
+                dw, db = side_wgrad()
+            if need_t:
+                wt = ctx.wt if ctx.wt is not None else hip.transpose(weight, rows_out=ctx.ldx)
+                gfm = dfm.contiguous() if dfm is not None else None
+                g = store.first_layer_grad(keys, ctx.B, dpre, wt, gfm, ssum if gfm is not None else None, presorted=ctx.presorted,
+                                           w=weight if seg else None, dw=dw_seg)
+                f = g.forms
+                if not seg:  # (recording or not) the tiny tables on the side, one row-sorted launch for all others
                     if f.tiny:
+                        with plan.side2(in_plan):
+                            g.tiny()
+                    g.gemm()
+                elif not in_plan:  # the caller's stream: tiny, sample-major, row-sorted, the launches behind the sample-major one
+                    if f.tiny:
+                        g.tiny()
+                    ws = g.big(1) if f.big else None
+                    if f.rest:
+                        g.rest()
+                    if f.big:
+                        g.big(2, ws)
+                else:
+                    # (round 5) the LONG main-stream launch is issued first and the short side launches behind it, all forked from
+                    # the same point (plan.fork2_mark) — issued the other way round the side launches filled every CU and
+                    # rp_embed_grad_seg (77 KB of LDS per workgroup) started 58 us late (profiles/r05_trace_step.txt)
+                    # Measured (profiles/r05 lines, alternating runs on one box): 0.946 / 0.947 ms with the main launch first
+                    # against 0.929 / 0.932 the other way round (long-run means equal, 0.906-0.916): the side launches then stretch
+                    # to twice their time and the join comes later
+                    # (re-measured at the end of round 5, after the loss head moved into the MLP tail and the side streams went to
+                    #  the lowest priority: main launch first 0.8324 / 0.8375 ms against 0.8369 / 0.8384 in the 20-step window,
+                    #  0.8086 / 0.8099 against 0.8152 / 0.8161 over 600 steps)
+                    # (round 6) with big tables the sample-major launch is that long launch; the tiny tables' launches are forked IN
+                    # FRONT of it and run beside it on the second stream, and the launches behind the sample-major one follow them
+                    # there (plan.side2_sync: that stream waits for the sample-major launch at that point); without tiny tables the
+                    # fork is marked behind the sample-major launch
+                    if f.tiny or not f.big:
+                        plan.fork2_mark()
+                    if f.big:
+                        ws = g.big(1)
+                        if f.tiny:
+                            with plan.side2():
+                                g.tiny()
+                            plan.side2_sync()
+                        else:
+                            plan.fork2_mark()
+                    # (the streaming segment-sum launch uses no LDS, but it cannot run BESIDE the sample-major launch on a second
+                    #  stream: 4 x 112 and 2 x 240 registers per SIMD lane do not fit the file of 512 together — one after the
+                    #  other on the main stream)
+                    if f.rest:
+                        g.rest()
+                    if f.big:
+                        # on the second stream beside the row-sorted form's launches; in ISSUE order behind those: issued in front
+                        # of them, the 4096 short workgroups of the duplicate reduce held the segment-sum launch up by 56 us
+                        # (profiles/r06 trace notes)
+                        with plan.side2():
+                            g.big(2, ws)
+                    elif f.tiny:  # (no sample-major launch: behind the long main-stream launch in issue order)
                         with plan.side2():
                             g.tiny()
-                        plan.side2_sync()
-                    else:
-                        plan.fork2_mark()
-                # (the streaming segment-sum launch uses no LDS, but it cannot run BESIDE the sample-major launch on a second
-                #  stream: 4 x 112 and 2 x 240 registers per SIMD lane do not fit the file of 512 together — one after the other
-                #  on the main stream)
-                if f.rest:
-                    g.rest()
-                if f.big:
-                    # on the second stream beside the row-sorted form's launches; in ISSUE order behind those: issued in front of
-                    # them, the 4096 short workgroups of the duplicate reduce held the segment-sum launch up by 56 us
-                    # (profiles/r06 trace notes)
-                    with plan.side2():
-                        g.big(2, ws)
-                elif f.tiny:  # (no sample-major launch: behind the long main-stream launch in issue order)
-                    with plan.side2():
-                        g.tiny()
-            g.done()
-        if in_plan:
-            if seg:
-                dw, db = side_wgrad()
-            plan.join()
+                g.done()
+            if in_plan:
+                if seg:
+                    dw, db = side_wgrad()
+                plan.join()
         if wstream is not None:
             main.wait_stream(wstream)  # whoever consumes dw / db (AccumulateGrad, the optimizer) is ordered behind them
             dw.record_stream(main)     # (allocated under the second stream, consumed and freed on the main one)

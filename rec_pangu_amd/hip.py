@@ -311,6 +311,56 @@ def _rowmajor(t: torch.Tensor, name: str) -> int:
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
 
 
+# ---- device memory: ONE allocator, and one rule for recorded steps ----------------------------------------------------
+# Every device tensor this module allocates — outputs, workspaces, internal scratch — comes from `_new`; while a
+# `holding()` block is open, `_new` keeps it referenced by the block's list.  Why: inside a stream capture the allocator
+# hands a freed block to the NEXT allocation of the same capture — fine for launches that replay in recorded order on one
+# stream, wrong for launches the replay runs BESIDE others (a plan's inline section between its fork and its join, the
+# row-sharded step's look-ahead segments): a temporary one of them dropped would be overwritten by its neighbour on
+# every replay.  Whoever records such launches opens the block around them and everything they run beside.
+_HOLDING = None
+
+
+class holding:
+    """with holding() as items: ...  (nestable: an inner block collects its own tensors; closed behind an exception too)"""
+
+    def __enter__(self):
+        global _HOLDING
+        self.prev, self.items = _HOLDING, []
+        _HOLDING = self.items
+        return self.items
+
+    def __exit__(self, *exc):
+        global _HOLDING
+        _HOLDING = self.prev
+        return False
+
+    @staticmethod
+    def active() -> bool:
+        return _HOLDING is not None
+
+
+def _new(shape, dtype, device):
+    t = torch.empty(shape, dtype=dtype, device=device)
+    if _HOLDING is not None:
+        _HOLDING.append(t)
+    return t
+
+
+def _new_like(t):
+    return _new(t.shape, t.dtype, t.device)
+
+
+def _workspace(query: str, *dims, device, given=None):
+    """-> (uint8 workspace, bytes) of the size rp_<query>_workspace_bytes(*dims) asks for; given: a caller's persistent
+    workspace, taken instead of a fresh one when it is on the device and large enough"""
+    name, nbytes = f"rp_{query}_workspace_bytes", _sz(0)
+    _check(getattr(lib(), name)(*dims, C.byref(nbytes)), name)
+    if given is not None and given.numel() >= nbytes.value and given.device == device:
+        return given, nbytes.value
+    return _new((nbytes.value,), torch.uint8, device), nbytes.value
+
+
 # ---- optional per-entry-point timing with HIP events on the launch stream (bench.py's roofline) ----
 _timing = None
 
@@ -413,10 +463,10 @@ def embed_gather_fwd(arena, row_base, row_count, idx: List[torch.Tensor], dense:
         if t.dim() != 1 or t.shape[0] != B or not t.is_contiguous():
             raise RuntimeError("dense tensors must be contiguous float32 [B]")
     dev = arena.device
-    x = torch.empty((B, ldx), dtype=torch.float32, device=dev)
-    fm = torch.empty((B, 1), dtype=torch.float32, device=dev) if want_fm else None
-    ssum = torch.empty((B, D), dtype=torch.float32, device=dev) if want_sum else None
-    keys = torch.empty((F * B,), dtype=torch.int32, device=dev) if want_keys else None
+    x = _new((B, ldx), torch.float32, dev)
+    fm = _new((B, 1), torch.float32, dev) if want_fm else None
+    ssum = _new((B, D), torch.float32, dev) if want_sum else None
+    keys = _new((F * B,), torch.int32, dev) if want_keys else None
     with _Timed("embed_gather_fwd", f"D={D}"):
         _check(lib().rp_embed_gather_fwd(arena.data_ptr(), row_base.data_ptr(), row_count.data_ptr(), _ptr_array(idx), F,
                                      _ptr_array(dense), ND, B, D, x.data_ptr(), ldx, _ptr(fm), _ptr(ssum), _ptr(keys),
@@ -447,12 +497,12 @@ def embed_gather_linear_fwd(arena, row_base, row_count, idx: List[torch.Tensor],
             raise RuntimeError("dense tensors must be contiguous float32 [B]")
     dev = arena.device
     assert x_mode in ("full", "dense", "none")
-    x = torch.empty((B, ldx), dtype=torch.float32, device=dev) if x_mode == "full" else None
-    xd = torch.empty((B, 64), dtype=torch.float32, device=dev) if x_mode == "dense" else None
-    h1 = torch.empty((B, 64), dtype=torch.float32, device=dev)
-    fm = torch.empty((B, 1), dtype=torch.float32, device=dev) if want_fm else None
-    ssum = torch.empty((B, D), dtype=torch.float32, device=dev) if want_sum else None
-    keys = torch.empty((F * B,), dtype=torch.int32, device=dev) if want_keys else None
+    x = _new((B, ldx), torch.float32, dev) if x_mode == "full" else None
+    xd = _new((B, 64), torch.float32, dev) if x_mode == "dense" else None
+    h1 = _new((B, 64), torch.float32, dev)
+    fm = _new((B, 1), torch.float32, dev) if want_fm else None
+    ssum = _new((B, D), torch.float32, dev) if want_sum else None
+    keys = _new((F * B,), torch.int32, dev) if want_keys else None
     K = F * D + ND
     # algorithmic bytes (rows + ids read, the [B, F*D+ND] output written — counted whether or not the launch
     # stores it, the figure the gather is priced on) + h1
@@ -474,14 +524,14 @@ def embed_gather_linear_fwd_bf16(arena_bf16, row_base, row_count, idx: List[torc
     F, ND = len(idx), len(dense)
     B, D = idx[0].shape[0], arena_bf16.shape[1]
     dev = arena_bf16.device
-    h1 = torch.empty((B, 64), dtype=torch.float32, device=dev)
-    fm = torch.empty((B, 1), dtype=torch.float32, device=dev)
+    h1 = _new((B, 64), torch.float32, dev)
+    fm = _new((B, 1), torch.float32, dev)
     K = F * D + ND
     if train_ldx:
-        x16 = None if dense_only else torch.empty((B, train_ldx), dtype=torch.bfloat16, device=dev)
-        xd = torch.empty((B, 64), dtype=torch.float32, device=dev) if dense_only else None
-        ssum = torch.empty((B, D), dtype=torch.float32, device=dev)
-        keys = torch.empty((F * B,), dtype=torch.int32, device=dev) if want_keys else None
+        x16 = None if dense_only else _new((B, train_ldx), torch.bfloat16, dev)
+        xd = _new((B, 64), torch.float32, dev) if dense_only else None
+        ssum = _new((B, D), torch.float32, dev)
+        keys = _new((F * B,), torch.int32, dev) if want_keys else None
         # algorithmic bytes: bf16 rows + ids read, the bf16 activation "written" (SURVEY 8d's figure, whether or not the launch
         # stores it), h1 + the field sums
         with _Timed("embed_gather_linear_fwd_bf16", f"D={D}", B * (F * (D * 2 + 8) + (F * D + ND) * 2 + 64 * 4 + D * 4), 2 * B * K * 64):
@@ -504,28 +554,20 @@ def embed_gather_linear_fwd_bf16(arena_bf16, row_base, row_count, idx: List[torc
 
 def sort_workspace(n: int, device) -> torch.Tensor:
     """a workspace rp_sort_pairs_i32 accepts for n pairs (callers that must not allocate per call keep one)"""
-    nbytes = _sz(0)
-    _check(lib().rp_sort_workspace_bytes(n, C.byref(nbytes)), "rp_sort_workspace_bytes")
-    return torch.empty((nbytes.value,), dtype=torch.uint8, device=device)
+    return _workspace("sort", n, device=device)[0]
 
 
 def sort_pairs(keys: torch.Tensor, end_bit: int = 32, out=None, workspace=None):
-    """out = (sorted keys, positions) to write into (persistent buffers of the captured-step path), else fresh tensors;
-    workspace: a persistent sort_workspace(n) (else one is allocated per call)"""
+    """out = (sorted keys, positions) to write into (persistent buffers of the captured-step path; either may be None), else
+    fresh tensors; workspace: a persistent sort_workspace(n) (else one is allocated per call)"""
     _req(keys, torch.int32, "keys")
     n = keys.numel()
-    nbytes = _sz(0)
-    _check(lib().rp_sort_workspace_bytes(n, C.byref(nbytes)), "rp_sort_workspace_bytes")
-    if workspace is not None:
-        assert workspace.numel() >= nbytes.value and workspace.device == keys.device
-        ws = workspace
-    else:
-        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=keys.device)
-    ko, po = out if out is not None else (torch.empty_like(keys), torch.empty_like(keys))
+    ws, nbytes = _workspace("sort", n, device=keys.device, given=workspace)
+    assert workspace is None or ws is workspace
+    ko, po = (_new_like(keys) if t is None else t for t in (out or (None, None)))
     assert ko.shape == keys.shape and po.shape == keys.shape and ko.dtype == po.dtype == torch.int32
-    _held(keys, ws, ko, po)
     with _Timed("sort_pairs_i32"):
-        _check(lib().rp_sort_pairs_i32(ws.data_ptr(), nbytes.value, keys.data_ptr(), ko.data_ptr(), po.data_ptr(), n,
+        _check(lib().rp_sort_pairs_i32(ws.data_ptr(), nbytes, keys.data_ptr(), ko.data_ptr(), po.data_ptr(), n,
                                    end_bit, _stream()), "rp_sort_pairs_i32")
     return ko, po
 
@@ -534,9 +576,7 @@ _SORT_FIELDS: dict = {}
 
 
 def sort_fields_workspace(B: int, F: int, device) -> torch.Tensor:
-    nbytes = _sz(0)
-    _check(lib().rp_sort_pairs_fields_workspace_bytes(B, F, C.byref(nbytes)), "rp_sort_pairs_fields_workspace_bytes")
-    return torch.empty((nbytes.value,), dtype=torch.uint8, device=device)
+    return _workspace("sort_pairs_fields", B, F, device=device)[0]
 
 
 def sort_pairs_fields(keys: torch.Tensor, B: int, field_rows, out=None, workspace=None):
@@ -556,15 +596,9 @@ def sort_pairs_fields(keys: torch.Tensor, B: int, field_rows, out=None, workspac
             base.append(acc)
             acc += r
         arrs = _SORT_FIELDS[ck] = ((C.c_int64 * F)(*base), (C.c_int64 * F)(*ck))
-    nbytes = _sz(0)
-    _check(lib().rp_sort_pairs_fields_workspace_bytes(B, F, C.byref(nbytes)), "rp_sort_pairs_fields_workspace_bytes")
-    if workspace is not None and workspace.numel() >= nbytes.value and workspace.device == keys.device:
-        ws = workspace
-    else:
-        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=keys.device)
-    ko, po = out if out is not None else (torch.empty_like(keys), torch.empty_like(keys))
+    ws, _ = _workspace("sort_pairs_fields", B, F, device=keys.device, given=workspace)
+    ko, po = (_new_like(keys) if t is None else t for t in (out or (None, None)))
     assert ko.shape == keys.shape and po.shape == keys.shape and ko.dtype == po.dtype == torch.int32
-    _held(keys, ws, ko, po)
     with _Timed("sort_pairs_i32"):  # (the same row of the per-kernel table as the plain sort: it is that sort)
         _check(lib().rp_sort_pairs_fields_i32(ws.data_ptr(), ws.numel(), keys.data_ptr(), ko.data_ptr(), po.data_ptr(), B, F,
                                               arrs[0], arrs[1], _stream()), "rp_sort_pairs_fields_i32")
@@ -577,14 +611,11 @@ def embed_grad_reduce(sorted_keys, sorted_pos, B: int, D: int, dx, gfm, sum_in, 
     if dx is not None:
         _req(dx, torch.float32, "dx")
         ldx = _rowmajor(dx, "dx")
-    nbytes = _sz(0)
-    _check(lib().rp_embed_grad_reduce_workspace_bytes(sorted_keys.numel(), D, C.byref(nbytes)),
-           "rp_embed_grad_reduce_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=grad_arena.device)
+    ws, nbytes = _workspace("embed_grad_reduce", sorted_keys.numel(), D, device=grad_arena.device)
     with _Timed("embed_grad_reduce", f"D={D}"):
         _check(lib().rp_embed_grad_reduce(sorted_keys.data_ptr(), sorted_pos.data_ptr(), sorted_keys.numel(), B, D,
                                       _ptr(dx), ldx, _ptr(gfm), _ptr(sum_in), _ptr(arena), grad_arena.data_ptr(),
-                                      int(accumulate), ws.data_ptr(), nbytes.value, _stream()), "rp_embed_grad_reduce")
+                                      int(accumulate), ws.data_ptr(), nbytes, _stream()), "rp_embed_grad_reduce")
 
 
 def embed_grad_gemm_fits(D: int, hidden: int, dh, wt) -> bool:
@@ -592,11 +623,10 @@ def embed_grad_gemm_fits(D: int, hidden: int, dh, wt) -> bool:
         and dh.data_ptr() % 16 == 0 and wt.data_ptr() % 16 == 0
 
 
-def embed_grad_tiny(keys, B: int, tiny, dh, wt, gfm, sum_in, arena, grad_arena, accumulate: bool, keep=None, dw=None):
+def embed_grad_tiny(keys, B: int, tiny, dh, wt, gfm, sum_in, arena, grad_arena, accumulate: bool, dw=None):
     """rp_embed_grad_tiny: the gradient rows of the tiny tables `tiny` = [(field, first arena row, rows), ...] from the
-    unsorted pair keys [F * B] (sample-major one-hot GEMMs).  keep: a list that receives the workspace (launches that run
-    beside later ones inside a recorded plan).  dw [64, K]: the tiny tables' columns of the first layer's weight gradient
-    are written into it as well (the companion of embed_grad_seg)."""
+    unsorted pair keys [F * B] (sample-major one-hot GEMMs).  dw [64, K]: the tiny tables' columns of the first layer's
+    weight gradient are written into it as well (the companion of embed_grad_seg)."""
     _req(keys, torch.int32, "keys")
     _req(dh, torch.float32, "dh")
     n = len(tiny)
@@ -605,16 +635,12 @@ def embed_grad_tiny(keys, B: int, tiny, dh, wt, gfm, sum_in, arena, grad_arena, 
     if arrs is None:
         arrs = _TINY_ARRAYS[ckey] = ((C.c_int32 * n)(*[t[0] for t in tiny]), (C.c_int64 * n)(*[t[1] for t in tiny]),
                                      (C.c_int32 * n)(*[t[2] for t in tiny]))
-    nbytes = _sz(0)
-    _check(lib().rp_embed_grad_tiny_workspace_bytes(B, C.byref(nbytes)), "rp_embed_grad_tiny_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=grad_arena.device)
-    if keep is not None:
-        keep.append(ws)
+    ws, nbytes = _workspace("embed_grad_tiny", B, device=grad_arena.device)
     with _Timed("embed_grad_tiny", f"{n} tables", B * (64 * 8 + 4 + 4 * n)):
         _check(lib().rp_embed_grad_tiny(keys.data_ptr(), B, arrs[0], arrs[1], arrs[2], n, dh.data_ptr(), _rowmajor(dh, "dh"),
                                         wt.data_ptr(), _rowmajor(wt, "wt"), _ptr(gfm), _ptr(sum_in), _ptr(arena),
                                         grad_arena.data_ptr(), int(accumulate), _ptr(dw),
-                                        _rowmajor(dw, "dw") if dw is not None else 0, ws.data_ptr(), nbytes.value, _stream()),
+                                        _rowmajor(dw, "dw") if dw is not None else 0, ws.data_ptr(), nbytes, _stream()),
                "rp_embed_grad_tiny")
 
 
@@ -629,15 +655,12 @@ def embed_grad_gemm(sorted_keys, sorted_pos, B: int, D: int, dh, wt, dx, gfm, su
     _req(dh, torch.float32, "dh")
     _req(wt, torch.float32, "wt")
     ldx = _rowmajor(dx, "dx") if dx is not None else 0
-    nbytes = _sz(0)
-    _check(lib().rp_embed_grad_reduce_workspace_bytes(sorted_keys.numel(), D, C.byref(nbytes)),
-           "rp_embed_grad_reduce_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=grad_arena.device)
+    ws, nbytes = _workspace("embed_grad_reduce", sorted_keys.numel(), D, device=grad_arena.device)
     with _Timed("embed_grad_gemm", f"D={D}"):
         _check(lib().rp_embed_grad_gemm(sorted_keys.data_ptr(), sorted_pos.data_ptr(), sorted_keys.numel(), B, D,
                                         dh.data_ptr(), _rowmajor(dh, "dh"), wt.data_ptr(), _rowmajor(wt, "wt"), _ptr(dx), ldx,
                                         _ptr(gfm), _ptr(sum_in), _ptr(arena), grad_arena.data_ptr(), int(accumulate),
-                                        skip_fields, ws.data_ptr(), nbytes.value, _stream()), "rp_embed_grad_gemm")
+                                        skip_fields, ws.data_ptr(), nbytes, _stream()), "rp_embed_grad_gemm")
 
 
 def embed_grad_seg_fits(D: int, hidden: int, dh) -> bool:
@@ -647,8 +670,19 @@ def embed_grad_seg_fits(D: int, hidden: int, dh) -> bool:
 _SEG_ROWS: dict = {}
 
 
+def _seg_rows(field_rows):
+    """the table sizes per field as a ctypes array (None stays None), built once per distinct tuple"""
+    if field_rows is None:
+        return None
+    ck = tuple(field_rows)
+    fr = _SEG_ROWS.get(ck)
+    if fr is None:
+        fr = _SEG_ROWS[ck] = (C.c_int64 * len(ck))(*ck)
+    return fr
+
+
 def embed_grad_seg(sorted_keys, sorted_pos, B: int, D: int, dh, w, gfm, sum_in, arena, grad_arena, accumulate: bool,
-                   skip_fields: int = 0, field_rows=None, dw=None, keep=None):
+                   skip_fields: int = 0, field_rows=None, dw=None):
     """rp_embed_grad_seg: the first layer's whole backward on the embedding columns, segment-sum first — the table
     gradient rows (dgrad of `w` [64, K] formed per run of equal keys + the FM term) AND, with dw [64, K], the embedding
     columns of the layer's weight gradient from the table rows the launch reads anyway (no stored activation).
@@ -657,22 +691,13 @@ def embed_grad_seg(sorted_keys, sorted_pos, B: int, D: int, dh, w, gfm, sum_in, 
     _req(dh, torch.float32, "dh")
     _req(w, torch.float32, "w")
     n = sorted_keys.numel()
-    fr = None
-    if field_rows is not None:
-        ck = tuple(field_rows)
-        fr = _SEG_ROWS.get(ck)
-        if fr is None:
-            fr = _SEG_ROWS[ck] = (C.c_int64 * len(ck))(*ck)
-    nbytes = _sz(0)
-    _check(lib().rp_embed_grad_seg_workspace_bytes(n, B, D, C.byref(nbytes)), "rp_embed_grad_seg_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=grad_arena.device)
-    if keep is not None:
-        keep.append(ws)
+    fr = _seg_rows(field_rows)
+    ws, nbytes = _workspace("embed_grad_seg", n, B, D, device=grad_arena.device)
     with _Timed("embed_grad_seg", f"D={D}"):  # (algorithmic bytes / flops: bench.py knows the unique-row count)
         _check(lib().rp_embed_grad_seg(sorted_keys.data_ptr(), sorted_pos.data_ptr(), n, B, D, dh.data_ptr(), _rowmajor(dh, "dh"),
                                        w.data_ptr(), _rowmajor(w, "w"), _ptr(gfm), _ptr(sum_in), arena.data_ptr(),
                                        grad_arena.data_ptr(), int(accumulate), skip_fields, fr, _ptr(dw),
-                                       _rowmajor(dw, "dw") if dw is not None else 0, ws.data_ptr(), nbytes.value, _stream()),
+                                       _rowmajor(dw, "dw") if dw is not None else 0, ws.data_ptr(), nbytes, _stream()),
                "rp_embed_grad_seg")
 
 
@@ -703,9 +728,9 @@ def embed_grad_smp_mark(sorted_keys, sorted_pos, B: int, fields, out=None):
     if out is None:
         nsc = _sz(0)
         _check(lib().rp_embed_grad_smp_mark_scratch(B, nf, C.byref(nsc)), "rp_embed_grad_smp_mark_scratch")
-        out = (torch.empty((nf * B,), dtype=torch.int32, device=sorted_keys.device),
-               torch.empty((nf * B,), dtype=torch.int32, device=sorted_keys.device),
-               torch.empty((nsc.value,), dtype=torch.int32, device=sorted_keys.device))
+        out = (_new((nf * B,), torch.int32, sorted_keys.device),
+               _new((nf * B,), torch.int32, sorted_keys.device),
+               _new((nsc.value,), torch.int32, sorted_keys.device))
     with _Timed("embed_grad_smp_mark", f"{nf} fields", 16 * nf * B):
         _check(lib().rp_embed_grad_smp_mark(sorted_keys.data_ptr(), sorted_pos.data_ptr(), sorted_keys.numel(), B,
                                             _smp_fields(fields)[0], nf, out[0].data_ptr(), out[1].data_ptr(), out[2].data_ptr(),
@@ -714,7 +739,7 @@ def embed_grad_smp_mark(sorted_keys, sorted_pos, B: int, fields, out=None):
 
 
 def embed_grad_smp(keys, marks, B: int, F: int, fields, dh, w, gfm, sum_in, arena, grad_arena, accumulate: bool, dw=None,
-                   keep=None, phases: int = 3, ws=None):
+                   phases: int = 3, ws=None):
     """rp_embed_grad_smp: the first layer's backward on the embedding columns of the big tables `fields`, sample-major (the
     table rows' gradient incl. the FM term + those fields' columns of dw [64, K]); `fields` = [(field, first arena row,
     rows), ...] ascending; `marks` = embed_grad_smp_mark's pair.  phases = 1: the main launch only, 2: the launches behind
@@ -724,18 +749,13 @@ def embed_grad_smp(keys, marks, B: int, F: int, fields, dh, w, gfm, sum_in, aren
     _req(w, torch.float32, "w")
     _req(grad_arena, torch.float32, "grad_arena")
     nf = len(fields)
-    nbytes = _sz(0)
-    _check(lib().rp_embed_grad_smp_workspace_bytes(B, nf, C.byref(nbytes)), "rp_embed_grad_smp_workspace_bytes")
-    if ws is None:
-        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=grad_arena.device)
-        if keep is not None:
-            keep.append(ws)
+    ws, nbytes = _workspace("embed_grad_smp", B, nf, device=grad_arena.device, given=ws)
     fa = _smp_fields(fields)
     with _Timed("embed_grad_smp" if phases & 1 else "embed_grad_smp_behind", f"{nf} fields"):
         _check(lib().rp_embed_grad_smp(keys.data_ptr(), marks[0].data_ptr(), marks[1].data_ptr(), B, F, fa[0], fa[1], fa[2], nf,
                                        dh.data_ptr(), _rowmajor(dh, "dh"), w.data_ptr(), _rowmajor(w, "w"), _ptr(gfm),
                                        _ptr(sum_in), arena.data_ptr(), grad_arena.data_ptr(), int(accumulate), _ptr(dw),
-                                       _rowmajor(dw, "dw") if dw is not None else 0, phases, ws.data_ptr(), nbytes.value, _stream()),
+                                       _rowmajor(dw, "dw") if dw is not None else 0, phases, ws.data_ptr(), nbytes, _stream()),
                "rp_embed_grad_smp")
     return ws
 
@@ -745,11 +765,9 @@ def embed_grad_reduce_rows(keys, rows, grad_arena, accumulate: bool):
     _req(keys, torch.int32, "keys")
     _req(rows, torch.float32, "rows")
     n, D = keys.numel(), rows.shape[1]
-    nbytes = _sz(0)
-    _check(lib().rp_embed_grad_reduce_workspace_bytes(n, D, C.byref(nbytes)), "rp_embed_grad_reduce_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=grad_arena.device)
+    ws, nbytes = _workspace("embed_grad_reduce", n, D, device=grad_arena.device)
     _check(lib().rp_embed_grad_reduce_rows(keys.data_ptr(), rows.data_ptr(), n, D, grad_arena.data_ptr(), int(accumulate),
-                                           ws.data_ptr(), nbytes.value, _stream()), "rp_embed_grad_reduce_rows")
+                                           ws.data_ptr(), nbytes, _stream()), "rp_embed_grad_reduce_rows")
 
 
 def embed_grad_ss_mark(sorted_keys, B: int, skip_fields: int, out=None):
@@ -762,9 +780,9 @@ def embed_grad_ss_mark(sorted_keys, B: int, skip_fields: int, out=None):
     if out is None:
         nr, no = _sz(0), _sz(0)
         _check(lib().rp_embed_grad_ss_mark_sizes(B, kept, C.byref(nr), C.byref(no)), "rp_embed_grad_ss_mark_sizes")
-        out = (torch.empty((nr.value,), dtype=torch.int32, device=sorted_keys.device),
-               torch.empty((nr.value,), dtype=torch.int32, device=sorted_keys.device),
-               torch.empty((no.value,), dtype=torch.int32, device=sorted_keys.device))
+        out = (_new((nr.value,), torch.int32, sorted_keys.device),
+               _new((nr.value,), torch.int32, sorted_keys.device),
+               _new((no.value,), torch.int32, sorted_keys.device))
     with _Timed("embed_grad_ss_mark", f"{kept} fields", 12 * kept * B):
         _check(lib().rp_embed_grad_ss_mark(sorted_keys.data_ptr(), n, B, skip_fields, out[0].data_ptr(), out[1].data_ptr(),
                                            out[2].data_ptr(), _stream()), "rp_embed_grad_ss_mark")
@@ -772,7 +790,7 @@ def embed_grad_ss_mark(sorted_keys, B: int, skip_fields: int, out=None):
 
 
 def embed_grad_ss(sorted_keys, sorted_pos, B: int, D: int, dh, w, gfm, sum_in, arena, grad_arena, accumulate: bool,
-                  skip_fields: int = 0, field_rows=None, dw=None, keep=None, phases: int = 3, ws=None, marks=None):
+                  skip_fields: int = 0, field_rows=None, dw=None, phases: int = 3, ws=None, marks=None):
     """rp_embed_grad_ss: embed_grad_seg's work as a streaming segment-sum launch + a matrix launch over the unique rows (the
     mid-size tables' share of the first layer's backward); same arguments and results up to fp32 summation order.
     marks: embed_grad_ss_mark's triple for this sort and skip_fields (None: made inside the call).
@@ -781,25 +799,15 @@ def embed_grad_ss(sorted_keys, sorted_pos, B: int, D: int, dh, w, gfm, sum_in, a
     _req(dh, torch.float32, "dh")
     _req(w, torch.float32, "w")
     n = sorted_keys.numel()
-    fr = None
-    if field_rows is not None:
-        ck = tuple(field_rows)
-        fr = _SEG_ROWS.get(ck)
-        if fr is None:
-            fr = _SEG_ROWS[ck] = (C.c_int64 * len(ck))(*ck)
-    nbytes = _sz(0)
-    _check(lib().rp_embed_grad_ss_workspace_bytes(n, B, D, skip_fields, C.byref(nbytes)), "rp_embed_grad_ss_workspace_bytes")
-    if ws is None:
-        ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=grad_arena.device)
-        if keep is not None:
-            keep.append(ws)
+    fr = _seg_rows(field_rows)
+    ws, nbytes = _workspace("embed_grad_ss", n, B, D, skip_fields, device=grad_arena.device, given=ws)
     with _Timed("embed_grad_ss" if phases & 2 else "embed_grad_segsum", f"D={D}"):
         _check(lib().rp_embed_grad_ss(sorted_keys.data_ptr(), sorted_pos.data_ptr(), n, B, D, dh.data_ptr(), _rowmajor(dh, "dh"),
                                       w.data_ptr(), _rowmajor(w, "w"), _ptr(gfm), _ptr(sum_in), arena.data_ptr(),
                                       grad_arena.data_ptr(), int(accumulate), skip_fields, fr, _ptr(dw),
                                       _rowmajor(dw, "dw") if dw is not None else 0,
                                       None if marks is None else marks[0].data_ptr(), None if marks is None else marks[1].data_ptr(),
-                                      None if marks is None else marks[2].data_ptr(), phases, ws.data_ptr(), nbytes.value, _stream()),
+                                      None if marks is None else marks[2].data_ptr(), phases, ws.data_ptr(), nbytes, _stream()),
                "rp_embed_grad_ss")
     return ws
 
@@ -807,7 +815,7 @@ def embed_grad_ss(sorted_keys, sorted_pos, B: int, D: int, dh, w, gfm, sum_in, a
 def zeros(shape, dtype, device):
     """torch.zeros through the library's own fill launch (rp_fill_words): inside a recorded step an ATen fill kernel would
     keep the step from replaying as a launch plan"""
-    t = torch.empty(shape, dtype=dtype, device=device)
+    t = _new(shape, dtype, device)
     nb = t.numel() * t.element_size()
     if nb % 4 != 0 or t.data_ptr() % 16 != 0:
         return t.zero_()
@@ -831,7 +839,7 @@ def linear_fwd(a, w, bias, act: int = ACT_NONE, aux=None, K: Optional[int] = Non
     if a.shape[1] < K:
         raise RuntimeError(f"linear_fwd: a has {a.shape[1]} columns, need {K}")
     if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=a.device)
+        out = _new((M, N), torch.float32, a.device)
     ldo = _rowmajor(out, "out")
     ldaux = _rowmajor(aux, "aux") if aux is not None else 0
     with _Timed("linear_fwd", f"{M}x{N}x{K}", 4 * (M * K + N * K + M * N * (2 if aux is not None else 1)), 2 * M * N * K):
@@ -856,43 +864,34 @@ def linear_fwd_rowadd(a, w, row_scale, row_add, add_cols: int, out) -> bool:
     return True
 
 
-def linear_wgrad(dy, x, K: int, dw=None, db=None, accumulate: bool = False, want_bias: bool = True, keep=None):
-    """dw[N,K] = dy[M,N]^T @ x[:, :K]; db[N] = colsum(dy).  keep: a list that receives the launch's workspace (a caller that
-    lets the launch run beside later ones keeps it alive until they are joined)."""
+def linear_wgrad(dy, x, K: int, dw=None, db=None, accumulate: bool = False, want_bias: bool = True):
+    """dw[N,K] = dy[M,N]^T @ x[:, :K]; db[N] = colsum(dy)."""
     _req(dy, torch.float32, "dy")
     _req(x, torch.float32, "x")
     M, N = dy.shape
     lddy, ldx = _rowmajor(dy, "dy"), _rowmajor(x, "x")
     if dw is None:
-        dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
+        dw = _new((N, K), torch.float32, dy.device)
     if db is None and want_bias:
-        db = torch.empty((N,), dtype=torch.float32, device=dy.device)
-    nbytes = _sz(0)
-    _check(lib().rp_linear_wgrad_workspace_bytes(M, N, K, C.byref(nbytes)), "rp_linear_wgrad_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dy.device)
-    if keep is not None:
-        keep.append(ws)
+        db = _new((N,), torch.float32, dy.device)
+    ws, nbytes = _workspace("linear_wgrad", M, N, K, device=dy.device)
     with _Timed("linear_wgrad", f"{M}x{N}x{K}", 4 * (M * N + M * K + N * K), 2 * M * N * K):
         _check(lib().rp_linear_wgrad(dy.data_ptr(), lddy, x.data_ptr(), ldx, dw.data_ptr(), _rowmajor(dw, "dw"), _ptr(db),
-                                 M, N, K, int(accumulate), ws.data_ptr(), nbytes.value, _stream()), "rp_linear_wgrad")
+                                 M, N, K, int(accumulate), ws.data_ptr(), nbytes, _stream()), "rp_linear_wgrad")
     return dw, db
 
 
-def linear_wgrad_xbf16(dy, x16, K: int, want_bias: bool = True, keep=None):
+def linear_wgrad_xbf16(dy, x16, K: int, want_bias: bool = True):
     """rp_linear_wgrad_xbf16: dw[N, K] = dy^T @ x16[:, :K] with the activation stored as bfloat16 (bf16-storage training)"""
     _req(dy, torch.float32, "dy")
     _req(x16, torch.bfloat16, "x16")
     M, N = dy.shape
-    dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
-    db = torch.empty((N,), dtype=torch.float32, device=dy.device) if want_bias else None
-    nbytes = _sz(0)
-    _check(lib().rp_linear_wgrad_workspace_bytes(M, N, K, C.byref(nbytes)), "rp_linear_wgrad_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dy.device)
-    if keep is not None:
-        keep.append(ws)
+    dw = _new((N, K), torch.float32, dy.device)
+    db = _new((N,), torch.float32, dy.device) if want_bias else None
+    ws, nbytes = _workspace("linear_wgrad", M, N, K, device=dy.device)
     with _Timed("linear_wgrad_xbf16", f"{M}x{N}x{K}", 4 * (M * N + N * K) + 2 * M * K, 2 * M * N * K):
         _check(lib().rp_linear_wgrad_xbf16(dy.data_ptr(), _rowmajor(dy, "dy"), x16.data_ptr(), _rowmajor(x16, "x16"),
-                                           dw.data_ptr(), K, _ptr(db), M, N, K, 0, ws.data_ptr(), nbytes.value, _stream()),
+                                           dw.data_ptr(), K, _ptr(db), M, N, K, 0, ws.data_ptr(), nbytes, _stream()),
                "rp_linear_wgrad_xbf16")
     return dw, db
 
@@ -909,15 +908,13 @@ def linear_wgrad_gather(dy, arena, keys, Kg: int, xd, K: int, want_bias: bool = 
     _req(keys, torch.int32, "keys")
     M, N = dy.shape
     assert keys.numel() == (Kg // 64) * M and arena.shape[1] == 64
-    dw = torch.empty((N, K), dtype=torch.float32, device=dy.device)
-    db = torch.empty((N,), dtype=torch.float32, device=dy.device) if want_bias else None
-    nbytes = _sz(0)
-    _check(lib().rp_linear_wgrad_workspace_bytes(M, N, K, C.byref(nbytes)), "rp_linear_wgrad_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dy.device)
+    dw = _new((N, K), torch.float32, dy.device)
+    db = _new((N,), torch.float32, dy.device) if want_bias else None
+    ws, nbytes = _workspace("linear_wgrad", M, N, K, device=dy.device)
     with _Timed("linear_wgrad_gather", f"{M}x{N}x{K}", 4 * (M * N + M * K + N * K), 2 * M * N * K):
         _check(lib().rp_linear_wgrad_gather(dy.data_ptr(), _rowmajor(dy, "dy"), arena.data_ptr(), keys.data_ptr(), Kg, _ptr(xd),
                                             _rowmajor(xd, "xd") if xd is not None else 0, dw.data_ptr(), K, _ptr(db), M, N, K,
-                                            0, ws.data_ptr(), nbytes.value, _stream()), "rp_linear_wgrad_gather")
+                                            0, ws.data_ptr(), nbytes, _stream()), "rp_linear_wgrad_gather")
     return dw, db
 
 
@@ -928,7 +925,7 @@ def transpose(w, rows_out: Optional[int] = None):
     R, Cc = w.shape
     R4 = (R + 3) // 4 * 4  # 16-byte aligned rows (the GEMM then fetches them with dwordx4, unguarded)
     rows = max(Cc, rows_out or 0)
-    out = torch.empty((rows, R4), dtype=torch.float32, device=w.device)[:, :R]
+    out = _new((rows, R4), torch.float32, w.device)[:, :R]
     with _Timed("transpose", f"{R}x{Cc}", 4 * (R * Cc + rows * R)):
         _check(lib().rp_transpose(w.data_ptr(), _rowmajor(w, "w"), out.data_ptr(), R4, R, Cc, rows, _stream()),
                "rp_transpose")
@@ -941,8 +938,8 @@ def transpose_copy(w, rows_out: int, ld_copy: int):
     R, Cc = w.shape
     R4 = (R + 3) // 4 * 4
     rows = max(Cc, rows_out or 0)
-    out = torch.empty((rows, R4), dtype=torch.float32, device=w.device)[:, :R]
-    buf = torch.empty((R, ld_copy), dtype=torch.float32, device=w.device)
+    out = _new((rows, R4), torch.float32, w.device)[:, :R]
+    buf = _new((R, ld_copy), torch.float32, w.device)
     with _Timed("transpose_copy", f"{R}x{Cc}", 4 * (2 * R * Cc + rows * R)):
         _check(lib().rp_transpose_copy(w.data_ptr(), _rowmajor(w, "w"), out.data_ptr(), R4, R, Cc, rows, buf.data_ptr(), ld_copy,
                                        _stream()), "rp_transpose_copy")
@@ -961,7 +958,7 @@ def pieces_pack(x, np_: int = 2, K: Optional[int] = None, out=None):
     K = x.shape[1] if K is None else K
     ldo = pieces_ld(K, np_)
     if out is None:
-        out = torch.empty((M, ldo), dtype=torch.bfloat16, device=x.device)
+        out = _new((M, ldo), torch.bfloat16, x.device)
     with _Timed("pieces_pack", f"{M}x{K}x{np_}", 4 * M * K + 2 * M * ldo):
         _check(lib().rp_pieces_pack(x.data_ptr(), _rowmajor(x, "x"), M, K, np_, out.data_ptr(), _rowmajor(out, "out"), _stream()),
                "rp_pieces_pack")
@@ -975,7 +972,7 @@ def linear_fwd_pieces(a_pc, w_pc, bias, K: int, np_: int = 2, act: int = ACT_NON
     _req(w_pc, torch.bfloat16, "w_pc")
     M, N = a_pc.shape[0], w_pc.shape[0]
     if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=a_pc.device)
+        out = _new((M, N), torch.float32, a_pc.device)
     ldaux = _rowmajor(aux, "aux") if aux is not None else 0
     with _Timed("linear_fwd_pieces", f"{M}x{N}x{K}x{np_}", 2 * (M + N) * pieces_ld(K, np_) + 4 * M * N * (2 if aux is not None else 1),
                 2 * M * N * K):
@@ -989,7 +986,7 @@ def copy_rows(w, ld_out: int):
     """a copy of the 2-D tensor w with row stride ld_out >= w.shape[1] (rp_copy_rows); returns the [R, C] view of it"""
     _req(w, torch.float32, "w")
     R, Cc = w.shape
-    buf = torch.empty((R, ld_out), dtype=torch.float32, device=w.device)
+    buf = _new((R, ld_out), torch.float32, w.device)
     with _Timed("copy_rows", f"{R}x{Cc}", 8 * R * Cc):
         _check(lib().rp_copy_rows(w.data_ptr(), _rowmajor(w, "w"), buf.data_ptr(), ld_out, R, Cc, _stream()), "rp_copy_rows")
     return buf[:, :Cc]
@@ -1140,15 +1137,16 @@ class LaunchPlan:
         _check(lib().rp_plan_fork2_mark(), "rp_plan_fork2_mark")
 
     # launches a recording step wants on the inline section (2) but has no hurry with: issued behind the next launches
-    # recorded there (run_deferred), at the latest in front of the section's join; `keep` = the tensors they touch (the
-    # capture's allocator would hand their memory to the launches recorded in between)
+    # recorded there (run_deferred), at the latest in front of the section's join.  `_kept` holds the callables until then
+    # (join / end), and through their closures the tensors they touch: the capture's allocator would hand that memory to
+    # the launches recorded in between
     _deferred: list = []
     _kept: list = []
 
     @classmethod
-    def defer_side(cls, fn, keep=()):
+    def defer_side(cls, fn):
         cls._deferred.append(fn)
-        cls._kept.append(keep)
+        cls._kept.append(fn)
 
     @classmethod
     def run_deferred(cls):
@@ -1298,32 +1296,6 @@ class LaunchPlan:
 _COPY_PLANS: dict = {}
 
 
-# Tensors the wrappers below allocate while a `holding()` block is open stay referenced by its list.  Why: inside a stream
-# capture the allocator hands a freed block to the NEXT allocation of the same capture — fine for launches that replay in
-# recorded order on one stream, wrong for a group of launches the replay runs on another stream BESIDE the rest (the
-# row-sharded step's look-ahead: graph_step).  Their temporaries — also the ones a wrapper allocates and drops internally —
-# must outlive the recording of everything they run beside.
-_HOLDING = None
-
-
-class holding:
-    def __enter__(self):
-        global _HOLDING
-        self.prev, self.items = _HOLDING, []
-        _HOLDING = self.items
-        return self.items
-
-    def __exit__(self, *exc):
-        global _HOLDING
-        _HOLDING = self.prev
-        return False
-
-
-def _held(*tensors):
-    if _HOLDING is not None:
-        _HOLDING.extend(t for t in tensors if t is not None)
-
-
 def make_side_stream(device, role: str = "sort") -> "torch.cuda.Stream":
     """a stream for work that runs BESIDE the main stream (the next batch's sort, the side work of the first layer's backward):
     of the LOWEST priority the device offers (rp_stream_create_low, wrapped as an ExternalStream), so that the main stream's
@@ -1401,7 +1373,7 @@ def graph_node_counts(raw_graph: int):
 
 def relu_bwd(dy, act_out):
     M, N = dy.shape
-    out = torch.empty((M, N), dtype=torch.float32, device=dy.device)
+    out = _new((M, N), torch.float32, dy.device)
     with _Timed("relu_bwd", f"{M}x{N}", 12 * M * N):
         _check(lib().rp_relu_bwd(dy.data_ptr(), _rowmajor(dy, "dy"), act_out.data_ptr(), _rowmajor(act_out, "act_out"),
                              out.data_ptr(), N, M, N, _stream()), "rp_relu_bwd")
@@ -1411,7 +1383,7 @@ def relu_bwd(dy, act_out):
 def act_bwd(dy, act_out, act: int):
     """dy * act'(.) through the activation's output (rp_act_bwd; act = ACT_RELU / TANH / SIGMOID / LEAKY)"""
     M, N = dy.shape
-    out = torch.empty((M, N), dtype=torch.float32, device=dy.device)
+    out = _new((M, N), torch.float32, dy.device)
     with _Timed("act_bwd", f"{M}x{N}", 12 * M * N):
         _check(lib().rp_act_bwd(dy.data_ptr(), _rowmajor(dy, "dy"), act_out.data_ptr(), _rowmajor(act_out, "act_out"),
                                 out.data_ptr(), N, M, N, act, _stream()), "rp_act_bwd")
@@ -1421,7 +1393,7 @@ def act_bwd(dy, act_out, act: int):
 def act_fwd(x, act: int):
     """act(x) as a launch of its own (rp_act_fwd), 2-D x"""
     M, N = x.shape
-    out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    out = _new((M, N), torch.float32, x.device)
     with _Timed("act_fwd", f"{M}x{N}", 8 * M * N):
         _check(lib().rp_act_fwd(x.data_ptr(), _rowmajor(x, "x"), out.data_ptr(), N, M, N, act, _stream()), "rp_act_fwd")
     return out
@@ -1432,9 +1404,9 @@ def crossnet_fwd(x0, d: int, W, Bv, wfc=None, bfc=None, want_x: bool = True):
     _req(x0, torch.float32, "x0")
     B, L = x0.shape[0], W.shape[0]
     dev = x0.device
-    xout = torch.empty((B, d), dtype=torch.float32, device=dev) if want_x else None
-    logit = torch.empty((B, 1), dtype=torch.float32, device=dev) if wfc is not None else None
-    s = torch.empty((B, L), dtype=torch.float32, device=dev)
+    xout = _new((B, d), torch.float32, dev) if want_x else None
+    logit = _new((B, 1), torch.float32, dev) if wfc is not None else None
+    s = _new((B, L), torch.float32, dev)
     with _Timed("crossnet_fwd"):
         _check(lib().rp_crossnet_fwd(x0.data_ptr(), _rowmajor(x0, "x0"), d, L, W.data_ptr(), Bv.data_ptr(), _ptr(wfc),
                                      _ptr(bfc), _ptr(xout), d, _ptr(logit), s.data_ptr(), B, _stream()),
@@ -1445,7 +1417,7 @@ def crossnet_fwd(x0, d: int, W, Bv, wfc=None, bfc=None, want_x: bool = True):
 def crossnet_bwd_rows(x0, d: int, W, wfc, s, g_x, g_logit):
     """-> dx0 [B, x0.shape[1]] (columns >= d zeroed), V [B, 2L+2] (see rp_crossnet_bwd_rows)."""
     B, L = x0.shape[0], W.shape[0]
-    dx0 = torch.empty_like(x0)
+    dx0 = _new_like(x0)
     ldg = _rowmajor(g_x, "g_x") if g_x is not None else 0
     # the vectorised kernel writes whole dwordx4 up to the leading dimension (exact zeros beyond d); only the unaligned form
     # leaves the padding columns to a fill (an ATen launch: it kept a DCN step from replaying as a launch plan)
@@ -1453,7 +1425,7 @@ def crossnet_bwd_rows(x0, d: int, W, wfc, s, g_x, g_logit):
            and (g_x is None or (ldg % 4 == 0 and g_x.data_ptr() % 16 == 0)) and x0.shape[1] <= (d + 255) // 256 * 256)
     if x0.shape[1] > d and not vec:
         dx0[:, d:].zero_()
-    V = torch.empty((B, 2 * L + 2), dtype=torch.float32, device=x0.device)
+    V = _new((B, 2 * L + 2), torch.float32, x0.device)
     with _Timed("crossnet_bwd_rows"):
         _check(lib().rp_crossnet_bwd_rows(x0.data_ptr(), _rowmajor(x0, "x0"), d, L, W.data_ptr(), _ptr(wfc),
                                           s.data_ptr(), _ptr(g_x), ldg, _ptr(g_logit), dx0.data_ptr(),
@@ -1465,9 +1437,9 @@ def crossnet_param_grads(P, cs, W, Bv, wfc, colg):
     """(dW [L, d], dB [L, d], dwfc [d] or None) of the CrossNet from the skinny weight gradient P = V^T X_0 and the column
     sums cs of V (rp_crossnet_param_grads)"""
     L, d = W.shape
-    dW = torch.empty((L, d), dtype=torch.float32, device=W.device)
-    dB = torch.empty((L, d), dtype=torch.float32, device=W.device)
-    dwfc = torch.empty((d,), dtype=torch.float32, device=W.device) if wfc is not None else None
+    dW = _new((L, d), torch.float32, W.device)
+    dB = _new((L, d), torch.float32, W.device)
+    dwfc = _new((d,), torch.float32, W.device) if wfc is not None else None
     with _Timed("crossnet_param_grads", f"{L}x{d}"):
         _check(lib().rp_crossnet_param_grads(P.data_ptr(), _rowmajor(P, "P"), cs.data_ptr(), W.data_ptr(), Bv.data_ptr(), _ptr(wfc),
                                              _ptr(colg), L, d, dW.data_ptr(), dB.data_ptr(), _ptr(dwfc), _stream()),
@@ -1481,8 +1453,8 @@ def cin_layer_fwd(x0, xp, W, bias, H: int, M: int, D: int, want_out: bool, want_
     _req(x0, torch.float32, "x0")
     _req(xp, torch.float32, "xp")
     B, O = x0.shape[0], W.shape[0]
-    out = torch.empty((B, O, D), dtype=torch.float32, device=x0.device) if want_out else None
-    pooled = torch.empty((B, O), dtype=torch.float32, device=x0.device) if want_pool else None
+    out = _new((B, O, D), torch.float32, x0.device) if want_out else None
+    pooled = _new((B, O), torch.float32, x0.device) if want_pool else None
     with _Timed("cin_layer_fwd"):
         _check(lib().rp_cin_layer_fwd(x0.data_ptr(), _rowmajor(x0, "x0"), xp.data_ptr(), _rowmajor(xp, "xp"),
                                       W.data_ptr(), _ptr(bias), _ptr(out), _ptr(pooled), O, H, M, O, D, B, _stream()),
@@ -1494,25 +1466,23 @@ def cin_layer_bwd(x0, xp, W, H: int, M: int, D: int, g_out, g_pool, want_bias: b
     """Gradients of one CIN layer: -> (dx0 like x0, dxp [B, M*D] or None when xp is x0, dW like W, dbias [O] or None)."""
     B, O = x0.shape[0], W.shape[0]
     same = xp is x0
-    dx0 = torch.empty_like(x0)
+    dx0 = _new_like(x0)
     if x0.shape[1] > H * D:
         dx0[:, H * D:].zero_()
-    dxp = None if same else torch.empty((B, M * D), dtype=torch.float32, device=x0.device)
+    dxp = None if same else _new((B, M * D), torch.float32, x0.device)
     ldgp = _rowmajor(g_pool, "g_pool") if g_pool is not None else 0
     with _Timed("cin_layer_bwd_x"):
         _check(lib().rp_cin_layer_bwd_x(x0.data_ptr(), _rowmajor(x0, "x0"), xp.data_ptr(), _rowmajor(xp, "xp"),
                                         W.data_ptr(), _ptr(g_out), _ptr(g_pool), ldgp, dx0.data_ptr(),
                                         _rowmajor(dx0, "dx0"), 0, _ptr(dxp), M * D, H, M, O, D, B, _stream()),
                "rp_cin_layer_bwd_x")
-    dW = torch.empty_like(W)
-    db = torch.empty((O,), dtype=torch.float32, device=x0.device) if want_bias else None
-    nbytes = _sz(0)
-    _check(lib().rp_cin_layer_bwd_w_workspace_bytes(B, H, M, O, C.byref(nbytes)), "rp_cin_layer_bwd_w_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=x0.device)
+    dW = _new_like(W)
+    db = _new((O,), torch.float32, x0.device) if want_bias else None
+    ws, nbytes = _workspace("cin_layer_bwd_w", B, H, M, O, device=x0.device)
     with _Timed("cin_layer_bwd_w"):
         _check(lib().rp_cin_layer_bwd_w(x0.data_ptr(), _rowmajor(x0, "x0"), xp.data_ptr(), _rowmajor(xp, "xp"),
                                         _ptr(g_out), _ptr(g_pool), ldgp, dW.data_ptr(), _ptr(db), H, M, O, D, B,
-                                        ws.data_ptr(), nbytes.value, _stream()), "rp_cin_layer_bwd_w")
+                                        ws.data_ptr(), nbytes, _stream()), "rp_cin_layer_bwd_w")
     return dx0, dxp, dW, db
 
 
@@ -1525,7 +1495,7 @@ def field_attention_fwd(x, W, T: int, Din: int, H: int, a: int, has_res: bool, s
     _req(x, torch.float32, "x")
     _req(W, torch.float32, "W")
     B = x.shape[0]
-    out = torch.empty((B, T, H * a), dtype=torch.float32, device=x.device)
+    out = _new((B, T, H * a), torch.float32, x.device)
     with _Timed("field_attention_fwd"):
         _check(lib().rp_field_attention_fwd(x.data_ptr(), _rowmajor(x, "x"), W.data_ptr(), T, Din, H, a, int(has_res),
                                             scale, out.data_ptr(), B, _stream()), "rp_field_attention_fwd")
@@ -1536,18 +1506,15 @@ def field_attention_bwd(x, W, T: int, Din: int, H: int, a: int, has_res: bool, s
     B = x.shape[0]
     dx = None
     if want_dx:
-        dx = torch.empty_like(x)
+        dx = _new_like(x)
         if x.shape[1] > T * Din:
             dx[:, T * Din:].zero_()
-    dW = torch.empty_like(W)
-    nbytes = _sz(0)
-    _check(lib().rp_field_attention_bwd_workspace_bytes(B, T, Din, H, a, int(has_res), C.byref(nbytes)),
-           "rp_field_attention_bwd_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=x.device)
+    dW = _new_like(W)
+    ws, nbytes = _workspace("field_attention_bwd", B, T, Din, H, a, int(has_res), device=x.device)
     with _Timed("field_attention_bwd"):
         _check(lib().rp_field_attention_bwd(x.data_ptr(), _rowmajor(x, "x"), W.data_ptr(), T, Din, H, a, int(has_res),
                                             scale, gout.data_ptr(), _ptr(dx), _rowmajor(dx, "dx") if want_dx else 0,
-                                            dW.data_ptr(), B, ws.data_ptr(), nbytes.value, _stream()),
+                                            dW.data_ptr(), B, ws.data_ptr(), nbytes, _stream()),
                "rp_field_attention_bwd")
     return dx, dW
 
@@ -1561,7 +1528,7 @@ def bf16_pieces(w3: torch.Tensor) -> torch.Tensor:
     padded — the operand format of the split-bf16 matrix-core kernels (round-to-nearest-even conversions, exactly
     what v_cvt_pk_bf16_f32 does in the kernels that split on the fly)."""
     O, R, Cc = w3.shape
-    pad = torch.zeros((O, 32, 32), dtype=torch.float32, device=w3.device)
+    pad = _new((O, 32, 32), torch.float32, w3.device).zero_()
     pad[:, :R, :Cc] = w3
     hi = pad.to(torch.bfloat16)
     r1 = pad - hi.float()
@@ -1572,8 +1539,8 @@ def bf16_pieces(w3: torch.Tensor) -> torch.Tensor:
 
 def cin_bs_fwd(x0, xp, wp, bias, H: int, M: int, O: int, D: int, want_out: bool, want_pool: bool):
     B = x0.shape[0]
-    out = torch.empty((B, O, D), dtype=torch.float32, device=x0.device) if want_out else None
-    pooled = torch.empty((B, O), dtype=torch.float32, device=x0.device) if want_pool else None
+    out = _new((B, O, D), torch.float32, x0.device) if want_out else None
+    pooled = _new((B, O), torch.float32, x0.device) if want_pool else None
     with _Timed("cin_bs_fwd"):
         _check(lib().rp_cin_bs_fwd(x0.data_ptr(), _rowmajor(x0, "x0"), xp.data_ptr(), _rowmajor(xp, "xp"), wp.data_ptr(),
                                    _ptr(bias), H, M, O, D, _ptr(out), _ptr(pooled), B, _stream()), "rp_cin_bs_fwd")
@@ -1594,7 +1561,7 @@ def cin_bs_bwd_x(xk, wp, g_out, g_pool, R: int, Cn: int, O: int, D: int, like, o
     """-> dx shaped like `like` ([B, >= R*D], zero beyond R*D), or written into `out` ([B, R*D] view, any leading
     dimension)."""
     B = xk.shape[0]
-    dx = out if out is not None else torch.empty_like(like)
+    dx = out if out is not None else _new_like(like)
     if out is None and like.shape[1] > R * D:
         dx[:, R * D:].zero_()
     with _Timed("cin_bs_bwd_x"):
@@ -1606,14 +1573,12 @@ def cin_bs_bwd_x(xk, wp, g_out, g_pool, R: int, Cn: int, O: int, D: int, like, o
 def cin_bs_bwd_w(x0, xp, g_out, g_pool, H: int, M: int, O: int, D: int, want_bias: bool):
     """dW [O, H*M], dbias [O] or None on the bf16 matrix core (rp_cin_bs_bwd_w); g_pool must be packed [B, O]."""
     B = x0.shape[0]
-    dW = torch.empty((O, H * M), dtype=torch.float32, device=x0.device)
-    db = torch.empty((O,), dtype=torch.float32, device=x0.device) if want_bias else None
-    nbytes = _sz(0)
-    _check(lib().rp_cin_bs_bwd_w_workspace_bytes(B, O, C.byref(nbytes)), "rp_cin_bs_bwd_w_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=x0.device)
+    dW = _new((O, H * M), torch.float32, x0.device)
+    db = _new((O,), torch.float32, x0.device) if want_bias else None
+    ws, nbytes = _workspace("cin_bs_bwd_w", B, O, device=x0.device)
     with _Timed("cin_bs_bwd_w"):
         _check(lib().rp_cin_bs_bwd_w(x0.data_ptr(), _rowmajor(x0, "x0"), xp.data_ptr(), _rowmajor(xp, "xp"), _ptr(g_out),
-                                     _ptr(g_pool), H, M, O, D, dW.data_ptr(), _ptr(db), B, ws.data_ptr(), nbytes.value,
+                                     _ptr(g_pool), H, M, O, D, dW.data_ptr(), _ptr(db), B, ws.data_ptr(), nbytes,
                                      _stream()), "rp_cin_bs_bwd_w")
     return dW, db
 
@@ -1642,10 +1607,10 @@ def cin_pair_pieces_torch(W3, transposed: bool = False):
     ws = _cin_pair_ws(W3)
     npair = ws.shape[1]
     if transposed:
-        full = torch.zeros(((npair + 127) // 128 * 128, 128), dtype=torch.float32, device=W3.device)
+        full = _new(((npair + 127) // 128 * 128, 128), torch.float32, W3.device).zero_()
         full[:npair, :O] = ws.t()
     else:
-        full = torch.zeros((128, (npair + 31) // 32 * 32), dtype=torch.float32, device=W3.device)
+        full = _new((128, (npair + 31) // 32 * 32), torch.float32, W3.device).zero_()
         full[:O, :npair] = ws
     return _bf16_split3(full)
 
@@ -1660,8 +1625,8 @@ def cin_pair_pieces(W3, transposed: bool = False, both: bool = False):
     W3 = W3.contiguous()
     npair = H * (H + 1) // 2
     dev = W3.device
-    wsp = torch.empty((3, 128, (npair + 31) // 32 * 32), dtype=torch.bfloat16, device=dev) if (both or not transposed) else None
-    wst = torch.empty((3, (npair + 127) // 128 * 128, 128), dtype=torch.bfloat16, device=dev) if (both or transposed) else None
+    wsp = _new((3, 128, (npair + 31) // 32 * 32), torch.bfloat16, dev) if (both or not transposed) else None
+    wst = _new((3, (npair + 127) // 128 * 128, 128), torch.bfloat16, dev) if (both or transposed) else None
     _check(lib().rp_cin_pair_pieces(W3.data_ptr(), O, H, _ptr(wsp), _ptr(wst), _stream()), "rp_cin_pair_pieces")
     return (wsp, wst) if both else (wst if transposed else wsp)
 
@@ -1669,8 +1634,8 @@ def cin_pair_pieces(W3, transposed: bool = False, both: bool = False):
 def cin_head_params_fwd(WL, bL, c, H: int, M: int):
     """-> (vt [M, 32], vb [1]): V^T = (c . W_L)^T zero padded and c . b_L of the collapsed last CIN layer (rp_cin_head_params_fwd)"""
     O = WL.shape[0]
-    vt = torch.empty((M, 32), dtype=torch.float32, device=WL.device)
-    vb = torch.empty((1,), dtype=torch.float32, device=WL.device)
+    vt = _new((M, 32), torch.float32, WL.device)
+    vb = _new((1,), torch.float32, WL.device)
     _check(lib().rp_cin_head_params_fwd(WL.data_ptr(), _ptr(bL), c.data_ptr(), O, H, M, vt.data_ptr(), vb.data_ptr(), _stream()),
            "rp_cin_head_params_fwd")
     return vt, vb
@@ -1680,9 +1645,9 @@ def cin_head_params_bwd(WL, bL, c, dV, sg, D: int, H: int, M: int):
     """-> (dWL [O, H M], dbL [O] or None, dc [O]) of the collapsed last layer's weights from dV [H, M] and sg = sum g
     (rp_cin_head_params_bwd)"""
     O = WL.shape[0]
-    dWL = torch.empty((O, H * M), dtype=torch.float32, device=WL.device)
-    dbL = torch.empty((O,), dtype=torch.float32, device=WL.device) if bL is not None else None
-    dc = torch.empty((O,), dtype=torch.float32, device=WL.device)
+    dWL = _new((O, H * M), torch.float32, WL.device)
+    dbL = _new((O,), torch.float32, WL.device) if bL is not None else None
+    dc = _new((O,), torch.float32, WL.device)
     _check(lib().rp_cin_head_params_bwd(WL.data_ptr(), _ptr(bL), c.data_ptr(), dV.data_ptr(), sg.data_ptr(), float(D), O, H, M,
                                         dWL.data_ptr(), _ptr(dbL), dc.data_ptr(), _stream()), "rp_cin_head_params_bwd")
     return dWL, dbL, dc
@@ -1698,7 +1663,7 @@ def add_scalars(out, a, scale: float, b0=None):
 def sum_all(x):
     """-> [1] = the sum of x's elements in a fixed order (rp_sum_all)"""
     assert x.is_contiguous() and x.dtype == torch.float32
-    out = torch.empty((1,), dtype=torch.float32, device=x.device)
+    out = _new((1,), torch.float32, x.device)
     _check(lib().rp_sum_all(x.data_ptr(), x.numel(), out.data_ptr(), _stream()), "rp_sum_all")
     return out
 
@@ -1737,7 +1702,7 @@ def cin_pair_bwd_x(x0, wst, g_out, g_pool, H: int, O: int, D: int, like, into=No
         assert into.shape[0] == B and into.shape[1] >= H * D and into.stride(1) == 1
         dx = into
     else:
-        dx = torch.empty_like(like)
+        dx = _new_like(like)
         if like.shape[1] > H * D:
             dx[:, H * D:].zero_()
     lstart, lent = cin_pair_lists(H, x0.device)
@@ -1750,8 +1715,8 @@ def cin_pair_bwd_x(x0, wst, g_out, g_pool, H: int, O: int, D: int, like, into=No
 
 def cin_pair_fwd(x0, wsp, bias, H: int, O: int, D: int, want_out: bool, want_pool: bool):
     B = x0.shape[0]
-    out = torch.empty((B, O, D), dtype=torch.float32, device=x0.device) if want_out else None
-    pooled = torch.empty((B, O), dtype=torch.float32, device=x0.device) if want_pool else None
+    out = _new((B, O, D), torch.float32, x0.device) if want_out else None
+    pooled = _new((B, O), torch.float32, x0.device) if want_pool else None
     with _Timed("cin_pair_fwd"):
         _check(lib().rp_cin_pair_fwd(x0.data_ptr(), _rowmajor(x0, "x0"), wsp.data_ptr(), _ptr(bias), H, O, D, _ptr(out),
                                      _ptr(pooled), B, _stream()), "rp_cin_pair_fwd")
@@ -1761,14 +1726,12 @@ def cin_pair_fwd(x0, wsp, bias, H: int, O: int, D: int, want_out: bool, want_poo
 def cin_pair_bwd_w(x0, g_out, g_pool, H: int, O: int, D: int, want_bias: bool):
     """first-layer dW [O, H*H], dbias [O] or None in the symmetric pair form (rp_cin_pair_bwd_w); O <= 128."""
     B = x0.shape[0]
-    dW = torch.empty((O, H * H), dtype=torch.float32, device=x0.device)
-    db = torch.empty((O,), dtype=torch.float32, device=x0.device) if want_bias else None
-    nbytes = _sz(0)
-    _check(lib().rp_cin_pair_bwd_w_workspace_bytes(B, H, O, C.byref(nbytes)), "rp_cin_pair_bwd_w_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=x0.device)
+    dW = _new((O, H * H), torch.float32, x0.device)
+    db = _new((O,), torch.float32, x0.device) if want_bias else None
+    ws, nbytes = _workspace("cin_pair_bwd_w", B, H, O, device=x0.device)
     with _Timed("cin_pair_bwd_w"):
         _check(lib().rp_cin_pair_bwd_w(x0.data_ptr(), _rowmajor(x0, "x0"), _ptr(g_out), _ptr(g_pool), H, O, D, dW.data_ptr(),
-                                       _ptr(db), B, ws.data_ptr(), nbytes.value, _stream()), "rp_cin_pair_bwd_w")
+                                       _ptr(db), B, ws.data_ptr(), nbytes, _stream()), "rp_cin_pair_bwd_w")
     return dW, db
 
 
@@ -1776,15 +1739,13 @@ def cin_layer_bwd_w(x0, xp, W, H: int, M: int, D: int, g_out, g_pool, want_bias:
     """dW like W, dbias [O] or None (rp_cin_layer_bwd_w alone)."""
     B, O = x0.shape[0], W.shape[0]
     ldgp = _rowmajor(g_pool, "g_pool") if g_pool is not None else 0
-    dW = torch.empty_like(W)
-    db = torch.empty((O,), dtype=torch.float32, device=x0.device) if want_bias else None
-    nbytes = _sz(0)
-    _check(lib().rp_cin_layer_bwd_w_workspace_bytes(B, H, M, O, C.byref(nbytes)), "rp_cin_layer_bwd_w_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=x0.device)
+    dW = _new_like(W)
+    db = _new((O,), torch.float32, x0.device) if want_bias else None
+    ws, nbytes = _workspace("cin_layer_bwd_w", B, H, M, O, device=x0.device)
     with _Timed("cin_layer_bwd_w"):
         _check(lib().rp_cin_layer_bwd_w(x0.data_ptr(), _rowmajor(x0, "x0"), xp.data_ptr(), _rowmajor(xp, "xp"),
                                         _ptr(g_out), _ptr(g_pool), ldgp, dW.data_ptr(), _ptr(db), H, M, O, D, B,
-                                        ws.data_ptr(), nbytes.value, _stream()), "rp_cin_layer_bwd_w")
+                                        ws.data_ptr(), nbytes, _stream()), "rp_cin_layer_bwd_w")
     return dW, db
 
 
@@ -1796,7 +1757,7 @@ def cin_last_fwd(x0, xp, vt, H: int, M: int, D: int):
     """x0 [B, >=H*D], xp [B, >=M*D], vt [M, 32] (V^T zero padded) -> pooled [B, 1]."""
     _req(x0, torch.float32, "x0")
     B = x0.shape[0]
-    pooled = torch.empty((B, 1), dtype=torch.float32, device=x0.device)
+    pooled = _new((B, 1), torch.float32, x0.device)
     with _Timed("cin_last_fwd"):
         _check(lib().rp_cin_last_fwd(x0.data_ptr(), _rowmajor(x0, "x0"), xp.data_ptr(), _rowmajor(xp, "xp"), vt.data_ptr(),
                                      H, M, D, pooled.data_ptr(), B, _stream()), "rp_cin_last_fwd")
@@ -1806,7 +1767,7 @@ def cin_last_fwd(x0, xp, vt, H: int, M: int, D: int):
 def cin_last_bwd(x0, xp, vt, g, H: int, M: int, D: int):
     """-> dx0 (shape of x0, zero beyond H*D), dxp (shape of xp), dV [H, M]."""
     B = x0.shape[0]
-    dx0, dxp = torch.empty_like(x0), torch.empty_like(xp)
+    dx0, dxp = _new_like(x0), _new_like(xp)
     if x0.shape[1] > H * D:
         dx0[:, H * D:].zero_()
     if xp.shape[1] > M * D:
@@ -1815,13 +1776,11 @@ def cin_last_bwd(x0, xp, vt, g, H: int, M: int, D: int):
         _check(lib().rp_cin_last_bwd_x(x0.data_ptr(), _rowmajor(x0, "x0"), xp.data_ptr(), _rowmajor(xp, "xp"),
                                        vt.data_ptr(), g.data_ptr(), H, M, D, dx0.data_ptr(), _rowmajor(dx0, "dx0"),
                                        dxp.data_ptr(), _rowmajor(dxp, "dxp"), B, _stream()), "rp_cin_last_bwd_x")
-    dV = torch.empty((H, M), dtype=torch.float32, device=x0.device)
-    nbytes = _sz(0)
-    _check(lib().rp_cin_last_bwd_v_workspace_bytes(B, H, M, C.byref(nbytes)), "rp_cin_last_bwd_v_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=x0.device)
+    dV = _new((H, M), torch.float32, x0.device)
+    ws, nbytes = _workspace("cin_last_bwd_v", B, H, M, device=x0.device)
     with _Timed("cin_last_bwd_v"):
         _check(lib().rp_cin_last_bwd_v(x0.data_ptr(), _rowmajor(x0, "x0"), xp.data_ptr(), _rowmajor(xp, "xp"), g.data_ptr(),
-                                       H, M, D, dV.data_ptr(), B, ws.data_ptr(), nbytes.value, _stream()),
+                                       H, M, D, dV.data_ptr(), B, ws.data_ptr(), nbytes, _stream()),
                "rp_cin_last_bwd_v")
     return dx0, dxp, dV
 
@@ -1835,8 +1794,8 @@ def attention_core_fwd(qkvr, nproj: int, xres, T: int, H: int, a: int, scale: fl
     _req(qkvr, torch.float32, "qkvr")
     BT = qkvr.shape[0]
     B = BT // T
-    out = torch.empty((BT, H * a), dtype=torch.float32, device=qkvr.device)
-    stats = torch.empty((B, H * T, 2), dtype=torch.float32, device=qkvr.device)
+    out = _new((BT, H * a), torch.float32, qkvr.device)
+    stats = _new((B, H * T, 2), torch.float32, qkvr.device)
     with _Timed("attention_core_fwd"):
         _check(lib().rp_attention_core_fwd(qkvr.data_ptr(), _rowmajor(qkvr, "qkvr"), nproj, _ptr(xres),
                                            _rowmajor(xres, "xres") if xres is not None else 0, T, H, a, scale,
@@ -1846,8 +1805,8 @@ def attention_core_fwd(qkvr, nproj: int, xres, T: int, H: int, a: int, scale: fl
 
 def attention_core_bwd(qkvr, nproj: int, out, dout, stats, T: int, H: int, a: int, scale: float):
     BT = qkvr.shape[0]
-    dqkvr = torch.empty_like(qkvr)
-    dxres = torch.empty((BT, H * a), dtype=torch.float32, device=qkvr.device) if nproj == 3 else None
+    dqkvr = _new_like(qkvr)
+    dxres = _new((BT, H * a), torch.float32, qkvr.device) if nproj == 3 else None
     with _Timed("attention_core_bwd"):
         _check(lib().rp_attention_core_bwd(qkvr.data_ptr(), _rowmajor(qkvr, "qkvr"), nproj, out.data_ptr(), dout.data_ptr(),
                                            stats.data_ptr(), T, H, a, scale, dqkvr.data_ptr(), _rowmajor(dqkvr, "dqkvr"),
@@ -1860,8 +1819,8 @@ def mmoe_combine_fwd(z, K: int, E: int, T: int):
     """z [B, >=K*E+T*E] -> (out [T,B,K], gate [B,T*E])."""
     _req(z, torch.float32, "z")
     B = z.shape[0]
-    out = torch.empty((T, B, K), dtype=torch.float32, device=z.device)
-    gate = torch.empty((B, T * E), dtype=torch.float32, device=z.device)
+    out = _new((T, B, K), torch.float32, z.device)
+    gate = _new((B, T * E), torch.float32, z.device)
     with _Timed("mmoe_combine_fwd"):
         _check(lib().rp_mmoe_combine_fwd(z.data_ptr(), _rowmajor(z, "z"), K, E, T, out.data_ptr(), gate.data_ptr(), B,
                                          _stream()), "rp_mmoe_combine_fwd")
@@ -1871,7 +1830,7 @@ def mmoe_combine_fwd(z, K: int, E: int, T: int):
 def mmoe_combine_bwd(z, K: int, E: int, T: int, gate, dout):
     """dout [T,B,K] -> dz [B, K*E+T*E]."""
     B = z.shape[0]
-    dz = torch.empty((B, K * E + T * E), dtype=torch.float32, device=z.device)
+    dz = _new((B, K * E + T * E), torch.float32, z.device)
     with _Timed("mmoe_combine_bwd"):
         _check(lib().rp_mmoe_combine_bwd(z.data_ptr(), _rowmajor(z, "z"), K, E, T, gate.data_ptr(), dout.data_ptr(),
                                          dz.data_ptr(), K * E + T * E, B, _stream()), "rp_mmoe_combine_bwd")
@@ -1896,8 +1855,8 @@ def fm_pool_fwd(x2d, F: int, D: int, want_sum: bool, want_bi: bool):
     """x2d [B, >=F*D] -> (sum [B,1] or None, bi [B,D] or None)."""
     _req(x2d, torch.float32, "x")
     B = x2d.shape[0]
-    out_sum = torch.empty((B, 1), dtype=torch.float32, device=x2d.device) if want_sum else None
-    out_bi = torch.empty((B, D), dtype=torch.float32, device=x2d.device) if want_bi else None
+    out_sum = _new((B, 1), torch.float32, x2d.device) if want_sum else None
+    out_bi = _new((B, D), torch.float32, x2d.device) if want_bi else None
     with _Timed("fm_pool_fwd"):
         _check(lib().rp_fm_pool_fwd(x2d.data_ptr(), _rowmajor(x2d, "x"), F, D, _ptr(out_sum), _ptr(out_bi), B,
                                     _stream()), "rp_fm_pool_fwd")
@@ -1905,7 +1864,7 @@ def fm_pool_fwd(x2d, F: int, D: int, want_sum: bool, want_bi: bool):
 
 
 def fm_pool_bwd(x2d, F: int, D: int, g_sum, g_bi):
-    dx = torch.empty_like(x2d)
+    dx = _new_like(x2d)
     if x2d.shape[1] > F * D:
         dx[:, F * D:].zero_()
     with _Timed("fm_pool_bwd"):
@@ -1914,20 +1873,14 @@ def fm_pool_bwd(x2d, F: int, D: int, g_sum, g_bi):
     return dx
 
 
-def _bn_ws(M, N, dev):
-    nbytes = _sz(0)
-    _check(lib().rp_batchnorm_workspace_bytes(M, N, C.byref(nbytes)), "rp_batchnorm_workspace_bytes")
-    return torch.empty((nbytes.value,), dtype=torch.uint8, device=dev), nbytes.value
-
-
 def batchnorm_train_fwd(x, gamma, beta, eps: float):
     """-> y, mean [N], var [N] (biased), rstd [N]"""
     _req(x, torch.float32, "x")
     M, N = x.shape
     dev = x.device
-    y = torch.empty((M, N), dtype=torch.float32, device=dev)
-    mean, var, rstd = (torch.empty((N,), dtype=torch.float32, device=dev) for _ in range(3))
-    ws, nb = _bn_ws(M, N, dev)
+    y = _new((M, N), torch.float32, dev)
+    mean, var, rstd = (_new((N,), torch.float32, dev) for _ in range(3))
+    ws, nb = _workspace("batchnorm", M, N, device=dev)
     with _Timed("batchnorm_train_fwd", f"{M}x{N}", 16 * M * N):  # 3 reads + 1 write
         _check(lib().rp_batchnorm_train_fwd(x.data_ptr(), _rowmajor(x, "x"), _ptr(gamma), _ptr(beta), eps, y.data_ptr(),
                                             N, mean.data_ptr(), var.data_ptr(), rstd.data_ptr(), M, N, ws.data_ptr(),
@@ -1938,9 +1891,9 @@ def batchnorm_train_fwd(x, gamma, beta, eps: float):
 def batchnorm_train_bwd(x, dy, mean, rstd, gamma):
     M, N = x.shape
     dev = x.device
-    dx = torch.empty((M, N), dtype=torch.float32, device=dev)
-    dgamma, dbeta = (torch.empty((N,), dtype=torch.float32, device=dev) for _ in range(2))
-    ws, nb = _bn_ws(M, N, dev)
+    dx = _new((M, N), torch.float32, dev)
+    dgamma, dbeta = (_new((N,), torch.float32, dev) for _ in range(2))
+    ws, nb = _workspace("batchnorm", M, N, device=dev)
     with _Timed("batchnorm_train_bwd", f"{M}x{N}", 20 * M * N):  # x, dy twice + dx
         _check(lib().rp_batchnorm_train_bwd(x.data_ptr(), _rowmajor(x, "x"), dy.data_ptr(), _rowmajor(dy, "dy"),
                                             mean.data_ptr(), rstd.data_ptr(), _ptr(gamma), dx.data_ptr(), N,
@@ -1951,7 +1904,7 @@ def batchnorm_train_bwd(x, dy, mean, rstd, gamma):
 
 def batchnorm_apply(x, mean, rstd, gamma, beta):
     M, N = x.shape
-    y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    y = _new((M, N), torch.float32, x.device)
     with _Timed("batchnorm_apply", f"{M}x{N}", 8 * M * N):
         _check(lib().rp_batchnorm_apply(x.data_ptr(), _rowmajor(x, "x"), mean.data_ptr(), rstd.data_ptr(), _ptr(gamma),
                                         _ptr(beta), y.data_ptr(), N, M, N, _stream()), "rp_batchnorm_apply")
@@ -1970,13 +1923,13 @@ def layernorm_fwd(x, gamma, beta, eps: float, mul=None, out=None, out_scale: flo
     if x.dim() != 2 or x.shape[1] < N or beta.numel() != N or (mul is not None and (mul.shape[0] != M or mul.shape[1] < N)):
         raise RuntimeError(f"layernorm_fwd: x {tuple(x.shape)} / mul against {N} normalised columns")
     if out is None:
-        out = torch.empty((M, N), dtype=torch.float32, device=x.device)
+        out = _new((M, N), torch.float32, x.device)
     if out.shape[0] != M or out.shape[1] < N:
         raise RuntimeError(f"layernorm_fwd: out {tuple(out.shape)} for [{M}, >= {N}]")
     if stats is None:
         if stats_given:
             raise RuntimeError("layernorm_fwd: stats_given without stats")
-        stats = torch.empty((M, 2), dtype=torch.float32, device=x.device)
+        stats = _new((M, 2), torch.float32, x.device)
     ldmul = _rowmajor(mul, "mul") if mul is not None else 0
     with _Timed("layernorm_fwd", f"{M}x{N}" + ("*mul" if mul is not None else "") + ("+=" if accumulate else ""),
                 4 * M * N * (2 + (mul is not None) + bool(accumulate))):
@@ -1997,22 +1950,19 @@ def layernorm_bwd(dy, x, stats, gamma, beta, mul=None, dy_scale: float = 1.0, dx
     if dx is None:
         if accumulate:
             raise RuntimeError("layernorm_bwd: accumulate without dx")
-        dx = torch.empty((M, x.shape[1]), dtype=torch.float32, device=dev)
-    dmul = torch.empty((M, mul.shape[1]), dtype=torch.float32, device=dev) if mul is not None else None
-    dgamma, dbeta = (torch.empty((N,), dtype=torch.float32, device=dev) for _ in range(2))
+        dx = _new((M, x.shape[1]), torch.float32, dev)
+    dmul = _new((M, mul.shape[1]), torch.float32, dev) if mul is not None else None
+    dgamma, dbeta = (_new((N,), torch.float32, dev) for _ in range(2))
     if M == 0:
         return dx, dmul, dgamma.zero_(), dbeta.zero_()
-    nbytes = _sz(0)
-    _check(lib().rp_layernorm_bwd_workspace_bytes(N, C.byref(nbytes)), "rp_layernorm_bwd_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
-    _held(ws)
+    ws, nbytes = _workspace("layernorm_bwd", N, device=dev)
     with _Timed("layernorm_bwd", f"{M}x{N}" + ("*mul" if mul is not None else "") + ("+=" if accumulate else ""),
                 4 * M * N * (3 + 2 * (mul is not None) + bool(accumulate))):
         _check(lib().rp_layernorm_bwd(dy.data_ptr(), _rowmajor(dy, "dy"), dy_scale, x.data_ptr(), _rowmajor(x, "x"),
                                       stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), _ptr(mul),
                                       _rowmajor(mul, "mul") if mul is not None else 0, dx.data_ptr(), _rowmajor(dx, "dx"),
                                       dx.shape[1], int(accumulate), _ptr(dmul), _rowmajor(dmul, "dmul") if dmul is not None else 0,
-                                      dgamma.data_ptr(), dbeta.data_ptr(), M, N, ws.data_ptr(), nbytes.value, _stream()),
+                                      dgamma.data_ptr(), dbeta.data_ptr(), M, N, ws.data_ptr(), nbytes, _stream()),
                "rp_layernorm_bwd")
     return dx, dmul, dgamma, dbeta
 
@@ -2023,7 +1973,7 @@ def dice_gate_fwd(x, xhat, alpha):
     _req(xhat, torch.float32, "xhat")
     _req(alpha, torch.float32, "alpha")
     M, N = x.shape
-    y = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    y = _new((M, N), torch.float32, x.device)
     with _Timed("dice_gate_fwd", f"{M}x{N}", 12 * M * N):
         _check(lib().rp_dice_gate_fwd(x.data_ptr(), _rowmajor(x, "x"), xhat.data_ptr(), _rowmajor(xhat, "xhat"),
                                       alpha.data_ptr(), y.data_ptr(), N, M, N, _stream()), "rp_dice_gate_fwd")
@@ -2033,7 +1983,7 @@ def dice_gate_fwd(x, xhat, alpha):
 def dice_gate_bwd(x, xhat, alpha, dy):
     """-> (dx_direct, dxhat, dal) packed [M, N] each (rp_dice_gate_bwd); dalpha = column sums of dal"""
     M, N = x.shape
-    dxd, dxh, dal = (torch.empty((M, N), dtype=torch.float32, device=x.device) for _ in range(3))
+    dxd, dxh, dal = (_new((M, N), torch.float32, x.device) for _ in range(3))
     with _Timed("dice_gate_bwd", f"{M}x{N}", 24 * M * N):
         _check(lib().rp_dice_gate_bwd(x.data_ptr(), _rowmajor(x, "x"), xhat.data_ptr(), _rowmajor(xhat, "xhat"),
                                       alpha.data_ptr(), dy.data_ptr(), _rowmajor(dy, "dy"), dxd.data_ptr(), dxh.data_ptr(),
@@ -2043,7 +1993,7 @@ def dice_gate_bwd(x, xhat, alpha, dy):
 
 def batchnorm_apply_bwd(dy, rstd, gamma):
     M, N = dy.shape
-    dx = torch.empty((M, N), dtype=torch.float32, device=dy.device)
+    dx = _new((M, N), torch.float32, dy.device)
     with _Timed("batchnorm_apply_bwd", f"{M}x{N}", 8 * M * N):
         _check(lib().rp_batchnorm_apply_bwd(dy.data_ptr(), _rowmajor(dy, "dy"), rstd.data_ptr(), _ptr(gamma),
                                             dx.data_ptr(), N, M, N, _stream()), "rp_batchnorm_apply_bwd")
@@ -2058,14 +2008,14 @@ def sigmoid_bce_fwd(addends: Sequence[torch.Tensor], label: Optional[torch.Tenso
         if z.numel() != B or not z.is_contiguous():
             raise RuntimeError("logit addends must be contiguous with B elements")
     dev = addends[0].device
-    pred = torch.empty((B, 1), dtype=torch.float32, device=dev)
+    pred = _new((B, 1), torch.float32, dev)
     loss = partial = None
     if label is not None:
         _req(label, torch.float32, "label")
         if label.numel() != B or not label.is_contiguous():
             raise RuntimeError("label must be contiguous float32 with B elements")
-        partial = torch.empty((lib().rp_loss_partials(B),), dtype=torch.float32, device=dev)
-        loss = torch.empty((), dtype=torch.float32, device=dev) if add_to is None else add_to
+        partial = _new((lib().rp_loss_partials(B),), torch.float32, dev)
+        loss = _new((), torch.float32, dev) if add_to is None else add_to
     elif add_to is not None:
         raise RuntimeError("sigmoid_bce_fwd: add_to needs a label")
     with _Timed("sigmoid_bce_fwd"):
@@ -2078,7 +2028,7 @@ def sigmoid_bce_fwd(addends: Sequence[torch.Tensor], label: Optional[torch.Tenso
 
 def sigmoid_bce_bwd(pred, label, gloss, apply_sigmoid: bool = True, p_eps: float = 0.0, weight: float = 1.0):
     B = pred.numel()
-    dz = torch.empty((B, 1), dtype=torch.float32, device=pred.device)
+    dz = _new((B, 1), torch.float32, pred.device)
     gloss = gloss.reshape(1).contiguous()
     with _Timed("sigmoid_bce_bwd"):
         _check(lib().rp_sigmoid_bce_bwd(pred.data_ptr(), label.data_ptr(), gloss.data_ptr(), B, p_eps, weight,
@@ -2135,9 +2085,8 @@ def adam_step(params, grads, ms, vs, lr, beta1, beta2, eps, step: int, zero_grad
 # ---- exact lazy dense Adam (arena rows) ---------------------------------------------------------------
 def embed_keys(row_base, row_count, idx: List[torch.Tensor], err_flag, out=None):
     F, B = len(idx), idx[0].shape[0]
-    keys = out if out is not None else torch.empty((F * B,), dtype=torch.int32, device=idx[0].device)
+    keys = out if out is not None else _new((F * B,), torch.int32, idx[0].device)
     assert keys.numel() == F * B and keys.dtype == torch.int32
-    _held(keys)
     with _Timed("embed_keys"):
         _check(lib().rp_embed_keys(row_base.data_ptr(), row_count.data_ptr(), _ptr_array(idx), F, B, keys.data_ptr(),
                                    err_flag.data_ptr(), _stream()), "rp_embed_keys")
@@ -2147,8 +2096,7 @@ def embed_keys(row_base, row_count, idx: List[torch.Tensor], err_flag, out=None)
 def shard_keys(row_base, row_count, idx: List[torch.Tensor], world: int, lbits: int, err_flag):
     """composite (owner << lbits | local row) int32 keys of a batch's row requests, p = f*B + b (rp_shard_keys)."""
     F, B = len(idx), idx[0].shape[0]
-    keys = torch.empty((F * B,), dtype=torch.int32, device=idx[0].device)
-    _held(keys)
+    keys = _new((F * B,), torch.int32, idx[0].device)
     with _Timed("shard_keys"):
         _check(lib().rp_shard_keys(row_base.data_ptr(), row_count.data_ptr(), _ptr_array(idx), F, B, world, lbits,
                                    keys.data_ptr(), err_flag.data_ptr(), _stream()), "rp_shard_keys")
@@ -2166,16 +2114,13 @@ def route_build(sorted_keys, sorted_pos, world: int, lbits: int, out=None):
         assert slot_sorted.shape == (n,) and slot_sorted.dtype == torch.int32 and slot_of_pair.shape == (n,) \
             and slot_of_pair.dtype == torch.int64
     else:
-        slot_sorted = torch.empty((n,), dtype=torch.int32, device=dev)
-        slot_of_pair = torch.empty((n,), dtype=torch.int64, device=dev)
-    uniq_rows = torch.empty((n,), dtype=torch.int64, device=dev)
-    counts = torch.empty((world + 1,), dtype=torch.int64, device=dev)
-    nbytes = _sz(0)
-    _check(lib().rp_route_workspace_bytes(n, world, C.byref(nbytes)), "rp_route_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
-    _held(slot_sorted, slot_of_pair, uniq_rows, counts, ws)
+        slot_sorted = _new((n,), torch.int32, dev)
+        slot_of_pair = _new((n,), torch.int64, dev)
+    uniq_rows = _new((n,), torch.int64, dev)
+    counts = _new((world + 1,), torch.int64, dev)
+    ws, nbytes = _workspace("route", n, world, device=dev)
     with _Timed("route_build"):
-        _check(lib().rp_route_build(ws.data_ptr(), nbytes.value, sorted_keys.data_ptr(), sorted_pos.data_ptr(), n, world,
+        _check(lib().rp_route_build(ws.data_ptr(), nbytes, sorted_keys.data_ptr(), sorted_pos.data_ptr(), n, world,
                                     lbits, slot_sorted.data_ptr(), slot_of_pair.data_ptr(), uniq_rows.data_ptr(),
                                     counts.data_ptr(), _stream()), "rp_route_build")
     return slot_sorted, slot_of_pair, uniq_rows, counts
@@ -2191,7 +2136,6 @@ def route_pad(sorted_keys, sorted_pos, world: int, lbits: int, capacity: int, co
         _check(lib().rp_fill_words(rows_padded.data_ptr(), rows_padded.numel() * 2, 0, _stream()), "rp_fill_words")
     else:
         rows_padded = zeros((world * capacity,), torch.int64, sorted_keys.device)
-    _held(rows_padded)
     with _Timed("route_pad"):
         _check(lib().rp_route_pad(sorted_keys.data_ptr(), sorted_pos.data_ptr(), sorted_keys.numel(), world, lbits, capacity,
                                   counts.data_ptr(), slot_sorted.data_ptr(), slot_of_pair.data_ptr(),
@@ -2208,10 +2152,9 @@ def route_field_major(sorted_keys, sorted_pos, slot_sorted, B: int, world: int, 
         slot_fm, pos_fm = out
         assert slot_fm.shape == (n,) and pos_fm.shape == (n,) and slot_fm.dtype == pos_fm.dtype == torch.int32
     else:
-        slot_fm = torch.empty((n,), dtype=torch.int32, device=dev)
-        pos_fm = torch.empty((n,), dtype=torch.int32, device=dev)
-    delta = torch.empty((world * (n // B),), dtype=torch.int64, device=dev)
-    _held(slot_fm, pos_fm, delta)
+        slot_fm = _new((n,), torch.int32, dev)
+        pos_fm = _new((n,), torch.int32, dev)
+    delta = _new((world * (n // B),), torch.int64, dev)
     with _Timed("route_field_major"):
         _check(lib().rp_route_field_major(sorted_keys.data_ptr(), sorted_pos.data_ptr(), slot_sorted.data_ptr(), n, B, world, lbits,
                                           slot_fm.data_ptr(), pos_fm.data_ptr(), delta.data_ptr(), _stream()),
@@ -2235,8 +2178,8 @@ def batchnorm_colsum(x, center=None):
     """column sums of x, or of (x - center)^2 (rp_batchnorm_colsum) -> [N]"""
     _req(x, torch.float32, "x")
     M, N = x.shape
-    out = torch.empty((N,), dtype=torch.float32, device=x.device)
-    ws, nb = _bn_ws(M, N, x.device)
+    out = _new((N,), torch.float32, x.device)
+    ws, nb = _workspace("batchnorm", M, N, device=x.device)
     with _Timed("batchnorm_colsum", f"{M}x{N}", 4 * M * N):
         _check(lib().rp_batchnorm_colsum(x.data_ptr(), _rowmajor(x, "x"), _ptr(center), out.data_ptr(), M, N, ws.data_ptr(),
                                          nb, _stream()), "rp_batchnorm_colsum")
@@ -2246,8 +2189,8 @@ def batchnorm_colsum(x, center=None):
 def batchnorm_bwd_sums(x, dy, mean, rstd):
     """-> (dgamma [N] = sum dy * xhat, dbeta [N] = sum dy) over the local rows (rp_batchnorm_bwd_sums)"""
     M, N = x.shape
-    dgamma, dbeta = (torch.empty((N,), dtype=torch.float32, device=x.device) for _ in range(2))
-    ws, nb = _bn_ws(M, N, x.device)
+    dgamma, dbeta = (_new((N,), torch.float32, x.device) for _ in range(2))
+    ws, nb = _workspace("batchnorm", M, N, device=x.device)
     with _Timed("batchnorm_bwd_sums", f"{M}x{N}", 8 * M * N):
         _check(lib().rp_batchnorm_bwd_sums(x.data_ptr(), _rowmajor(x, "x"), dy.data_ptr(), _rowmajor(dy, "dy"),
                                            mean.data_ptr(), rstd.data_ptr(), dgamma.data_ptr(), dbeta.data_ptr(), M, N,
@@ -2257,7 +2200,7 @@ def batchnorm_bwd_sums(x, dy, mean, rstd):
 
 def batchnorm_bwd_apply(x, dy, mean, rstd, gamma, mean_dy, mean_dyx):
     M, N = x.shape
-    dx = torch.empty((M, N), dtype=torch.float32, device=x.device)
+    dx = _new((M, N), torch.float32, x.device)
     with _Timed("batchnorm_bwd_apply", f"{M}x{N}", 12 * M * N):
         _check(lib().rp_batchnorm_bwd_apply(x.data_ptr(), _rowmajor(x, "x"), dy.data_ptr(), _rowmajor(dy, "dy"),
                                             mean.data_ptr(), rstd.data_ptr(), _ptr(gamma), mean_dy.data_ptr(),
@@ -2285,8 +2228,8 @@ def mlp_tail_fwd(hin, Ws, bs, w_out, b_out):
     """hin [M,64] -> (logit [M,1], hidden outputs [M,64] x len(Ws)) in one launch (rp_mlp_tail_fwd)."""
     _req(hin, torch.float32, "hin")
     M, L = hin.shape[0], len(Ws)
-    hs = [torch.empty((M, 64), dtype=torch.float32, device=hin.device) for _ in range(L)]
-    logit = torch.empty((M, 1), dtype=torch.float32, device=hin.device)
+    hs = [_new((M, 64), torch.float32, hin.device) for _ in range(L)]
+    logit = _new((M, 1), torch.float32, hin.device)
     with _Timed("mlp_tail_fwd", f"{M}x64x{L}", 4 * M * (64 * (L + 1) + 1), 2 * M * (64 * 64 * L + 64)):
         _check(lib().rp_mlp_tail_fwd(hin.data_ptr(), _rowmajor(hin, "hin"), L, _ptr_array(Ws), _i64_array([_rowmajor(w, "W") for w in Ws]),
                                      _opt_ptr_array(bs), _ptr_array(hs), w_out.data_ptr(), _ptr(b_out), logit.data_ptr(), M,
@@ -2302,11 +2245,11 @@ def mlp_tail_fwd_bce(hin, Ws, bs, w_out, b_out, addends, label, p_eps: float = 0
     _req(label, torch.float32, "label")
     M, L = hin.shape[0], len(Ws)
     dev = hin.device
-    hs = [torch.empty((M, 64), dtype=torch.float32, device=dev) for _ in range(L)]
-    pred = torch.empty((M, 1), dtype=torch.float32, device=dev)
+    hs = [_new((M, 64), torch.float32, dev) for _ in range(L)]
+    pred = _new((M, 1), torch.float32, dev)
     n_part = lib().rp_mlp_tail_loss_partials(M)
-    partial = torch.empty((n_part,), dtype=torch.float32, device=dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
+    partial = _new((n_part,), torch.float32, dev)
+    loss = _new((), torch.float32, dev)
     for t in addends:
         _req(t, torch.float32, "addend")
         if t.numel() != M or not t.is_contiguous():
@@ -2324,7 +2267,7 @@ def mlp_tail_fwd_bce(hin, Ws, bs, w_out, b_out, addends, label, p_eps: float = 0
         _check(lib().rp_loss_finish(partial.data_ptr(), n_part, weight / M, loss.data_ptr(), _stream()), "rp_loss_finish")
 
     if LaunchPlan.is_recording() and os.environ.get("RP_TAIL_REDUCE_SIDE", "1") != "0":
-        LaunchPlan.defer_side(finish, (partial, loss))
+        LaunchPlan.defer_side(finish)
     else:
         finish()
     return pred, loss, hs
@@ -2336,22 +2279,20 @@ def mlp_tail_bwd(dz, Ws, acts, w_out, bce=None):
     `dz` is then None and the logit's gradient is written to dz_out [M] for the other logit addends."""
     M, L = (dz.shape[0] if bce is None else bce[0].shape[0]), len(Ws)
     dev = dz.device if bce is None else bce[0].device
-    dhin = torch.empty((M, 64), dtype=torch.float32, device=dev)
-    grads = torch.empty((L * 4096 + L * 64 + 65,), dtype=torch.float32, device=dev)
-    nbytes = _sz(0)
-    _check(lib().rp_mlp_tail_bwd_workspace_bytes(M, L, C.byref(nbytes)), "rp_mlp_tail_bwd_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+    dhin = _new((M, 64), torch.float32, dev)
+    grads = _new((L * 4096 + L * 64 + 65,), torch.float32, dev)
+    ws, nbytes = _workspace("mlp_tail_bwd", M, L, device=dev)
     def launch(parts):
         if bce is not None:
             pred, label, gloss, p_eps, weight, dz_out = bce
             _check(lib().rp_mlp_tail_bwd_bce(pred.data_ptr(), label.data_ptr(), gloss.data_ptr(), p_eps, weight, _ptr(dz_out), L,
                                              _ptr_array(Ws), _i64_array([_rowmajor(w, "W") for w in Ws]), _ptr_array(acts),
                                              _rowmajor(acts[0], "hin"), w_out.data_ptr(), dhin.data_ptr(), 64, grads.data_ptr(),
-                                             M, ws.data_ptr(), nbytes.value, parts, _stream()), "rp_mlp_tail_bwd_bce")
+                                             M, ws.data_ptr(), nbytes, parts, _stream()), "rp_mlp_tail_bwd_bce")
             return
         _check(lib().rp_mlp_tail_bwd_parts(dz.data_ptr(), L, _ptr_array(Ws), _i64_array([_rowmajor(w, "W") for w in Ws]),
                                            _ptr_array(acts), _rowmajor(acts[0], "hin"), w_out.data_ptr(), dhin.data_ptr(), 64,
-                                           grads.data_ptr(), M, ws.data_ptr(), nbytes.value, parts, _stream()),
+                                           grads.data_ptr(), M, ws.data_ptr(), nbytes, parts, _stream()),
                "rp_mlp_tail_bwd")
 
     with _Timed("mlp_tail_bwd", f"{M}x64x{L}", 4 * M * (64 * (L + 2) + 1), 2 * M * (2 * 64 * 64 * L + 128)):
@@ -2359,9 +2300,9 @@ def mlp_tail_bwd(dz, Ws, acts, w_out, bce=None):
             # a captured step: the second stage (workspace -> grads, ~20 us of latency) reads nothing the following
             # launches write and nobody needs `grads` before the optimizer: it joins the plan's inline section (the second
             # side stream) behind the next launches recorded there, instead of standing between this launch and the first
-            # layer's backward.  The workspace stays referenced until that section is joined.
+            # layer's backward.  The plan keeps the closure, and with it the workspace, until that section is joined.
             launch(1)
-            LaunchPlan.defer_side(lambda: launch(2), (ws, grads))
+            LaunchPlan.defer_side(lambda: launch(2))
         else:
             launch(3)
     dWs = [grads[l * 4096:(l + 1) * 4096].view(64, 64) for l in range(L)]
@@ -2407,8 +2348,8 @@ def dropout_fwd(x, p: float, seed: Optional[int] = None, offset: Optional[int] =
     clock = None
     if seed is None:
         seed, offset, clock = _dropout_seed_offset(x.device)
-    y = torch.empty((M, N), dtype=torch.float32, device=x.device)
-    mask = torch.empty((M, N), dtype=torch.uint8, device=x.device)
+    y = _new((M, N), torch.float32, x.device)
+    mask = _new((M, N), torch.uint8, x.device)
     with _Timed("dropout_fwd", f"{M}x{N}", 9 * M * N):
         if clock is not None:
             _check(lib().rp_dropout_fwd_dev(x.data_ptr(), _rowmajor(x, "x"), y.data_ptr(), N, mask.data_ptr(), M, N, p, seed,
@@ -2431,7 +2372,7 @@ def device_generator(device):
 
 def dropout_bwd(dy, mask, p: float):
     M, N = dy.shape
-    dx = torch.empty((M, N), dtype=torch.float32, device=dy.device)
+    dx = _new((M, N), torch.float32, dy.device)
     with _Timed("dropout_bwd", f"{M}x{N}", 9 * M * N):
         _check(lib().rp_dropout_bwd(dy.data_ptr(), _rowmajor(dy, "dy"), mask.data_ptr(), dx.data_ptr(), N, M, N, p, _stream()),
                "rp_dropout_bwd")
@@ -2523,9 +2464,9 @@ def embed_gather_pool_fwd(arena, row_base: int, row_count: int, ids, offsets, L:
     offsets None; CSR: offsets int64 [B + 1]).  Returns (out [B, D], inv [B, D] or None, bag_of int32 [nnz] or None)."""
     _req(arena, torch.float32, "arena")
     D = arena.shape[1]
-    out = torch.empty((B, D), dtype=torch.float32, device=arena.device)
-    inv = torch.empty((B, D), dtype=torch.float32, device=arena.device) if (want_bwd and mode == "average") else None
-    bag = torch.empty((ids.numel(),), dtype=torch.int32, device=arena.device) if (want_bwd and offsets is not None) else None
+    out = _new((B, D), torch.float32, arena.device)
+    inv = _new((B, D), torch.float32, arena.device) if (want_bwd and mode == "average") else None
+    bag = _new((ids.numel(),), torch.int32, arena.device) if (want_bwd and offsets is not None) else None
     nnz = ids.numel()
     with _Timed("embed_gather_pool_fwd", f"D={D}", nnz * (D * 4 + 8) + B * D * 4):
         _check(lib().rp_embed_gather_pool_fwd(arena.data_ptr(), row_base, row_count, ids.data_ptr(), _ptr(offsets), L, B, D,
@@ -2538,21 +2479,19 @@ def embed_pool_bwd(sorted_keys, sorted_pos, D: int, g, scale, bag_of, L: int, gr
     _req(grad_arena, torch.float32, "grad_arena")
     _req(g, torch.float32, "g")
     n = sorted_keys.numel()
-    nbytes = _sz(0)
-    _check(lib().rp_embed_grad_reduce_workspace_bytes(n, D, C.byref(nbytes)), "rp_embed_grad_reduce_workspace_bytes")
-    ws = torch.empty((nbytes.value,), dtype=torch.uint8, device=grad_arena.device)
+    ws, nbytes = _workspace("embed_grad_reduce", n, D, device=grad_arena.device)
     with _Timed("embed_pool_bwd", f"D={D}", n * (D * 4 + 8)):
         _check(lib().rp_embed_pool_bwd(sorted_keys.data_ptr(), sorted_pos.data_ptr(), n, D, g.data_ptr(), _rowmajor(g, "g"),
                                        _ptr(scale), _ptr(bag_of), L, grad_arena.data_ptr(), int(accumulate), ws.data_ptr(),
-                                       nbytes.value, _stream()), "rp_embed_pool_bwd")
+                                       nbytes, _stream()), "rp_embed_pool_bwd")
 
 
 def seq_pool_fwd(e, mode: str, want_bwd: bool):
     """MaskedSumPooling / MaskedAveragePooling of an explicit contiguous [B, L, D] tensor -> (out [B, D], inv or None)"""
     _req(e, torch.float32, "e")
     B, L, D = e.shape
-    out = torch.empty((B, D), dtype=torch.float32, device=e.device)
-    inv = torch.empty((B, D), dtype=torch.float32, device=e.device) if (want_bwd and mode == "average") else None
+    out = _new((B, D), torch.float32, e.device)
+    inv = _new((B, D), torch.float32, e.device) if (want_bwd and mode == "average") else None
     with _Timed("seq_pool_fwd", f"{B}x{L}x{D}", (B * L * D + B * D) * 4):
         _check(lib().rp_seq_pool_fwd(e.data_ptr(), B, L, D, POOL_MODES[mode], out.data_ptr(), _ptr(inv), _stream()),
                "rp_seq_pool_fwd")
@@ -2562,7 +2501,7 @@ def seq_pool_fwd(e, mode: str, want_bwd: bool):
 def seq_pool_bwd(g, inv, L: int):
     _req(g, torch.float32, "g")
     B, D = g.shape
-    de = torch.empty((B, L, D), dtype=torch.float32, device=g.device)
+    de = _new((B, L, D), torch.float32, g.device)
     with _Timed("seq_pool_bwd", f"{B}x{L}x{D}", (B * L * D + B * D) * 4):
         _check(lib().rp_seq_pool_bwd(g.data_ptr(), _ptr(inv), B, L, D, de.data_ptr(), _stream()), "rp_seq_pool_bwd")
     return de

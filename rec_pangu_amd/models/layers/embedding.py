@@ -491,14 +491,13 @@ class EmbeddingLayer(nn.Module):
                            accumulate=not self._grad_clean)
         self._grad_end(look.sk, fresh)
 
-    def first_layer_grad(self, keys, B: int, dh, wt, gfm, ssum, presorted=None, dx=None, w=None, dw=None, keep=None):
+    def first_layer_grad(self, keys, B: int, dh, wt, gfm, ssum, presorted=None, dx=None, w=None, dw=None):
         """The backward of the lookup fused with the Linear that consumes x — its dgrad is formed inside the reduce from
         (dh, wt = W^T) — as NAMED LAUNCHES: this call only opens the pass (gradient arena, sort, the tables' forms); the autograd
         node issues `tiny`, `big`, `rest` or `gemm` in the order and on the plan section it wants and then `done`
         (functional._EmbedGatherLinear.backward: the one place that order is written down).
         w, dw ([64, K] each, both or neither): segment sums first, one matrix pass per run that also yields the embedding columns
-        of the weight gradient dw — the forward stored no activation.  keep: the list that holds the workspaces of launches
-        other launches run beside (a recording plan), or None.  -> .forms (GradForms) and the launches:
+        of the weight gradient dw — the forward stored no activation.  -> .forms (GradForms) and the launches:
           tiny    the tables of a few rows (Criteo: 8 fields, 31 % of the pairs): the sample-major one-hot path
           big(1)  round 6: the BIG tables (runs of the sorted list are mostly single pairs: the sort buys nothing and the
                   (field, row) order re-gathers every dH / S row once per field) go through the batch in sample order instead
@@ -522,20 +521,19 @@ class EmbeddingLayer(nn.Module):
         to = (gfm, ssum, self._arena, self._grad_arena)
 
         def tiny():
-            hip.embed_grad_tiny(keys, B, forms.tiny, dh, wt, *to, accumulate=acc, keep=keep, dw=dw)
+            hip.embed_grad_tiny(keys, B, forms.tiny, dh, wt, *to, accumulate=acc, dw=dw)
 
         def big(phase, ws=None):
             if phase == 1:
                 self._marks_wanted = True
                 if look.smp_sig != (B, tuple(forms.big)):
                     self._mark_sorted(look, force=True)  # (a sort nobody marked: an eager backward that sorted for itself)
-            return hip.embed_grad_smp(keys, look.smp, B, F, forms.big, dh, w, *to, accumulate=acc, dw=dw,
-                                      keep=keep if phase == 1 else None, phases=phase, ws=ws)
+            return hip.embed_grad_smp(keys, look.smp, B, F, forms.big, dh, w, *to, accumulate=acc, dw=dw, phases=phase, ws=ws)
 
         def rest():
             launch, marks = (hip.embed_grad_ss, {"marks": look.ss_lists(forms.skip)}) if forms.ss else (hip.embed_grad_seg, {})
             launch(look.sk, look.sp, B, D, dh, w, *to, accumulate=acc, skip_fields=forms.skip, field_rows=self._rows_sig(),
-                   dw=dw, keep=keep, **marks)
+                   dw=dw, **marks)
 
         def gemm():
             hip.embed_grad_gemm(look.sk, look.sp, B, D, dh, wt, dx, *to, accumulate=acc, skip_fields=forms.skip)

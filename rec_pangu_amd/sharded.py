@@ -215,8 +215,7 @@ class _Route:
             err = layer._err_flag(idx[0].device)
             comp = hip.shard_keys(layer._row_base, layer._row_count, idx, world, lbits, err)
             if pin is not None:
-                sk, sp = hip.sort_pairs(comp, end_bit=nbits, out=(torch.empty_like(comp), pin.pos_sorted))
-                hip._held(sk)
+                sk, sp = hip.sort_pairs(comp, end_bit=nbits, out=(None, pin.pos_sorted))
             else:
                 sk, sp = hip.sort_pairs(comp, end_bit=nbits)  # stable radix sort (csrc/sort.hip), (key, position) pairs
             self.slot_sorted, self.slot_of_pair, uniq_rows, counts = hip.route_build(

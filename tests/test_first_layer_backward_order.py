@@ -6,7 +6,9 @@ EmbeddingLayer with D = 64 and the sort is a hand-made SortedLookup.  (functiona
 second-torch-stream variant of the eager loop is the one thing not seen here.)
 
 The literals in EXPECTED were recorded with this very recorder on the code as it stood BEFORE the backward was gathered
-into one function; they are the specification, not a description of the present code."""
+into one function; they are the specification, not a description of the present code.  `held=1 / 0` (whether the launch
+ran inside a hip.holding() block, which keeps what it allocates until the block ends) stands where that recording had
+`keep=plan / None`; it is 1 for EVERY launch between the point a recording backward opens its block and the plan's join."""
 from types import SimpleNamespace
 
 import pytest
@@ -39,7 +41,7 @@ class Recorder:
     """stands in for the hip entry points and the LaunchPlan calls of the path; `log` is the issue order"""
 
     def __init__(self, monkeypatch, recording: bool, fail_in: str = None, smp_fits: bool = True):
-        self.log, self.dw_ptrs, self.keeps, self.fail_in = [], set(), [], fail_in
+        self.log, self.dw_ptrs, self.scopes, self.fail_in = [], set(), [], fail_in
         self.ss_marked, self.ss_made, self.ss_given = [], [], []
         for name in ("relu_bwd", "linear_wgrad", "linear_wgrad_xbf16", "transpose", "embed_grad_tiny", "embed_grad_smp",
                      "embed_grad_smp_mark", "embed_grad_ss_mark", "embed_grad_ss", "embed_grad_seg", "embed_grad_gemm"):
@@ -51,14 +53,13 @@ class Recorder:
         monkeypatch.setattr(hip.LaunchPlan, "is_recording", staticmethod(lambda: recording))
         monkeypatch.setattr(Fh, "_wgrad_stream", lambda device: None)
 
-    def _launch(self, name, accumulate=None, keep="absent", dw="absent", **what):
+    def _launch(self, name, accumulate=None, dw="absent", **what):
         parts = [name] + [f"{k}={v}" for k, v in what.items()]
         if accumulate is not None:
             parts.append(f"acc={int(accumulate)}")
-        if keep != "absent":
-            parts.append("keep=" + ("None" if keep is None else "plan"))
-            if keep is not None:
-                self.keeps.append(keep)
+        parts.append(f"held={int(hip.holding.active())}")  # inside a hip.holding() block: what the launch allocates stays
+        if hip.holding.active():
+            self.scopes.append(hip._HOLDING)
         if dw != "absent":
             parts.append("dw=" + ("None" if dw is None else "shared"))
             if dw is not None:
@@ -75,25 +76,25 @@ class Recorder:
         self._launch("transpose")
         return torch.zeros((rows_out or w.shape[1], w.shape[0]))
 
-    def linear_wgrad(self, dy, x, K, dw=None, db=None, accumulate=False, want_bias=True, keep=None):
-        self._launch("linear_wgrad", cols=K, out="new" if dw is None else "view", keep=keep)
+    def linear_wgrad(self, dy, x, K, dw=None, db=None, accumulate=False, want_bias=True):
+        self._launch("linear_wgrad", cols=K, out="new" if dw is None else "view")
         return (dw if dw is not None else torch.zeros((dy.shape[1], K))), (torch.zeros(dy.shape[1]) if want_bias else None)
 
-    def linear_wgrad_xbf16(self, dy, x16, K, want_bias=True, keep=None):
-        self._launch("linear_wgrad_xbf16", cols=K, keep=keep)
+    def linear_wgrad_xbf16(self, dy, x16, K, want_bias=True):
+        self._launch("linear_wgrad_xbf16", cols=K)
         return torch.zeros((dy.shape[1], K)), (torch.zeros(dy.shape[1]) if want_bias else None)
 
-    def embed_grad_tiny(self, keys, B, tiny, dh, wt, gfm, sum_in, arena, grad_arena, accumulate, keep=None, dw=None):
-        self._launch("embed_grad_tiny", fields=_mask(t[0] for t in tiny), accumulate=accumulate, keep=keep, dw=dw)
+    def embed_grad_tiny(self, keys, B, tiny, dh, wt, gfm, sum_in, arena, grad_arena, accumulate, dw=None):
+        self._launch("embed_grad_tiny", fields=_mask(t[0] for t in tiny), accumulate=accumulate, dw=dw)
 
     def embed_grad_smp_mark(self, sorted_keys, sorted_pos, B, fields, out=None):
         self._launch("embed_grad_smp_mark", fields=_mask(fields))
         return out if out is not None else tuple(torch.zeros(1, dtype=torch.int32) for _ in range(3))
 
-    def embed_grad_smp(self, keys, marks, B, F, fields, dh, w, gfm, sum_in, arena, grad_arena, accumulate, dw=None,
-                       keep=None, phases=3, ws=None):
+    def embed_grad_smp(self, keys, marks, B, F, fields, dh, w, gfm, sum_in, arena, grad_arena, accumulate, dw=None, phases=3,
+                       ws=None):
         assert marks is not None and (phases == 1 or ws == "smp workspace")
-        self._launch(f"embed_grad_smp[{phases}]", fields=_mask(t[0] for t in fields), accumulate=accumulate, keep=keep, dw=dw)
+        self._launch(f"embed_grad_smp[{phases}]", fields=_mask(t[0] for t in fields), accumulate=accumulate, dw=dw)
         return "smp workspace" if phases == 1 else None
 
     def embed_grad_ss_mark(self, sorted_keys, B, skip_fields, out=None):
@@ -103,14 +104,14 @@ class Recorder:
         return self.ss_made[-1]
 
     def embed_grad_ss(self, sorted_keys, sorted_pos, B, D, dh, w, gfm, sum_in, arena, grad_arena, accumulate,
-                      skip_fields=0, field_rows=None, dw=None, keep=None, phases=3, ws=None, marks=None):
+                      skip_fields=0, field_rows=None, dw=None, phases=3, ws=None, marks=None):
         self.ss_given.append((skip_fields, marks))
         self._launch("embed_grad_ss", skip=_bits(skip_fields), marks="None" if marks is None else "sort",
-                     accumulate=accumulate, keep=keep, dw=dw)
+                     accumulate=accumulate, dw=dw)
 
     def embed_grad_seg(self, sorted_keys, sorted_pos, B, D, dh, w, gfm, sum_in, arena, grad_arena, accumulate,
-                       skip_fields=0, field_rows=None, dw=None, keep=None):
-        self._launch("embed_grad_seg", skip=_bits(skip_fields), accumulate=accumulate, keep=keep, dw=dw)
+                       skip_fields=0, field_rows=None, dw=None):
+        self._launch("embed_grad_seg", skip=_bits(skip_fields), accumulate=accumulate, dw=dw)
 
     def embed_grad_gemm(self, sorted_keys, sorted_pos, B, D, dh, wt, dx, gfm, sum_in, arena, grad_arena, accumulate,
                         skip_fields=0):
@@ -162,294 +163,295 @@ def _run(monkeypatch, tables: str, recording: bool, x_mode: str, premarked: bool
         del rec.log[:]
     dw = _backward(layer, look, x_mode)
     assert rec.dw_ptrs <= {dw.data_ptr()}          # every `dw=shared` above is the buffer the node returns
-    assert all(k is rec.keeps[0] for k in rec.keeps)  # every `keep=plan` is one list
+    assert all(sc is rec.scopes[0] for sc in rec.scopes)  # every `held=1` launch of this backward saw the same scope list
+    assert not hip.holding.active()
     return rec
 
 
 # recorded on the parent of the change that gathered this backward into one function (see the module docstring)
 EXPECTED = {
     ('tiny+big+mid', True, 'seg'): [
-        'relu_bwd',
-        'transpose',
+        'relu_bwd held=0',
+        'transpose held=1',
         'fork2_mark',
-        'embed_grad_smp_mark fields=0,5',
-        'embed_grad_ss_mark skip=0,1,3,4,5',
-        'embed_grad_smp[1] fields=0,5 acc=0 keep=plan dw=shared',
+        'embed_grad_smp_mark fields=0,5 held=1',
+        'embed_grad_ss_mark skip=0,1,3,4,5 held=1',
+        'embed_grad_smp[1] fields=0,5 acc=0 held=1 dw=shared',
         'section(2)',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=plan dw=shared',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=1 dw=shared',
         'section(0)',
         'side2_sync',
-        'embed_grad_ss skip=0,1,3,4,5 marks=sort acc=0 keep=plan dw=shared',
+        'embed_grad_ss skip=0,1,3,4,5 marks=sort acc=0 held=1 dw=shared',
         'section(2)',
-        'embed_grad_smp[2] fields=0,5 acc=0 keep=None dw=shared',
+        'embed_grad_smp[2] fields=0,5 acc=0 held=1 dw=shared',
         'section(0)',
         'section(2)',
-        'linear_wgrad cols=13 out=view keep=plan',
+        'linear_wgrad cols=13 out=view held=1',
         'run_deferred',
         'section(0)',
         'join',
     ],
     ('tiny+big+mid', True, 'full'): [
-        'relu_bwd',
+        'relu_bwd held=0',
         'section(2)',
-        'linear_wgrad cols=397 out=new keep=plan',
+        'linear_wgrad cols=397 out=new held=1',
         'run_deferred',
         'section(0)',
-        'transpose',
+        'transpose held=1',
         'section(2)',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=plan dw=None',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=1 dw=None',
         'section(0)',
-        'embed_grad_gemm skip=1,3,4 acc=0',
+        'embed_grad_gemm skip=1,3,4 acc=0 held=1',
         'join',
     ],
     ('tiny+big+mid', False, 'seg'): [
-        'relu_bwd',
-        'linear_wgrad cols=13 out=view keep=None',
-        'transpose',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=None dw=shared',
-        'embed_grad_smp_mark fields=0,5',
-        'embed_grad_ss_mark skip=0,1,3,4,5',
-        'embed_grad_smp[1] fields=0,5 acc=0 keep=None dw=shared',
-        'embed_grad_ss skip=0,1,3,4,5 marks=sort acc=0 keep=None dw=shared',
-        'embed_grad_smp[2] fields=0,5 acc=0 keep=None dw=shared',
+        'relu_bwd held=0',
+        'linear_wgrad cols=13 out=view held=0',
+        'transpose held=0',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=0 dw=shared',
+        'embed_grad_smp_mark fields=0,5 held=0',
+        'embed_grad_ss_mark skip=0,1,3,4,5 held=0',
+        'embed_grad_smp[1] fields=0,5 acc=0 held=0 dw=shared',
+        'embed_grad_ss skip=0,1,3,4,5 marks=sort acc=0 held=0 dw=shared',
+        'embed_grad_smp[2] fields=0,5 acc=0 held=0 dw=shared',
     ],
     ('tiny+big+mid', False, 'full'): [
-        'relu_bwd',
-        'linear_wgrad cols=397 out=new keep=None',
-        'transpose',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=None dw=None',
-        'embed_grad_gemm skip=1,3,4 acc=0',
+        'relu_bwd held=0',
+        'linear_wgrad cols=397 out=new held=0',
+        'transpose held=0',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=0 dw=None',
+        'embed_grad_gemm skip=1,3,4 acc=0 held=0',
     ],
     ('tiny+mid', True, 'seg'): [
-        'relu_bwd',
-        'transpose',
+        'relu_bwd held=0',
+        'transpose held=1',
         'fork2_mark',
-        'embed_grad_seg skip=1,3,4 acc=0 keep=plan dw=shared',
+        'embed_grad_seg skip=1,3,4 acc=0 held=1 dw=shared',
         'section(2)',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=plan dw=shared',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=1 dw=shared',
         'section(0)',
         'section(2)',
-        'linear_wgrad cols=13 out=view keep=plan',
+        'linear_wgrad cols=13 out=view held=1',
         'run_deferred',
         'section(0)',
         'join',
     ],
     ('tiny+mid', True, 'full'): [
-        'relu_bwd',
+        'relu_bwd held=0',
         'section(2)',
-        'linear_wgrad cols=397 out=new keep=plan',
+        'linear_wgrad cols=397 out=new held=1',
         'run_deferred',
         'section(0)',
-        'transpose',
+        'transpose held=1',
         'section(2)',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=plan dw=None',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=1 dw=None',
         'section(0)',
-        'embed_grad_gemm skip=1,3,4 acc=0',
+        'embed_grad_gemm skip=1,3,4 acc=0 held=1',
         'join',
     ],
     ('tiny+mid', False, 'seg'): [
-        'relu_bwd',
-        'linear_wgrad cols=13 out=view keep=None',
-        'transpose',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=None dw=shared',
-        'embed_grad_seg skip=1,3,4 acc=0 keep=None dw=shared',
+        'relu_bwd held=0',
+        'linear_wgrad cols=13 out=view held=0',
+        'transpose held=0',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=0 dw=shared',
+        'embed_grad_seg skip=1,3,4 acc=0 held=0 dw=shared',
     ],
     ('tiny+mid', False, 'full'): [
-        'relu_bwd',
-        'linear_wgrad cols=397 out=new keep=None',
-        'transpose',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=None dw=None',
-        'embed_grad_gemm skip=1,3,4 acc=0',
+        'relu_bwd held=0',
+        'linear_wgrad cols=397 out=new held=0',
+        'transpose held=0',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=0 dw=None',
+        'embed_grad_gemm skip=1,3,4 acc=0 held=0',
     ],
     ('big+mid', True, 'seg'): [
-        'relu_bwd',
-        'transpose',
-        'embed_grad_smp_mark fields=0,3',
-        'embed_grad_ss_mark skip=0,3',
-        'embed_grad_smp[1] fields=0,3 acc=0 keep=plan dw=shared',
+        'relu_bwd held=0',
+        'transpose held=1',
+        'embed_grad_smp_mark fields=0,3 held=1',
+        'embed_grad_ss_mark skip=0,3 held=1',
+        'embed_grad_smp[1] fields=0,3 acc=0 held=1 dw=shared',
         'fork2_mark',
-        'embed_grad_ss skip=0,3 marks=sort acc=0 keep=plan dw=shared',
+        'embed_grad_ss skip=0,3 marks=sort acc=0 held=1 dw=shared',
         'section(2)',
-        'embed_grad_smp[2] fields=0,3 acc=0 keep=None dw=shared',
+        'embed_grad_smp[2] fields=0,3 acc=0 held=1 dw=shared',
         'section(0)',
         'section(2)',
-        'linear_wgrad cols=13 out=view keep=plan',
+        'linear_wgrad cols=13 out=view held=1',
         'run_deferred',
         'section(0)',
         'join',
     ],
     ('big+mid', True, 'full'): [
-        'relu_bwd',
+        'relu_bwd held=0',
         'section(2)',
-        'linear_wgrad cols=269 out=new keep=plan',
+        'linear_wgrad cols=269 out=new held=1',
         'run_deferred',
         'section(0)',
-        'transpose',
-        'embed_grad_gemm skip=- acc=0',
+        'transpose held=1',
+        'embed_grad_gemm skip=- acc=0 held=1',
         'join',
     ],
     ('big+mid', False, 'seg'): [
-        'relu_bwd',
-        'linear_wgrad cols=13 out=view keep=None',
-        'transpose',
-        'embed_grad_smp_mark fields=0,3',
-        'embed_grad_ss_mark skip=0,3',
-        'embed_grad_smp[1] fields=0,3 acc=0 keep=None dw=shared',
-        'embed_grad_ss skip=0,3 marks=sort acc=0 keep=None dw=shared',
-        'embed_grad_smp[2] fields=0,3 acc=0 keep=None dw=shared',
+        'relu_bwd held=0',
+        'linear_wgrad cols=13 out=view held=0',
+        'transpose held=0',
+        'embed_grad_smp_mark fields=0,3 held=0',
+        'embed_grad_ss_mark skip=0,3 held=0',
+        'embed_grad_smp[1] fields=0,3 acc=0 held=0 dw=shared',
+        'embed_grad_ss skip=0,3 marks=sort acc=0 held=0 dw=shared',
+        'embed_grad_smp[2] fields=0,3 acc=0 held=0 dw=shared',
     ],
     ('big+mid', False, 'full'): [
-        'relu_bwd',
-        'linear_wgrad cols=269 out=new keep=None',
-        'transpose',
-        'embed_grad_gemm skip=- acc=0',
+        'relu_bwd held=0',
+        'linear_wgrad cols=269 out=new held=0',
+        'transpose held=0',
+        'embed_grad_gemm skip=- acc=0 held=0',
     ],
     ('tiny+big', True, 'seg'): [
-        'relu_bwd',
-        'transpose',
+        'relu_bwd held=0',
+        'transpose held=1',
         'fork2_mark',
-        'embed_grad_smp_mark fields=0,4',
-        'embed_grad_smp[1] fields=0,4 acc=0 keep=plan dw=shared',
+        'embed_grad_smp_mark fields=0,4 held=1',
+        'embed_grad_smp[1] fields=0,4 acc=0 held=1 dw=shared',
         'section(2)',
-        'embed_grad_tiny fields=1,2,3 acc=0 keep=plan dw=shared',
+        'embed_grad_tiny fields=1,2,3 acc=0 held=1 dw=shared',
         'section(0)',
         'side2_sync',
         'section(2)',
-        'embed_grad_smp[2] fields=0,4 acc=0 keep=None dw=shared',
+        'embed_grad_smp[2] fields=0,4 acc=0 held=1 dw=shared',
         'section(0)',
         'section(2)',
-        'linear_wgrad cols=13 out=view keep=plan',
+        'linear_wgrad cols=13 out=view held=1',
         'run_deferred',
         'section(0)',
         'join',
     ],
     ('tiny+big', True, 'full'): [
-        'relu_bwd',
+        'relu_bwd held=0',
         'section(2)',
-        'linear_wgrad cols=333 out=new keep=plan',
+        'linear_wgrad cols=333 out=new held=1',
         'run_deferred',
         'section(0)',
-        'transpose',
+        'transpose held=1',
         'section(2)',
-        'embed_grad_tiny fields=1,2,3 acc=0 keep=plan dw=None',
+        'embed_grad_tiny fields=1,2,3 acc=0 held=1 dw=None',
         'section(0)',
-        'embed_grad_gemm skip=1,2,3 acc=0',
+        'embed_grad_gemm skip=1,2,3 acc=0 held=1',
         'join',
     ],
     ('tiny+big', False, 'seg'): [
-        'relu_bwd',
-        'linear_wgrad cols=13 out=view keep=None',
-        'transpose',
-        'embed_grad_tiny fields=1,2,3 acc=0 keep=None dw=shared',
-        'embed_grad_smp_mark fields=0,4',
-        'embed_grad_smp[1] fields=0,4 acc=0 keep=None dw=shared',
-        'embed_grad_smp[2] fields=0,4 acc=0 keep=None dw=shared',
+        'relu_bwd held=0',
+        'linear_wgrad cols=13 out=view held=0',
+        'transpose held=0',
+        'embed_grad_tiny fields=1,2,3 acc=0 held=0 dw=shared',
+        'embed_grad_smp_mark fields=0,4 held=0',
+        'embed_grad_smp[1] fields=0,4 acc=0 held=0 dw=shared',
+        'embed_grad_smp[2] fields=0,4 acc=0 held=0 dw=shared',
     ],
     ('tiny+big', False, 'full'): [
-        'relu_bwd',
-        'linear_wgrad cols=333 out=new keep=None',
-        'transpose',
-        'embed_grad_tiny fields=1,2,3 acc=0 keep=None dw=None',
-        'embed_grad_gemm skip=1,2,3 acc=0',
+        'relu_bwd held=0',
+        'linear_wgrad cols=333 out=new held=0',
+        'transpose held=0',
+        'embed_grad_tiny fields=1,2,3 acc=0 held=0 dw=None',
+        'embed_grad_gemm skip=1,2,3 acc=0 held=0',
     ],
     ('tiny+big+mid', True, 'seg', 'RP_SS_MARK_AHEAD=0'): [
-        'relu_bwd',
-        'transpose',
+        'relu_bwd held=0',
+        'transpose held=1',
         'fork2_mark',
-        'embed_grad_smp_mark fields=0,5',
-        'embed_grad_smp[1] fields=0,5 acc=0 keep=plan dw=shared',
+        'embed_grad_smp_mark fields=0,5 held=1',
+        'embed_grad_smp[1] fields=0,5 acc=0 held=1 dw=shared',
         'section(2)',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=plan dw=shared',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=1 dw=shared',
         'section(0)',
         'side2_sync',
-        'embed_grad_ss skip=0,1,3,4,5 marks=None acc=0 keep=plan dw=shared',
+        'embed_grad_ss skip=0,1,3,4,5 marks=None acc=0 held=1 dw=shared',
         'section(2)',
-        'embed_grad_smp[2] fields=0,5 acc=0 keep=None dw=shared',
+        'embed_grad_smp[2] fields=0,5 acc=0 held=1 dw=shared',
         'section(0)',
         'section(2)',
-        'linear_wgrad cols=13 out=view keep=plan',
+        'linear_wgrad cols=13 out=view held=1',
         'run_deferred',
         'section(0)',
         'join',
     ],
     ('tiny+big+mid', True, 'seg', 'premarked'): [
-        'relu_bwd',
-        'transpose',
+        'relu_bwd held=0',
+        'transpose held=1',
         'fork2_mark',
-        'embed_grad_smp[1] fields=0,5 acc=0 keep=plan dw=shared',
+        'embed_grad_smp[1] fields=0,5 acc=0 held=1 dw=shared',
         'section(2)',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=plan dw=shared',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=1 dw=shared',
         'section(0)',
         'side2_sync',
-        'embed_grad_ss skip=0,1,3,4,5 marks=sort acc=0 keep=plan dw=shared',
+        'embed_grad_ss skip=0,1,3,4,5 marks=sort acc=0 held=1 dw=shared',
         'section(2)',
-        'embed_grad_smp[2] fields=0,5 acc=0 keep=None dw=shared',
+        'embed_grad_smp[2] fields=0,5 acc=0 held=1 dw=shared',
         'section(0)',
         'section(2)',
-        'linear_wgrad cols=13 out=view keep=plan',
+        'linear_wgrad cols=13 out=view held=1',
         'run_deferred',
         'section(0)',
         'join',
     ],
     ('tiny+big+mid', True, 'bf16'): [
-        'relu_bwd',
+        'relu_bwd held=0',
         'section(2)',
-        'linear_wgrad_xbf16 cols=397 keep=plan',
+        'linear_wgrad_xbf16 cols=397 held=1',
         'run_deferred',
         'section(0)',
-        'transpose',
+        'transpose held=1',
         'section(2)',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=plan dw=None',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=1 dw=None',
         'section(0)',
-        'embed_grad_gemm skip=1,3,4 acc=0',
+        'embed_grad_gemm skip=1,3,4 acc=0 held=1',
         'join',
     ],
     ('tiny+big+mid', True, 'seg', 'smp does not fit'): [
-        'relu_bwd',
-        'transpose',
+        'relu_bwd held=0',
+        'transpose held=1',
         'fork2_mark',
-        'embed_grad_seg skip=1,3,4 acc=0 keep=plan dw=shared',
+        'embed_grad_seg skip=1,3,4 acc=0 held=1 dw=shared',
         'section(2)',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=plan dw=shared',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=1 dw=shared',
         'section(0)',
         'section(2)',
-        'linear_wgrad cols=13 out=view keep=plan',
+        'linear_wgrad cols=13 out=view held=1',
         'run_deferred',
         'section(0)',
         'join',
     ],
     ('tiny+big+mid', False, 'seg', 'RP_SS_MARK_AHEAD=0'): [
-        'relu_bwd',
-        'linear_wgrad cols=13 out=view keep=None',
-        'transpose',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=None dw=shared',
-        'embed_grad_smp_mark fields=0,5',
-        'embed_grad_smp[1] fields=0,5 acc=0 keep=None dw=shared',
-        'embed_grad_ss skip=0,1,3,4,5 marks=None acc=0 keep=None dw=shared',
-        'embed_grad_smp[2] fields=0,5 acc=0 keep=None dw=shared',
+        'relu_bwd held=0',
+        'linear_wgrad cols=13 out=view held=0',
+        'transpose held=0',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=0 dw=shared',
+        'embed_grad_smp_mark fields=0,5 held=0',
+        'embed_grad_smp[1] fields=0,5 acc=0 held=0 dw=shared',
+        'embed_grad_ss skip=0,1,3,4,5 marks=None acc=0 held=0 dw=shared',
+        'embed_grad_smp[2] fields=0,5 acc=0 held=0 dw=shared',
     ],
     ('tiny+big+mid', False, 'seg', 'premarked'): [
-        'relu_bwd',
-        'linear_wgrad cols=13 out=view keep=None',
-        'transpose',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=None dw=shared',
-        'embed_grad_smp[1] fields=0,5 acc=0 keep=None dw=shared',
-        'embed_grad_ss skip=0,1,3,4,5 marks=sort acc=0 keep=None dw=shared',
-        'embed_grad_smp[2] fields=0,5 acc=0 keep=None dw=shared',
+        'relu_bwd held=0',
+        'linear_wgrad cols=13 out=view held=0',
+        'transpose held=0',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=0 dw=shared',
+        'embed_grad_smp[1] fields=0,5 acc=0 held=0 dw=shared',
+        'embed_grad_ss skip=0,1,3,4,5 marks=sort acc=0 held=0 dw=shared',
+        'embed_grad_smp[2] fields=0,5 acc=0 held=0 dw=shared',
     ],
     ('tiny+big+mid', False, 'bf16'): [
-        'relu_bwd',
-        'linear_wgrad_xbf16 cols=397 keep=None',
-        'transpose',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=None dw=None',
-        'embed_grad_gemm skip=1,3,4 acc=0',
+        'relu_bwd held=0',
+        'linear_wgrad_xbf16 cols=397 held=0',
+        'transpose held=0',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=0 dw=None',
+        'embed_grad_gemm skip=1,3,4 acc=0 held=0',
     ],
     ('tiny+big+mid', False, 'seg', 'smp does not fit'): [
-        'relu_bwd',
-        'linear_wgrad cols=13 out=view keep=None',
-        'transpose',
-        'embed_grad_tiny fields=1,3,4 acc=0 keep=None dw=shared',
-        'embed_grad_seg skip=1,3,4 acc=0 keep=None dw=shared',
+        'relu_bwd held=0',
+        'linear_wgrad cols=13 out=view held=0',
+        'transpose held=0',
+        'embed_grad_tiny fields=1,3,4 acc=0 held=0 dw=shared',
+        'embed_grad_seg skip=1,3,4 acc=0 held=0 dw=shared',
     ],
 }
 
@@ -504,6 +506,7 @@ def test_a_failing_side_launch_still_returns_to_the_main_section(monkeypatch, ta
     with pytest.raises(RuntimeError, match="fails"):
         _backward(layer, _lookup(layer), x_mode)
     assert rec.log[-2].startswith(fail_in) and rec.log[-1] == "section(0)"
+    assert not hip.holding.active()  # the backward's holding() block is closed behind the exception
     assert rec.log.count("section(2)") == rec.log.count("section(0)")
 
 

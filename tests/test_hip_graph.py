@@ -73,19 +73,12 @@ def _build(kind, enc):
     return model
 
 
-@pytest.mark.parametrize("kind,replay,steps,defer", [("deepfm64", "closed", 330, False), ("deepfm64", "exact", 60, False),
-                                                     ("deepfm16", "closed", 300, False), ("dcn", "closed", 60, False),
-                                                     ("deepfm32tail", "closed", 40, True), ("xdeepfm_dropout", "closed", 40, True),
-                                                     ("deepfm64", "closed", 300, True), ("mmoe", "closed", 40, True),
-                                                     ("autoint", "closed", 40, True), ("xdeepfm64", "closed", 40, True)])
-def test_graphed_step_is_bit_identical_to_the_eager_loop(kind, replay, steps, defer, backend):
-    """(330 / 300 steps cross step 256, where the closed-form replay takes over, and — with TABLE_CHUNK = 100 — several
-    in-place extensions of the step tables; the learning rate changes twice on the way)"""
-    from rec_pangu_amd import hip
+def _eager_and_graphed(kind, enc, batches, steps, replay, defer, backend, after_call=None):
+    """`steps` training steps on `batches`, once as the eager loop and once through a GraphedTrainStep (the learning rate is
+    halved at steps 40 and 200) -> ({mode: (sampled predictions, losses, state dict, optimizer state, step counters)}, the
+    GraphedTrainStep).  after_call(i, gstep): called behind the graphed run's call i."""
     from rec_pangu_amd.graph_step import GraphedTrainStep
     from rec_pangu_amd.optim import FusedAdam, LazyAdamRows, StepTables
-    enc = _enc(5, [3000, 17, 900, 4, 20000, 250])
-    batches = _batches(enc, 384, steps + 1, seed=4)
     results = {}
     chunk, LazyAdamRows.TABLE_CHUNK = LazyAdamRows.TABLE_CHUNK, 100
     min_cap, StepTables.MIN_CAPACITY = StepTables.MIN_CAPACITY, 0  # (small tables: capacity doublings re-capture on the way)
@@ -101,6 +94,8 @@ def test_graphed_step_is_bit_identical_to_the_eager_loop(kind, replay, steps, de
                         grp["lr"] *= 0.5
                 if gstep is not None:
                     out = gstep(batches[i], batches[i + 1])
+                    if after_call is not None:
+                        after_call(i, gstep)
                 else:
                     model.prefetch(batches[i + 1])
                     out = model(batches[i])
@@ -137,7 +132,10 @@ def test_graphed_step_is_bit_identical_to_the_eager_loop(kind, replay, steps, de
         StepTables.MIN_CAPACITY = min_cap
         from rec_pangu_amd.models.layers.embedding import EmbeddingLayer
         EmbeddingLayer.unpin_sorts()
-    e, g = results["eager"], results["graph"]
+    return results, gstep
+
+
+def _assert_bit_identical(e, g):
     for a, b in zip(e[0], g[0]):
         assert torch.equal(a, b), "predictions differ"
     for a, b in zip(e[1], g[1]):
@@ -148,7 +146,58 @@ def test_graphed_step_is_bit_identical_to_the_eager_loop(kind, replay, steps, de
         for k in sa:
             assert torch.equal(sa[k], sb[k]), f"optimizer state {k}"
     assert e[4] == g[4]
+
+
+@pytest.mark.parametrize("kind,replay,steps,defer", [("deepfm64", "closed", 330, False), ("deepfm64", "exact", 60, False),
+                                                     ("deepfm16", "closed", 300, False), ("dcn", "closed", 60, False),
+                                                     ("deepfm32tail", "closed", 40, True), ("xdeepfm_dropout", "closed", 40, True),
+                                                     ("deepfm64", "closed", 300, True), ("mmoe", "closed", 40, True),
+                                                     ("autoint", "closed", 40, True), ("xdeepfm64", "closed", 40, True)])
+def test_graphed_step_is_bit_identical_to_the_eager_loop(kind, replay, steps, defer, backend):
+    """(330 / 300 steps cross step 256, where the closed-form replay takes over, and — with TABLE_CHUNK = 100 — several
+    in-place extensions of the step tables; the learning rate changes twice on the way)"""
+    from rec_pangu_amd import hip
+    enc = _enc(5, [3000, 17, 900, 4, 20000, 250])
+    batches = _batches(enc, 384, steps + 1, seed=4)
+    results, _ = _eager_and_graphed(kind, enc, batches, steps, replay, defer, backend)
+    _assert_bit_identical(results["eager"], results["graph"])
     assert hip.launch_count() > 0
+
+
+def test_a_recorded_first_layer_backward_holds_every_block_it_allocates(monkeypatch):
+    """The plan's inline section runs BESIDE the launches recorded behind it, so no two tensors hip allocates between the
+    backward's fork and its join may share memory: every allocation of the first capture made inside the backward's
+    hip.holding() block is logged (address, bytes) and the blocks must be pairwise disjoint — a dropped temporary whose
+    block the capture's allocator handed to the next launch would show here, where comparing results usually does not.
+    The smallest shape with all three backward forms and both side sections: tables of [600, 5, 300, 3, 7, 1000] rows at
+    B = 512 (tiny 1, 3, 4; big 0, 5; mid 2; RP_SMP_MIN_BATCH = 1: conftest).  Then twenty replays against the eager loop."""
+    from rec_pangu_amd import hip
+    monkeypatch.setenv("RP_GRAPH_BACKEND", "plan")
+    enc = _enc(5, [r - 1 for r in (600, 5, 300, 3, 7, 1000)])
+    steps = 3 + 20  # two eager calls, the call that captures, twenty more
+    batches = _batches(enc, 512, steps + 1, seed=11)
+    new, log = hip._new, []
+
+    def logged(shape, dtype, device):
+        t = new(shape, dtype, device)
+        log.append((t.data_ptr(), t.numel() * t.element_size(), hip.holding.active()))
+        return t
+
+    def after_call(i, gstep):
+        if i == 2:  # the first capture is done: later captures share its pool and may reuse what it dropped at its end
+            assert gstep.replays == 1 and gstep.backend_used == "plan", (gstep.backend_used, gstep.why_not_plan)
+            monkeypatch.setattr(hip, "_new", new)
+
+    monkeypatch.setattr(hip, "_new", logged)
+    results, gstep = _eager_and_graphed("deepfm64", enc, batches, steps, "closed", True, "plan", after_call)
+    assert hip._new is new and gstep.backend_used == "plan" and gstep.plans[0].inline >= 1
+    held = sorted((p, n) for p, n, active in log if active and n > 0)
+    print(f"{len(log)} allocations logged, {len(held)} non-empty ones inside the holding block: {sorted(n for _, n in held)} bytes")
+    # at least the workspaces of linear_wgrad, embed_grad_tiny, embed_grad_smp and embed_grad_ss
+    assert len(held) >= 4
+    for (p0, n0), (p1, _) in zip(held, held[1:]):
+        assert p0 + n0 <= p1, f"two blocks held at once overlap: {p0:#x}+{n0} and {p1:#x}"
+    _assert_bit_identical(results["eager"], results["graph"])
 
 
 def test_graphed_step_falls_back_to_eager_for_the_unannounced_and_the_last_batch(backend):
