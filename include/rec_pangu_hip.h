@@ -103,8 +103,8 @@ int rp_embed_gather_fwd(const float *arena, const int64_t *row_base, const int64
  * rp_embed_gather_linear_fits: D == 64, a 64-wide layer, ND <= 16 (and F <= 32); otherwise RP_ERR_UNSUPPORTED
  * (compose rp_embed_gather_fwd + rp_linear_fwd).
  *   xd [B, 64] (instead of x; NULL otherwise): ONLY the dense columns are stored (zero padded to 64) — the layer's weight
- *   gradient then gathers the embedding rows again itself (rp_linear_wgrad_gather below) and the 4*F*D bytes per sample of
- *   the x store (436 MB at Criteo shape) are never written. */
+ *   gradient's embedding columns then come from rp_embed_grad_seg and the 4*F*D bytes per sample of the x store (436 MB
+ *   at Criteo shape) are never written. */
 int rp_embed_gather_linear_fits(int D, int ND, int hidden, int64_t ldx, int64_t ldw);
 int rp_embed_gather_linear_fwd(const float *arena, const int64_t *row_base, const int64_t *row_count,
                                const int64_t *const *idx_ptrs, int F, const float *const *dense_ptrs, int ND, int64_t B,
@@ -133,7 +133,7 @@ int rp_embed_gather_linear_fwd_bf16(const void *arena_bf16, const int64_t *row_b
  * (stable, so equal rows keep ascending sample order; end_bit = 32 orders the keys as SIGNED ints);
  * position = index into keys_in.  keys_in / keys_out / pos_out must not alias.  Kernel launches only (no
  * memset, nothing carried between calls): capturable into a hipGraph at any n.  Workspace size from
- * rp_sort_workspace_bytes.  RP_SORT=rocprim in the environment selects rocPRIM's radix sort instead. */
+ * rp_sort_workspace_bytes. */
 int rp_sort_workspace_bytes(int64_t n, size_t *bytes);
 int rp_sort_pairs_i32(void *workspace, size_t workspace_bytes, const int32_t *keys_in, int32_t *keys_out,
                       int32_t *pos_out, int64_t n, int end_bit, rp_stream_t stream);
@@ -291,15 +291,6 @@ int rp_linear_wgrad(const float *dy, int64_t lddy, const float *x, int64_t ldx, 
 int rp_linear_wgrad_xbf16(const float *dy, int64_t lddy, const void *x_bf16, int64_t ldx, float *dw, int64_t lddw,
                           float *db, int64_t M, int N, int K, int accumulate, void *workspace, size_t workspace_bytes,
                           rp_stream_t stream);
-/* The weight gradient of a layer whose input is the embedding lookup, WITHOUT the stored activation: the first Kg = F*64
- * columns of X are gathered — X[m, f*64 + j] = arena[keys[f*M + m]*64 + j], keys = the arena rows the forward saved
- * (rp_embed_gather_linear_fwd keys_out / rp_embed_keys) — the remaining K - Kg <= 64 columns (dense features) come from
- * xd [M, ldxd].  N == 64, Kg a multiple of 128, bf16 matrix-core modes (rp_linear_wgrad_gather_fits); workspace as
- * rp_linear_wgrad_workspace_bytes(M, N, K). */
-int rp_linear_wgrad_gather_fits(int64_t M, int N, int K, int Kg);
-int rp_linear_wgrad_gather(const float *dy, int64_t lddy, const float *arena, const int32_t *keys, int Kg, const float *xd,
-                           int64_t ldxd, float *dw, int64_t lddw, float *db, int64_t M, int N, int K, int accumulate,
-                           void *workspace, size_t workspace_bytes, rp_stream_t stream);
 /* out[C,R] = in[R,C]^T (weights for the dgrad GEMM); rows C .. C_out-1 of out (C_out >= C) are written as zeros */
 int rp_transpose(const float *in, int64_t ldin, float *out, int64_t ldout, int R, int C, int C_out, rp_stream_t stream);
 /* rp_transpose and rp_copy_rows of the same matrix in ONE launch: out = in^T as rp_transpose, copy[r, 0:C] = in[r, 0:C] with

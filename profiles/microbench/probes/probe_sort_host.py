@@ -19,7 +19,7 @@ for eb in (9, 18, 26, 32):
         t1 = time.perf_counter()
         torch.cuda.synchronize()
         t2 = time.perf_counter()
-    print(f"RP_SORT={os.environ.get('RP_SORT','own')} n={n} end_bit={eb}: enqueue {(t1-t0)/200*1e6:.1f} us/call, with device {(t2-t0)/200*1e6:.1f} us/call", flush=True)
+    print(f"n={n} end_bit={eb}: enqueue {(t1-t0)/200*1e6:.1f} us/call, with device {(t2-t0)/200*1e6:.1f} us/call", flush=True)
 # the python wrapper (workspace query + torch.empty x3)
 torch.cuda.synchronize()
 t0 = time.perf_counter()

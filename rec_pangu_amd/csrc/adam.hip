@@ -1096,16 +1096,14 @@ extern "C" int rp_lazy_adam_catchup(const int32_t *sorted_keys, int64_t n, int D
     const int vw = (D % 4 == 0 && rp_aligned16(p) && rp_aligned16(m) && rp_aligned16(v) && (!g || rp_aligned16(g))) ? 4 : 1;
     LazyCfg c{(float)(1.0 - beta1), (float)beta2, (float)std::sqrt(beta2), (float)(1.0 - beta2), (float)eps};
     int tpr = lazy_tpr(D, vw);
-    // column chunks per lane (catchup_row_chunks): RP_CATCHUP_CHUNKS = 1, 2 (default) or 4
-    static const int chunks = getenv("RP_CATCHUP_CHUNKS") ? atoi(getenv("RP_CATCHUP_CHUNKS")) : 2;
-    if ((chunks == 2 || chunks == 4) && tpr >= chunks && D == tpr * vw) tpr /= chunks;
+    // two column chunks per lane (catchup_row_chunks) where the row splits evenly
+    if (tpr >= 2 && D == tpr * vw) tpr /= 2;
     hipStream_t s = (hipStream_t)stream;
     const float2 *sc = reinterpret_cast<const float2 *>(step_scalars);
     const CfEntry *cf = reinterpret_cast<const CfEntry *>(cf_table);
-    // D = 64 rows as two float4 chunks per lane (the layers of every BASELINE config): run heads compacted per wave
-    // (RP_CATCHUP_WAVE=0: one lane group per sorted pair, as before)
-    static const bool wave_form = !(getenv("RP_CATCHUP_WAVE") && getenv("RP_CATCHUP_WAVE")[0] == '0');
-    if (wave_form && vw == 4 && D == 64 && tpr == 8) {
+    // D = 64 rows as two float4 chunks per lane (the layers of every BASELINE config): run heads compacted per wave;
+    // every other shape: one lane group per sorted pair
+    if (vw == 4 && D == 64 && tpr == 8) {
         hipLaunchKernelGGL((lazy_adam_catchup_wave_kernel<2, 8, f32x4>), dim3((unsigned)rp_cdiv(n, 256)), dim3(256), 0, s, sorted_keys,
                            n, D, p, g, m, v, last, sc, (int)t_done, mark, c, cf, (int)cf_from, t_dev,
                            reinterpret_cast<uint16_t *>(shadow_bf16));

@@ -18,7 +18,8 @@ void rp_count_launch() { g_launches.fetch_add(1, std::memory_order_relaxed); }
 
 // bumped whenever an entry point's signature changes or one is added: rec_pangu_amd/hip.py refuses a library of another
 // version (its ctypes table would call through the wrong prototypes silently).  106 = round 6; 107: two launch-plan entry
-// points removed; 108: rp_layernorm_*.
+// points removed; 108: rp_layernorm_* (rp_linear_wgrad_gather and its _fits left without a bump: bindings that still name a
+// removed entry point fail when they look it up, nothing is called through a wrong prototype).
 extern "C" int rp_version(void) { return 108; }
 extern "C" const char *rp_last_error(void) { return g_err; }
 extern "C" uint64_t rp_launch_count(void) { return g_launches.load(std::memory_order_relaxed); }

@@ -29,10 +29,7 @@ __device__ __forceinline__ float block_allsum_256(float v, float *sh) {
 // next to them — the biases are staged once per workgroup, zero-padded to 256-column chunks; lane l owns columns
 // 256j + 4l .. +3 of chunk j (dwordx4 global accesses, conflict-free ds_read_b128).  The row stays in registers
 // through all L layers; each layer is one dot product (wave shuffles, no barrier) and one axpy.
-static int64_t cross_nb_max(int64_t dflt) {  // (RP_CROSS_NB: experiment knob for the persistent grid size)
-    static const int64_t v = getenv("RP_CROSS_NB") ? atoll(getenv("RP_CROSS_NB")) : 0;
-    return v > 0 ? v : dflt;
-}
+constexpr int64_t CROSS_NB_MAX = 2048;  // the persistent grid's size
 
 // Stage `nrows` weight rows of d floats into LDS, zero padded to dp (a multiple of 256) columns per row.  A 256-column
 // chunk lies inside one row, so the row (and its source pointer) is wave-uniform; four chunks are requested per iteration
@@ -313,8 +310,7 @@ extern "C" int rp_crossnet_bwd_rows(const float *x0, int64_t ldx, int d, int L, 
     const bool vec = (ldx % 4 == 0) && (lddx % 4 == 0) && rp_aligned16(x0) && rp_aligned16(dx0) &&
                      (g_x == nullptr || ((ldg % 4 == 0) && rp_aligned16(g_x)));
     int64_t nb = rp_cdiv(B, 4);
-    const int64_t nb_max = cross_nb_max(2048);
-    if (nb > nb_max) nb = nb_max;  // persistent: each wave walks over B / (4 * nb) rows, W staged once per workgroup
+    if (nb > CROSS_NB_MAX) nb = CROSS_NB_MAX;  // persistent: each wave walks over B / (4 * nb) rows, W staged once per workgroup
     if (vec)
         hipLaunchKernelGGL((crossnet_bwd_rows_kernel<true>), dim3((unsigned)nb), dim3(256), lds, (hipStream_t)stream, x0,
                            ldx, d, L, W, wfc, s_in, g_x, ldg, g_logit, dx0, lddx, V, B);
@@ -380,8 +376,7 @@ extern "C" int rp_crossnet_fwd(const float *x0, int64_t ldx, int d, int L, const
     const size_t lds = (size_t)(b_lds ? 2 * L + 1 : L + 1) * dp * sizeof(float);
     const bool vec = (ldx % 4 == 0) && rp_aligned16(x0) && (xout == nullptr || ((ldo % 4 == 0) && rp_aligned16(xout)));
     int64_t nb = rp_cdiv(B, 4);
-    const int64_t nb_max = cross_nb_max(2048);
-    if (nb > nb_max) nb = nb_max;
+    if (nb > CROSS_NB_MAX) nb = CROSS_NB_MAX;
     hipStream_t st = (hipStream_t)stream;
 #define CF(VEC, BL)                                                                                                   \
     hipLaunchKernelGGL((crossnet_fwd_kernel<VEC, BL>), dim3((unsigned)nb), dim3(256), lds, st, x0, ldx, d, L, W, Bv, wfc, \

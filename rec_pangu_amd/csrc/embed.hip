@@ -321,8 +321,8 @@ __global__ __launch_bounds__(256) void embed_grad_reduce_kernel(
 // ------------------------------------------------------------------------------------------------
 #define EGL_XLD 68  // floats per staged row (64 + 4 pad)
 #define EGL_KLD 33  // keys per row in LDS (odd: the key fill writes 32 consecutive rows at a fixed field)
-// STORE_X = false (with FULL): the gathered rows are NOT written to x — the first layer's weight gradient gathers them
-// again itself (rp_linear_wgrad_gather) — only the dense columns go to the compact buffer xd [B, 64]
+// STORE_X = false (with FULL): the gathered rows are NOT written to x — only the dense columns go to the compact buffer
+// xd [B, 64]
 // BF16_ROWS: the arena holds bf16 rows (128 bytes at D = 64: the bf16-STORAGE inference mode, half the gather traffic);
 // a lane reads 4 bf16 (8 bytes) where the fp32 form reads a float4 and widens them — exact — so everything downstream
 // (FM sums in fp32, the split-bf16 products) is unchanged.
@@ -1304,12 +1304,7 @@ extern "C" int rp_embed_grad_gemm(const int32_t *sorted_keys, const int32_t *sor
     float *piece0 = reinterpret_cast<float *>(wbase);
     int32_t *key0 = reinterpret_cast<int32_t *>(piece0 + nb0 * 2 * D);
     hipStream_t s = (hipStream_t)stream;
-    // RP_GRAD_GEMM_FMU=0: the FM sum rows are gathered per pair in the reduce phase (the round-3 form, kept for A/B runs)
-    static const bool fmu_on = []() {
-        const char *e = getenv("RP_GRAD_GEMM_FMU");
-        return !(e && e[0] == '0');
-    }();
-    if (gfm != nullptr && sum_in != nullptr && fmu_on)
+    if (gfm != nullptr && sum_in != nullptr)
         hipLaunchKernelGGL((embed_grad_gemm_kernel<true>), dim3((unsigned)nb0), dim3(256), 0, s, sorted_keys, sorted_pos, n, (int)B,
                            dh, lddh, wt, ldwt, dx, ldx, gfm, sum_in, arena, grad_arena, accumulate, piece0, key0, rg);
     else

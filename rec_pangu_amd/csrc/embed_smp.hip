@@ -368,21 +368,12 @@ __global__ __launch_bounds__(256) void embed_grad_smp_dw_kernel(const float *__r
 }
 
 // blocks of SM_ROWS samples per workgroup / fields per workgroup: ~512 workgroups (two per CU), a field's weight-gradient
-// partial covers `bpw` blocks (RP_SMP_BPW / RP_SMP_FPW override)
+// partial covers `bpw` blocks
 static void smp_shape(int64_t B, int nf, int *fpw, int *bpw, int *nranges) {
-    static const int e_bpw = []() {
-        const char *e = getenv("RP_SMP_BPW");
-        return e ? atoi(e) : 0;
-    }();
-    static const int e_fpw = []() {
-        const char *e = getenv("RP_SMP_FPW");
-        return e ? atoi(e) : 0;
-    }();
     const int nblk = (int)rp_cdiv(B, SM_ROWS);
-    int f = e_fpw > 0 ? e_fpw : 2;
-    f = f > nf ? nf : f;
+    const int f = nf < 2 ? nf : 2;
     const int fgroups = (int)rp_cdiv(nf, f);
-    int b = e_bpw > 0 ? e_bpw : (int)rp_cdiv((int64_t)nblk * fgroups, 512);
+    int b = (int)rp_cdiv((int64_t)nblk * fgroups, 512);
     b = b < 1 ? 1 : (b > nblk ? nblk : b);
     *fpw = f;
     *bpw = b;

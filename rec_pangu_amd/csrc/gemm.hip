@@ -818,25 +818,16 @@ static void run_smallk(const float *a, int64_t lda, const float *w, int64_t ldw,
 // registers.
 // (NA = 1: 168 registers, three workgroups per CU.  Deeper register prefetch (PF = 2, 3: 224 / 246 registers, two per CU)
 //  measured 4 % and 16 % SLOWER at 65536 x 64 x 1677.)
-// GATHER (rp_linear_wgrad_gather: the first layer of a model whose input is the embedding lookup): the first Kg = F * 64
-// columns of X are not read from a materialised activation buffer but GATHERED — X[m, f*64 + j] = arena[keys[f*keyB + m]*64
-// + j] with the arena-row keys the forward saved — so the forward never has to store its 436 MB of gathered rows; columns
-// >= Kg (the dense features) come from the compact buffer X (leading dimension ldx, column k - Kg).  A k-tile of 128
-// columns is two fields: lanes c < 32 read the row of field k0/64, the others the next one (two 256-byte segments per
-// wave-instruction, as coalesced as the activation read they replace).  Keys are fetched one stage ahead of the rows
-// they address.
 // X_BF16 (round 4, the bf16-storage training mode): X is stored as bf16 [M, ldx] (ldx in elements): a lane reads its two
 // columns as one dword and widens them — exact — so everything downstream is unchanged; half the bytes of the operand that
 // dominates this launch's traffic.
-template <int NPROD, int NA, int PF, bool VEC_X, bool GATHER = false, bool X_BF16 = false>
+template <int NPROD, int NA, int PF, bool VEC_X, bool X_BF16 = false>
 __global__ __launch_bounds__(256, NA == 1 ? 3 : 2) void linear_wgrad_bf16_kernel(const float *__restrict__ dY, int64_t lddy,
                                                                 const float *__restrict__ X, int64_t ldx,
                                                                 float *__restrict__ P, float *__restrict__ Pb,
                                                                 int64_t M, int N, int K, int64_t rows_per_split,
-                                                                const float *__restrict__ arena = nullptr,
-                                                                const int32_t *__restrict__ keys = nullptr,
-                                                                int64_t keyB = 0, int Kg = 0, int xcd_tiles = 0,
-                                                                int xcd_ktiles = 0, int xcd_splits = 0) {
+                                                                int xcd_tiles = 0, int xcd_ktiles = 0,
+                                                                int xcd_splits = 0) {
     // output tile (64*NA) n x 128 k; waves 2 (n) x 2 (k), each NA x 2 MFMA tiles (NA = 2 for wide layers: every
     // fragment read from LDS then feeds two MFMA tiles)
     constexpr int NP = BfProd<NPROD>::NP;
@@ -870,9 +861,6 @@ __global__ __launch_bounds__(256, NA == 1 ? 3 : 2) void linear_wgrad_bf16_kernel
 
     float ry[PF][NA][8];
     f32x2 rx[PF][8];
-    const bool gtile = GATHER && (k0 + TN_BK <= Kg);                      // this k-tile is gathered (block-uniform)
-    const int32_t *kcol = GATHER ? keys + (int64_t)(kx >> 6) * keyB : nullptr;  // the keys of this lane's field
-    const int cin = kx & 63;
     auto load_tile = [&](int64_t mm, float (&dy_)[NA][8], f32x2 (&dx_)[8]) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
@@ -881,15 +869,7 @@ __global__ __launch_bounds__(256, NA == 1 ? 3 : 2) void linear_wgrad_bf16_kernel
 #pragma unroll
             for (int u = 0; u < NA; ++u) dy_[u][r] = (ok && n0 + c + 64 * u < N) ? dY[m * lddy + n0 + c + 64 * u] : 0.f;
             f32x2 v = {0.f, 0.f};
-            if (GATHER && ok) {
-                if (gtile) {
-                    v = *reinterpret_cast<const f32x2 *>(arena + (int64_t)kcol[m] * 64 + cin);
-                } else {  // the dense columns, from the compact buffer
-                    const float *px = X + m * ldx + (kx - Kg);
-                    if (kx < K) v.x = px[0];
-                    if (kx + 1 < K) v.y = px[1];
-                }
-            } else if (X_BF16) {
+            if (X_BF16) {
                 // branch-free (a load behind a branch turns every wait of the loop into vmcnt(0): the guarded k-tile of a
                 // bf16 activation ran 16 serialized 2-byte loads per stage): row and column clamped into the buffer, the
                 // dword always loaded, what lies outside masked afterwards (ldx is even and >= K)
@@ -919,20 +899,12 @@ __global__ __launch_bounds__(256, NA == 1 ? 3 : 2) void linear_wgrad_bf16_kernel
     const float *yb = dY + (mbeg + 8 * o) * lddy + n0 + c;
     const float *xb = X + (mbeg + 8 * o) * ldx + kx;
     const uint16_t *xb16 = reinterpret_cast<const uint16_t *>(X) + (mbeg + 8 * o) * ldx + kx;  // (X_BF16)
-    const int32_t *kb = GATHER ? kcol + mbeg + 8 * o : nullptr;
-    int32_t kreg[8];  // GATHER: the keys of the rows the NEXT load_tile_full fetches
-    auto load_keys = [&](int64_t moff) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) kreg[r] = kb[moff + r];
-    };
     auto load_tile_full = [&](int64_t moff, float (&dy_)[NA][8], f32x2 (&dx_)[8]) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) {
 #pragma unroll
             for (int u = 0; u < NA; ++u) dy_[u][r] = yb[(moff + r) * lddy + 64 * u];
-            if (GATHER) {
-                dx_[r] = *reinterpret_cast<const f32x2 *>(arena + (int64_t)kreg[r] * 64 + cin);
-            } else if (X_BF16) {
+            if (X_BF16) {
                 const uint32_t w2 = *reinterpret_cast<const uint32_t *>(xb16 + (moff + r) * ldx);
                 dx_[r] = f32x2{__uint_as_float(w2 << 16), __uint_as_float(w2 & 0xFFFF0000u)};
             } else {
@@ -1012,23 +984,7 @@ __global__ __launch_bounds__(256, NA == 1 ? 3 : 2) void linear_wgrad_bf16_kernel
     const int64_t nst = (mend > mbeg) ? (mend - mbeg + TN_BM - 1) / TN_BM : 0;  // stages of 32 batch rows
     const int64_t nstf = (mend > mbeg) ? (mend - mbeg) / TN_BM : 0;             // ... that are complete
     int64_t sbeg = 0;
-    if (GATHER && gtile && PF == 1 && (n0 + BNT <= N) && nstf >= 3) {
-        // straight-line main loop as below; the keys of stage s + 2 are requested right after the rows of stage s + 1
-        load_keys(0);
-        load_tile_full(0, ry[0], rx[0]);
-        load_keys(TN_BM);
-        const int64_t nloop = nstf - 2;
-        for (int64_t it = 0; it < nloop; ++it) {
-            stage(ry[0], rx[0]);
-            load_tile_full((it + 1) * TN_BM, ry[0], rx[0]);
-            load_keys((it + 2) * TN_BM);
-            compute();
-        }
-        stage(ry[0], rx[0]);
-        load_tile_full((nloop + 1) * TN_BM, ry[0], rx[0]);
-        compute();
-        sbeg = nloop + 1;
-    } else if (!GATHER && VEC_X && (n0 + BNT <= N) && (k0 + TN_BK <= K) && nstf >= 2 * PF) {
+    if (VEC_X && (n0 + BNT <= N) && (k0 + TN_BK <= K) && nstf >= 2 * PF) {
 #pragma unroll
         for (int p = 0; p < PF; ++p) load_tile_full((int64_t)p * TN_BM, ry[p], rx[p]);
         const int64_t nloop = (nstf - PF) / PF;
@@ -1186,8 +1142,6 @@ int rp_matmul_products(double flops, double bytes) {
     return (bytes > 0 && flops * 3.0 / bytes > 312.0) ? 3 : 6;
 }
 
-static int g_wide_kernel = 1;  // RP_WIDE_KERNEL=0 in the environment: fall back to the 128 x 128 kernel (A/B measurements)
-
 static int linear_mode(int64_t M, int N, int K) {  // the RP_MATMUL_* mode one GEMM launch runs in
     if (g_matmul_precision != RP_MATMUL_AUTO) return g_matmul_precision;
     return rp_matmul_products(2.0 * M * N * K, 4.0 * ((double)M * K + (double)N * K + (double)M * N)) == 3
@@ -1195,15 +1149,6 @@ static int linear_mode(int64_t M, int N, int K) {  // the RP_MATMUL_* mode one G
 }
 
 extern "C" int rp_get_matmul_precision(void) { return g_matmul_precision; }
-
-namespace {
-struct WideKernelEnv {
-    WideKernelEnv() {
-        const char *e = getenv("RP_WIDE_KERNEL");
-        if (e && e[0] == '0') g_wide_kernel = 0;
-    }
-} g_wide_kernel_env;
-}  // namespace
 
 // out[M,N] = a[M,K] . w[N,K]^T  +  row_scale[m] * row_add[m, n % 64] for n < add_cols       (no bias, no activation)
 // Restricted to what the DeepFM dgrad needs and the straight-line short-K kernel covers: K <= 64 and a multiple of 4,
@@ -1264,7 +1209,7 @@ extern "C" int rp_linear_fwd(const float *a, int64_t lda, const float *w, int64_
                                  act, aux ? aux + Nb : nullptr, ldaux, stream);
         }
         // wide, matrix-core-bound layers in a two-piece mode: 256 x 128 tiles, 64 x 64 wave tiles, double-buffered LDS
-        if ((mode == RP_MATMUL_BF16X3 || mode == RP_MATMUL_BF16) && g_wide_kernel && N >= 256 && N % 32 == 0 && M % 256 == 0 &&
+        if ((mode == RP_MATMUL_BF16X3 || mode == RP_MATMUL_BF16) && N >= 256 && N % 32 == 0 && M % 256 == 0 &&
             K >= 192 && va && vw && rp_cdiv(N, 128) * (M / 256) >= 512) {
             const int mblocks = (int)(M / 256), nblocks = (int)rp_cdiv(N, 128);
             const int groups = (int)rp_cdiv(mblocks, 8);
@@ -1323,10 +1268,6 @@ extern "C" int rp_linear_fwd(const float *a, int64_t lda, const float *w, int64_
 }
 
 static bool wgrad_wide(int N) { return g_matmul_precision != RP_MATMUL_FP32 && N >= 128; }  // 128 x 128 output tiles
-static bool wgrad_xcd_local() {  // RP_WGRAD_XCD=0: the plain 3-D grid (A/B switch of the XCD-local tile order)
-    static const bool on = !(getenv("RP_WGRAD_XCD") && atoi(getenv("RP_WGRAD_XCD")) == 0);
-    return on;
-}
 
 static void wgrad_plan(int64_t M, int N, int K, int *S, int64_t *rows) {
     const bool wide = wgrad_wide(N);
@@ -1351,12 +1292,10 @@ static void wgrad_plan(int64_t M, int N, int K, int *S, int64_t *rows) {
         }
         s = best;
     }
-    if (wide && wgrad_xcd_local()) {  // XCD-local order: whole groups of eight splits (one per XCD)
+    if (wide) {  // XCD-local order: whole groups of eight splits (one per XCD)
         s = ((s + 4) / 8) * 8;
         if (s < 8) s = 8;
     }
-    static const int s_env = getenv("RP_WGRAD_S") ? atoi(getenv("RP_WGRAD_S")) : 0;  // (profiles/microbench/wgrad_one.py)
-    if (s_env > 0) s = s_env;
     int64_t r = rp_cdiv(rp_cdiv(M, s), TN_BM) * TN_BM;
     if (r < TN_BM) r = TN_BM;
     *rows = r;
@@ -1395,12 +1334,11 @@ extern "C" int rp_linear_wgrad(const float *dy, int64_t lddy, const float *x, in
         const bool vx2 = (ldx % 2 == 0) && (reinterpret_cast<uintptr_t>(x) % 8 == 0);
         const bool wide = wgrad_wide(N);
         dim3 gridb((unsigned)rp_cdiv(K, TN_BK), (unsigned)rp_cdiv(N, wide ? 2 * TN_BN : TN_BN), (unsigned)S);
-        const bool xl = wide && wgrad_xcd_local();
-        const int xt = xl ? (int)(gridb.x * gridb.y) : 0, xk = (int)gridb.x;
-        if (xl) gridb = dim3((unsigned)(8 * rp_cdiv(S, 8) * xt), 1u, 1u);
+        const int xt = wide ? (int)(gridb.x * gridb.y) : 0, xk = (int)gridb.x;  // (wide: the XCD-local 1-D grid)
+        if (wide) gridb = dim3((unsigned)(8 * rp_cdiv(S, 8) * xt), 1u, 1u);
 #define CALLW(NPROD, NA, PF, VX)                                                                                        \
     hipLaunchKernelGGL((linear_wgrad_bf16_kernel<NPROD, NA, PF, VX>), gridb, dim3(256), 0, s, dy, lddy, x, ldx, P, Pb, M, \
-                       N, K, rows, (const float *)nullptr, (const int32_t *)nullptr, (int64_t)0, 0, xt, xk, S)
+                       N, K, rows, xt, xk, S)
 #define CALLB(NPROD)                          \
     do {                                      \
         if (wide && vx2) CALLW(NPROD, 2, 2, true);   \
@@ -1453,8 +1391,8 @@ extern "C" int rp_linear_wgrad_xbf16(const float *dy, int64_t lddy, const void *
     hipStream_t s = (hipStream_t)stream;
     const float *xf = reinterpret_cast<const float *>(x_bf16);
 #define CALLX(NPROD)                                                                                                       \
-    hipLaunchKernelGGL((linear_wgrad_bf16_kernel<NPROD, 1, 1, true, false, true>), gridb, dim3(256), 0, s, dy, lddy, xf, ldx, P, \
-                       Pb, M, N, K, rows, (const float *)nullptr, (const int32_t *)nullptr, (int64_t)0, 0, 0, 0, S)
+    hipLaunchKernelGGL((linear_wgrad_bf16_kernel<NPROD, 1, 1, true, true>), gridb, dim3(256), 0, s, dy, lddy, xf, ldx, P, Pb, M, \
+                       N, K, rows, 0, 0, S)
     if (mode == RP_MATMUL_BF16X6) CALLX(6);
     else if (mode == RP_MATMUL_BF16X3) CALLX(3);
     else CALLX(1);
@@ -1464,50 +1402,6 @@ extern "C" int rp_linear_wgrad_xbf16(const float *dy, int64_t lddy, const void *
     hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rp_cdiv(total, 16)), dim3(256), 0, s, P, Pb, S, N, K, dw, lddw, db,
                        accumulate);
     RP_LAUNCH_CHECK("linear_wgrad_xbf16 reduce");
-    return RP_OK;
-}
-
-// dW[N, K] = dY[M, N]^T . X[M, K] where the first Kg = F * 64 columns of X are the embedding rows of the batch, gathered
-// from the arena through the keys the forward saved (keys[f * M + m] = arena row of field f of sample m) instead of being
-// read from a stored activation buffer, and the remaining K - Kg <= 64 columns (the dense features) come from xd [M, ldxd].
-// N = 64 (the fused first layer), F even, bf16 matrix-core modes only (rp_linear_wgrad_gather_fits).
-extern "C" int rp_linear_wgrad_gather_fits(int64_t M, int N, int K, int Kg) {
-    return (g_matmul_precision != RP_MATMUL_FP32 && N == TN_BN && Kg >= TN_BK && Kg % TN_BK == 0 && K >= Kg &&
-            K - Kg <= 64 && M >= 1) ? 1 : 0;
-}
-
-extern "C" int rp_linear_wgrad_gather(const float *dy, int64_t lddy, const float *arena, const int32_t *keys, int Kg,
-                                      const float *xd, int64_t ldxd, float *dw, int64_t lddw, float *db, int64_t M, int N,
-                                      int K, int accumulate, void *workspace, size_t workspace_bytes, rp_stream_t stream) {
-    RP_REQUIRE(dy && arena && keys && dw && workspace, "linear_wgrad_gather: null pointer");
-    RP_REQUIRE(K == Kg || xd, "linear_wgrad_gather: the dense columns need xd");
-    if (!rp_linear_wgrad_gather_fits(M, N, K, Kg) || !rp_aligned16(arena))
-        return rp_fail(RP_ERR_UNSUPPORTED, "linear_wgrad_gather: needs N = 64, F*64 a multiple of 128, <= 64 dense columns, a "
-                                           "bf16 matrix-core mode");
-    RP_REQUIRE(lddy >= N && lddw >= K && (K == Kg || ldxd >= K - Kg), "linear_wgrad_gather: leading dimension too small");
-    size_t need = 0;
-    rp_linear_wgrad_workspace_bytes(M, N, K, &need);
-    RP_REQUIRE(workspace_bytes >= need, "linear_wgrad_gather: workspace %zu < %zu bytes", workspace_bytes, need);
-    int S;
-    int64_t rows;
-    wgrad_plan(M, N, K, &S, &rows);
-    float *P = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-    float *Pb = P + (size_t)S * N * K;
-    hipStream_t s = (hipStream_t)stream;
-    const int mode = linear_mode(M, N, K);
-    dim3 gridb((unsigned)rp_cdiv(K, TN_BK), 1u, (unsigned)S);
-#define CALLG(NPROD)                                                                                                        \
-    hipLaunchKernelGGL((linear_wgrad_bf16_kernel<NPROD, 1, 1, true, true>), gridb, dim3(256), 0, s, dy, lddy, xd, ldxd, P, Pb, \
-                       M, N, K, rows, arena, keys, M, Kg)
-    if (mode == RP_MATMUL_BF16X6) CALLG(6);
-    else if (mode == RP_MATMUL_BF16X3) CALLG(3);
-    else CALLG(1);
-#undef CALLG
-    RP_LAUNCH_CHECK("linear_wgrad_gather partial");
-    const int64_t total = (int64_t)N * K + N;
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)rp_cdiv(total, 16)), dim3(256), 0, s, P, Pb, S, N, K, dw, lddw, db,
-                       accumulate);
-    RP_LAUNCH_CHECK("linear_wgrad_gather reduce");
     return RP_OK;
 }
 

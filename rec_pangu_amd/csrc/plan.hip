@@ -68,12 +68,8 @@ struct Plan {
 };
 
 // Fork/join events order streams of ONE device: an agent-scope release is all their consumers need.  The default event
-// carries a system-scope fence (L2 write-back + invalidate at the record) that the next launch on the stream queues behind;
-// RP_PLAN_EVENT_FENCE=system brings it back.
-inline unsigned plan_event_flags() {
-    static const bool sys = getenv("RP_PLAN_EVENT_FENCE") && strcmp(getenv("RP_PLAN_EVENT_FENCE"), "system") == 0;
-    return sys ? hipEventDisableTiming : (hipEventDisableTiming | hipEventDisableSystemFence);
-}
+// carries a system-scope fence (L2 write-back + invalidate at the record) that the next launch on the stream queues behind.
+inline unsigned plan_event_flags() { return hipEventDisableTiming | hipEventDisableSystemFence; }
 
 inline double plan_now_ms() {
     timespec ts;

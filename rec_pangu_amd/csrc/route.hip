@@ -93,7 +93,7 @@ __global__ void route_counts_kernel(const int32_t *__restrict__ incl, int64_t n,
 
 static size_t route_align(size_t x) { return (x + 255) & ~(size_t)255; }
 
-// ---- inclusive scan of the head flags, own kernels (round 5: rocprim::inclusive_scan sat on the sharded step's hot path —
+// ---- inclusive scan of the head flags, own kernels (round 5: rocPRIM's inclusive_scan sat on the sharded step's hot path —
 //      a foreign launch sequence with its own temporary storage query).  Three launches: per-block sums of 2048 flags, one
 //      workgroup scanning the block sums, per-block scan + offset.  int32 counts, n < 2^31.
 #define RS_PER_THREAD 8

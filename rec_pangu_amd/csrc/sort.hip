@@ -2,7 +2,7 @@
 // key (26 bits cover the 33.8 M rows of the Criteo-shape arena).  Stability keeps equal rows in ascending position
 // (= ascending sample) order, which fixes the summation order downstream.
 //
-// Own kernels (the default): 9-bit digits, three launches per digit pass and NO memset / no host-side dispatch work.
+// 9-bit digits, three launches per digit pass and NO memset / no host-side dispatch work.
 //   sort_hist_kernel     one workgroup per 4096-pair tile: the tile's digit histogram -> hist[tile][512]
 //   sort_scan_kernel     one wave per digit: exclusive prefix of that digit's counts over the tiles (in place) + its total
 //   sort_scatter_kernel  the tile again: digit base (scan of the 512 totals, in LDS) + tile prefix + the stable rank of
@@ -12,21 +12,12 @@
 // lower peers, and the lowest peer bumps the wave's LDS counter of that digit — LDS operations of one wave execute in
 // program order, so the 16 rounds chain without a barrier.  Waves then take their offsets from the waves before them.
 // Positions are implicit in the first pass (no iota buffer).  26 key bits = 3 passes = 9 launches, ~35 MB of traffic
-// per pass at 1.7 M pairs: latency-bound, like rocPRIM's onesweep (four 8-bit passes).  Measured (MI355X,
-// profiles/microbench/probes/probe_sort_host.py): 1.7 M pairs 151 us on the device / 28 us of host time per call (rocPRIM 148 / 49);
-// 213 k pairs (the per-GPU batch of a strong-scaling run) 77 us / 29 us (rocPRIM's merge sort 94 / 50); beside a step
-// on the side stream the event-bracketed duration is 0.13 ms against rocPRIM's 0.33.  What the own kernels buy besides:
-// NO memset nodes and no global counters carried between launches — a captured step replays at any batch size (with
-// rocPRIM's onesweep, unsynchronised replays above ~1 M pairs ended in memory access faults), and the
-// host-bound eager step at b = 8192 drops 1.04 -> 0.77 ms.
-//
-// RP_SORT=rocprim selects rocPRIM's device radix sort (onesweep above one million pairs, merge sort below) instead;
-// tests/test_hip_kernels.py::test_sort_pairs_rocprim_path keeps it checked.  Wider rocPRIM digits measured slower
-// (9 bits, match-based ranking: 162 us; 11 bits: 421 us).
+// per pass at 1.7 M pairs: latency-bound.  Measured (MI355X, profiles/microbench/probes/probe_sort_host.py): 1.7 M pairs
+// 151 us on the device / 28 us of host time per call; 213 k pairs (the per-GPU batch of a strong-scaling run) 77 us /
+// 29 us; beside a step on the side stream the event-bracketed duration is 0.13 ms.  NO memset nodes and no global
+// counters carried between launches: a captured step replays at any batch size.
 #include "common.h"
-#include <cstdlib>
 #include <cstring>
-#include <rocprim/rocprim.hpp>
 
 namespace {
 
@@ -182,44 +173,9 @@ __global__ __launch_bounds__(SORT_THREADS) void sort_scatter_kernel(const int32_
     }
 }
 
-__global__ void iota_i32_kernel(int32_t *out, int64_t n) {
-    int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = (int32_t)i;
-}
-
 size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
-bool sort_use_rocprim() {
-    static const bool v = [] {
-        const char *e = getenv("RP_SORT");
-        return e && strcmp(e, "rocprim") == 0;
-    }();
-    return v;
-}
-
-hipError_t sort_dispatch(void *temp, size_t &tb, const int32_t *ki, int32_t *ko, const int32_t *vi, int32_t *vo, int64_t n,
-                         int end_bit, hipStream_t s) {
-    return rocprim::radix_sort_pairs<rocprim::default_config>(temp, tb, ki, ko, vi, vo, (size_t)n, 0u, (unsigned)end_bit, s);
-}
-
-// rocPRIM's size query walks its config dispatch and asks the runtime for the device on every call (~0.1 ms of host time)
-int sort_bytes_rocprim(int64_t n, size_t *bytes) {
-    static thread_local int64_t cached_n = -1;
-    static thread_local size_t cached_tb = 0;
-    if (n == cached_n) {
-        *bytes = cached_tb;
-        return RP_OK;
-    }
-    size_t tb = 0;
-    hipError_t e = sort_dispatch(nullptr, tb, nullptr, nullptr, nullptr, nullptr, n, 32, nullptr);
-    if (e != hipSuccess) return rp_fail(RP_ERR_LAUNCH, "sort size query: %s", hipGetErrorString(e));
-    cached_n = n;
-    cached_tb = tb;
-    *bytes = tb;
-    return RP_OK;
-}
-
-// own kernels: [keys n][values n][hist tiles x 512][totals 512]
+// workspace: [keys n][values n][hist tiles x 512][totals 512]
 struct SortPlan {
     int64_t ntiles;
     size_t off_vals, off_hist, off_totals, bytes;
@@ -444,14 +400,7 @@ extern "C" int rp_sort_pairs_fields_i32(void *workspace, size_t workspace_bytes,
 extern "C" int rp_sort_workspace_bytes(int64_t n, size_t *bytes) {
     RP_REQUIRE(bytes && n >= 0 && n < INT32_MAX, "sort_workspace_bytes: bad argument");
     const int64_t m = n > 0 ? n : 1;
-    if (!sort_use_rocprim()) {
-        *bytes = sort_plan(m).bytes + 256;
-        return RP_OK;
-    }
-    size_t tb = 0;
-    int rc = sort_bytes_rocprim(m, &tb);
-    if (rc != RP_OK) return rc;
-    *bytes = align256((size_t)m * sizeof(int32_t)) + align256(tb) + 256;
+    *bytes = sort_plan(m).bytes + 256;
     return RP_OK;
 }
 
@@ -467,20 +416,6 @@ extern "C" int rp_sort_pairs_i32(void *workspace, size_t workspace_bytes, const 
     RP_REQUIRE(workspace_bytes >= need, "sort_pairs: workspace %zu < %zu bytes", workspace_bytes, need);
     hipStream_t s = (hipStream_t)stream;
     char *base = reinterpret_cast<char *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
-
-    if (sort_use_rocprim()) {
-        size_t tb = 0;
-        rc = sort_bytes_rocprim(n, &tb);
-        if (rc != RP_OK) return rc;
-        int32_t *iota = reinterpret_cast<int32_t *>(base);
-        void *temp = base + align256((size_t)n * sizeof(int32_t));
-        hipLaunchKernelGGL(iota_i32_kernel, dim3((unsigned)rp_cdiv(n, 256)), dim3(256), 0, s, iota, n);
-        RP_LAUNCH_CHECK("sort iota");
-        hipError_t e = sort_dispatch(temp, tb, keys_in, keys_out, iota, pos_out, n, end_bit, s);
-        if (e != hipSuccess) return rp_fail(RP_ERR_LAUNCH, "sort_pairs: %s", hipGetErrorString(e));
-        rp_count_launch();
-        return RP_OK;
-    }
 
     const SortPlan p = sort_plan(n);
     int32_t *tmp_k = reinterpret_cast<int32_t *>(base);

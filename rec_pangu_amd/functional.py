@@ -1300,7 +1300,7 @@ _WGRAD_STREAMS: dict = {}
 def _side2_stream(device):
     st = _WGRAD_STREAMS.get(device)
     if st is None:
-        st = _WGRAD_STREAMS[device] = hip.make_side_stream(device, "inline")
+        st = _WGRAD_STREAMS[device] = hip.make_side_stream(device)
     return st
 
 
@@ -1334,8 +1334,7 @@ class _EmbedGatherLinear(torch.autograd.Function):
         need_w = ctx.needs_input_grad[4] or (bias is not None and ctx.needs_input_grad[5])
         B, K, Kg = idx[0].shape[0], weight.shape[1], len(idx) * store.embedding_dim
         wt = None
-        if (need_grad and weight.is_cuda and weight.dtype is torch.float32 and K % 4 != 0 and K > 64
-                and os.environ.get("RP_STAGE_ONCE", "1") != "0"):
+        if need_grad and weight.is_cuda and weight.dtype is torch.float32 and K % 4 != 0 and K > 64:
             # the backward will want W^T (rp_embed_grad_gemm) and this forward wants the aligned copy of W: one launch makes
             # both from one read of W, in front of the forward, and the transpose leaves the backward's critical path
             with torch.no_grad():
@@ -1364,24 +1363,18 @@ class _EmbedGatherLinear(torch.autograd.Function):
             ctx.save_for_backward(keys, ssum, x, h1, weight)
             store._fm_link = None
             return h1, fm
-        # x exists only for the weight gradient; inference stores none.  RP_WGRAD_GATHER=1: the weight gradient gathers the
-        # embedding rows itself (rp_linear_wgrad_gather: the arena does not change between this forward and its backward) and
-        # only the dense columns are stored.  Measured at Criteo shape: forward 0.195 -> 0.139 ms, weight gradient 0.148 ->
-        # 0.248 ms (random 256-byte rows, two per wave-instruction, against a streamed activation): a net loss of 0.015 ms per
-        # step, so it is OFF by default (bit-identical either way: tests/test_hip_kernels.py).
+        # x exists only for the weight gradient; inference stores none.
         # "seg" (round 5, the default where it fits): NO activation is stored at all — the embedding columns of the weight
         # gradient come out of the gather backward itself (rp_embed_grad_seg: one matrix pass per run of equal rows over the
         # table rows it reads anyway), the dense columns from a small weight gradient over xd.  RP_GRAD_SEG=0: the stored x.
         if not need_w:
             x_mode = "none"
-        elif os.environ.get("RP_WGRAD_GATHER", "0") == "1" and hip.linear_wgrad_gather_fits(B, 64, K, Kg):
-            x_mode = "dense"
         elif (need_grad and K > Kg and len(idx) <= 64 and os.environ.get("RP_GRAD_SEG", "1") != "0"
               and store.embedding_dim == 64 and weight.shape[0] == 64):
             x_mode = "seg"
         else:
             x_mode = "full"
-        want_keys = (need_grad or x_mode == "dense") and pre is None
+        want_keys = need_grad and pre is None
         x, h1, fm, ssum, keys = hip.embed_gather_linear_fwd(store.arena, store.row_base, store.row_count, idx, dense, ldx, w16,
                                                             bias, True, need_grad, want_keys, store.err_flag,
                                                             x_mode="dense" if x_mode == "seg" else x_mode)
@@ -1389,7 +1382,7 @@ class _EmbedGatherLinear(torch.autograd.Function):
         ctx.ldx, ctx.x_mode, ctx.Kg, ctx.need_tables = ldx, x_mode, Kg, need_grad
         ctx.presorted = pre if need_grad else None
         if pre is not None:
-            keys = pre.keys if (need_grad or x_mode == "dense") else None
+            keys = pre.keys if need_grad else None
         ctx.save_for_backward(keys, ssum, x, h1, weight)
         store._fm_link = None
         return h1, fm
@@ -1417,8 +1410,6 @@ class _EmbedGatherLinear(torch.autograd.Function):
                 return dw_seg, hip.linear_wgrad(dpre, x, ctx.K - ctx.Kg, dw=dw_seg[:, ctx.Kg:], want_bias=ctx.has_bias)[1]
             if ctx.x_mode == "bf16":   # the activation was stored as bf16 (bf16-storage training)
                 return hip.linear_wgrad_xbf16(dpre, x, ctx.K, want_bias=ctx.has_bias)
-            if ctx.x_mode == "dense":  # x holds the dense columns only: the embedding columns are gathered from the arena
-                return hip.linear_wgrad_gather(dpre, store.arena, keys, ctx.Kg, x, ctx.K, want_bias=ctx.has_bias)
             return hip.linear_wgrad(dpre, x, ctx.K, want_bias=ctx.has_bias)
 
         # The weight gradient (streams x: 0.15 ms at Criteo shape) and the fused gather backward (bound by its random row
@@ -1429,7 +1420,7 @@ class _EmbedGatherLinear(torch.autograd.Function):
         # inline section (plan.side2): the replay issues them on the plan's second side stream, joined after the gather
         # backward; until that join hip.holding() keeps every tensor hip allocates (launches that run BESIDE others: hip.py).
         plan = hip.LaunchPlan
-        in_plan = (wstream is None and need_w and need_t and ctx.x_mode != "dense"
+        in_plan = (wstream is None and need_w and need_t
                    and os.environ.get("RP_WGRAD_OVERLAP", "1") != "0" and plan.is_recording())
 
         def side_wgrad():

@@ -35,10 +35,6 @@ import torch
 from . import hip
 from .models.layers import embedding as _emb
 
-# the run-ahead bound's completion markers: hip.Marker (no system-scope fence at the record) unless RP_STEP_MARKERS=torch
-_TORCH_MARKERS = os.environ.get("RP_STEP_MARKERS", "") == "torch"
-
-
 
 class GraphedTrainStep:
     """step = GraphedTrainStep(model, optimizer); out = step(batch, next_batch) in the training loop.
@@ -56,7 +52,7 @@ class GraphedTrainStep:
     made (the step holds references that long).  A loader that refills a device buffer in place is detected where torch can
     see it — the tensor's data pointer or version counter differs from what was announced — and the batch is then staged
     and re-sorted on the spot (correct, one copy + one sort slower); a refill torch cannot see (a raw kernel writing through
-    data_ptr()) is the caller's responsibility.  RP_PLAN_REBIND=0 restores the staging copy (a snapshot at call time)."""
+    data_ptr()) is the caller's responsibility."""
 
     MAX_IN_FLIGHT = 6
 
@@ -131,7 +127,7 @@ class GraphedTrainStep:
         # arguments that point at those buffers are re-pointed at the batch's own tensors before each replay
         # (rp_plan_bind_inputs / _set_inputs).  `_x_valid[Q]`: static batch Q holds the content of the batch it stands for
         # (false after a step that read the tensors directly); `_held`: the batches of the replays that may still be in flight.
-        self.rebind = os.environ.get("RP_PLAN_REBIND", "1") != "0"
+        self.rebind = True
         self.bind_report = None   # {"sites": {input: argument words}, "interior": derived pointers} of the last capture
         self._bind_sites = [0, 0]
         self._x_valid = [False, False]
@@ -151,21 +147,7 @@ class GraphedTrainStep:
         # stream) alive into the capture, which runs on another stream — that cross-stream dependency breaks the capture
         return {k: (v.detach() if torch.is_tensor(v) else v) for k, v in out.items()}
 
-    # Only with RP_SORT=rocprim: rocPRIM switches to its onesweep radix sort above ~1 M pairs (global digit counters reset
-    # by memset nodes between the passes).  Replayed from a graph WITHOUT device-wide synchronisations in between, that path
-    # ends in memory access faults within a few hundred steps (B = 40960 x 26 fields = 1.06 M pairs: fault; B = 32768 =
-    # 0.85 M pairs: 600 steps clean; B = 65536 with torch.cuda.synchronize() every 50 steps: 1300 steps clean).  The own
-    # radix sort of csrc/sort.hip (the default; kernels only, no memset nodes) replays cleanly at any size — B = 40960 and
-    # B = 65536, 1500 unsynchronised replays each, profiles/microbench/probes/probe_graph6.py — which is what pinned the faults on that path.
-    # (Captured steps remain the tool for SMALL, host-bound batches: at B = 65536 a replay is slower than eager launches.)
-    MAX_PAIRS_ROCPRIM = 900_000
-
     def _alloc(self, batch):
-        n_pairs = sum(batch[c].numel() for c in self.model.embedding_layer.emb_feature)
-        if os.environ.get("RP_SORT") == "rocprim" and n_pairs > self.MAX_PAIRS_ROCPRIM:
-            raise RuntimeError(f"GraphedTrainStep: {n_pairs} (sample, field) pairs per batch — above {self.MAX_PAIRS_ROCPRIM} "
-                               "rocPRIM's row sort takes its onesweep path, which does not survive unsynchronised graph "
-                               "replays on this runtime; unset RP_SORT=rocprim or run batches of this size eagerly")
         self.X = [{k: torch.zeros_like(v) for k, v in batch.items()} for _ in range(2)]
         self._one = torch.ones((), dtype=torch.float32, device=next(iter(batch.values())).device)
         self._drop_clock = torch.zeros((1,), dtype=torch.int64, device=self._one.device)
@@ -529,7 +511,7 @@ class GraphedTrainStep:
         else:
             self.graphs[P].replay()
         seg("replay")
-        ev = self._ev_pool.pop() if self._ev_pool else (torch.cuda.Event() if _TORCH_MARKERS else hip.Marker())
+        ev = self._ev_pool.pop() if self._ev_pool else hip.Marker()
         ev.record()
         self._inflight.append(ev)
         seg("record")

@@ -33,9 +33,6 @@ _SIGNATURES = {
                                              _vp, _vp, _vp, _vp, _vp]),
     "rp_embed_gather_linear_fwd_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp,
                                                   _i64, _vp, _vp, _vp, _vp, _vp]),
-    "rp_linear_wgrad_gather_fits": (C.c_int, [_i64, _i32, _i32, _i32]),
-    "rp_linear_wgrad_gather": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _sz,
-                                         _vp]),
     "rp_sort_workspace_bytes": (C.c_int, [_i64, C.POINTER(_sz)]),
     "rp_sort_pairs_i32": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _i64, _i32, _vp]),
     "rp_sort_pairs_fields_workspace_bytes": (C.c_int, [_i64, _i32, C.POINTER(_sz)]),
@@ -481,8 +478,8 @@ def embed_gather_linear_fits(D: int, F: int, ND: int, hidden: int, ldx: int, W) 
 def embed_gather_linear_fwd(arena, row_base, row_count, idx: List[torch.Tensor], dense: List[torch.Tensor], ldx: int, W, bias,
                             want_fm: bool, want_sum: bool, want_keys: bool, err_flag: torch.Tensor, x_mode: str = "full"):
     """the gather fused with the 64-wide Linear + ReLU that consumes it -> (x, h1 [B, 64], fm, ssum, keys).
-    x_mode: "full" = x [B, ldx] is stored; "dense" = only the dense columns, as xd [B, 64] (the weight gradient gathers the
-    embedding rows itself: linear_wgrad_gather); "none" = nothing is stored (inference)."""
+    x_mode: "full" = x [B, ldx] is stored; "dense" = only the dense columns, as xd [B, 64] (the embedding columns of the
+    weight gradient come from the gather backward: rp_embed_grad_seg); "none" = nothing is stored (inference)."""
     _req(arena, torch.float32, "arena")
     _req(W, torch.float32, "W")
     F, ND = len(idx), len(dense)
@@ -896,28 +893,6 @@ def linear_wgrad_xbf16(dy, x16, K: int, want_bias: bool = True):
     return dw, db
 
 
-def linear_wgrad_gather_fits(M: int, N: int, K: int, Kg: int) -> bool:
-    return bool(lib().rp_linear_wgrad_gather_fits(M, N, K, Kg))
-
-
-def linear_wgrad_gather(dy, arena, keys, Kg: int, xd, K: int, want_bias: bool = True):
-    """dw [N, K] = dy^T @ X with X[:, :Kg] gathered from the arena through `keys` ([F * M] int32, field-major) and
-    X[:, Kg:K] = xd[:, :K - Kg] (rp_linear_wgrad_gather)"""
-    _req(dy, torch.float32, "dy")
-    _req(arena, torch.float32, "arena")
-    _req(keys, torch.int32, "keys")
-    M, N = dy.shape
-    assert keys.numel() == (Kg // 64) * M and arena.shape[1] == 64
-    dw = _new((N, K), torch.float32, dy.device)
-    db = _new((N,), torch.float32, dy.device) if want_bias else None
-    ws, nbytes = _workspace("linear_wgrad", M, N, K, device=dy.device)
-    with _Timed("linear_wgrad_gather", f"{M}x{N}x{K}", 4 * (M * N + M * K + N * K), 2 * M * N * K):
-        _check(lib().rp_linear_wgrad_gather(dy.data_ptr(), _rowmajor(dy, "dy"), arena.data_ptr(), keys.data_ptr(), Kg, _ptr(xd),
-                                            _rowmajor(xd, "xd") if xd is not None else 0, dw.data_ptr(), K, _ptr(db), M, N, K,
-                                            0, ws.data_ptr(), nbytes, _stream()), "rp_linear_wgrad_gather")
-    return dw, db
-
-
 def transpose(w, rows_out: Optional[int] = None):
     """w [R, C] -> [C, R]; with rows_out > C the result has rows_out rows, the extra ones zero (a dgrad GEMM on it
     then writes exact zeros into the padding columns of a padded activation gradient)."""
@@ -1296,22 +1271,15 @@ class LaunchPlan:
 _COPY_PLANS: dict = {}
 
 
-def make_side_stream(device, role: str = "sort") -> "torch.cuda.Stream":
+def make_side_stream(device) -> "torch.cuda.Stream":
     """a stream for work that runs BESIDE the main stream (the next batch's sort, the side work of the first layer's backward):
     of the LOWEST priority the device offers (rp_stream_create_low, wrapped as an ExternalStream), so that the main stream's
     launches are dispatched first — measured in alternating runs on one box: 0.912 / 0.912 -> 0.903 / 0.887 ms per step in the
-    20-step window, 0.879 -> 0.866 over 600 steps.  RP_SIDE_PRIORITY=normal: a plain torch stream (rounds 2-4)"""
-    prio = os.environ.get("RP_SIDE_PRIORITY", "low")
-    if role == "inline":  # (the first layer's side work is waited for by the optimizer; the sort by nothing in its step)
-        prio = os.environ.get("RP_SIDE2_PRIORITY", prio)
-    if prio == "low":
-        with torch.cuda.device(device):
-            h = _vp()
-            _check(lib().rp_stream_create_low(C.byref(h)), "rp_stream_create_low")
-        return torch.cuda.ExternalStream(h.value, device=device)
-    if prio == "high":
-        return torch.cuda.Stream(device=device, priority=-1)
-    return torch.cuda.Stream(device=device)
+    20-step window, 0.879 -> 0.866 over 600 steps."""
+    with torch.cuda.device(device):
+        h = _vp()
+        _check(lib().rp_stream_create_low(C.byref(h)), "rp_stream_create_low")
+    return torch.cuda.ExternalStream(h.value, device=device)
 
 
 def multi_copy(dst: Sequence[torch.Tensor], src: Sequence[torch.Tensor]) -> bool:
@@ -2266,7 +2234,7 @@ def mlp_tail_fwd_bce(hin, Ws, bs, w_out, b_out, addends, label, p_eps: float = 0
     def finish():
         _check(lib().rp_loss_finish(partial.data_ptr(), n_part, weight / M, loss.data_ptr(), _stream()), "rp_loss_finish")
 
-    if LaunchPlan.is_recording() and os.environ.get("RP_TAIL_REDUCE_SIDE", "1") != "0":
+    if LaunchPlan.is_recording():
         LaunchPlan.defer_side(finish)
     else:
         finish()
@@ -2296,7 +2264,7 @@ def mlp_tail_bwd(dz, Ws, acts, w_out, bce=None):
                "rp_mlp_tail_bwd")
 
     with _Timed("mlp_tail_bwd", f"{M}x64x{L}", 4 * M * (64 * (L + 2) + 1), 2 * M * (2 * 64 * 64 * L + 128)):
-        if LaunchPlan.is_recording() and os.environ.get("RP_TAIL_REDUCE_SIDE", "1") != "0":
+        if LaunchPlan.is_recording():
             # a captured step: the second stage (workspace -> grads, ~20 us of latency) reads nothing the following
             # launches write and nobody needs `grads` before the optimizer: it joins the plan's inline section (the second
             # side stream) behind the next launches recorded there, instead of standing between this launch and the first

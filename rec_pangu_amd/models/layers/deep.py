@@ -8,7 +8,6 @@ transposed weight + rp_linear_wgrad.  Dropout runs on rp_dropout_* (training mod
 BatchNorm1d on rp_batchnorm_*; Tanh / Sigmoid / LeakyReLU(0.01) are epilogues of the same launch (round 5), other
 activation modules are applied as they are (counted: hip.note_torch_path).
 """
-import os
 from typing import List, Union
 
 import torch
@@ -83,7 +82,7 @@ class MLP(nn.Module):
         the fused tail ([Linear 64x64 + ReLU] x 1..3 -> Linear 64 -> 1 behind a Linear+ReLU whose ReluLink is `pending`) and
         there are at most 3 other addends: the loss head then rides inside the tail's two launches (Fh.mlp_tail64_bce).
         None otherwise — the caller runs the MLP and the loss separately."""
-        if not x.is_cuda or pending is None or len(addends) > 3 or os.environ.get("RP_TAIL_BCE", "1") == "0":
+        if not x.is_cuda or pending is None or len(addends) > 3:
             return None
         mods = list(self.net)
         if start <= 0 or self._tail64_start(mods, x) != start:

@@ -334,7 +334,7 @@ class EmbeddingLayer(nn.Module):
     # ------------------------------------------------------------------ gradients (HIP path)
     def _attach_grads(self):
         off = 0
-        guard = self._lazy is not None and bool(getattr(self._lazy, "defer", False)) and os.environ.get("RP_GRAD_GUARD", "1") != "0"
+        guard = self._lazy is not None and bool(getattr(self._lazy, "defer", False))
         for p in self._tables():
             r = p.shape[0]
             if p.requires_grad:  # a frozen table (set_weights(trainable=False)) never shows a gradient
@@ -387,19 +387,19 @@ class EmbeddingLayer(nn.Module):
         (first_layer_grad).  tiny / big = False: for a call that form does not cover — its tables fall to the row-sorted form.
         Cached per (row signature, D, B); the switches are read when the record is made.
         TINY (rp_embed_grad_tiny): D = 64; each <= 254 rows, the smallest first while they fit 224 accumulator rows, at most
-        16; RP_GRAD_TINY=0 turns the form off.
-        BIG (round 6, rp_embed_grad_smp: the sample-major form): tables of at least RP_SMP_MIN x B rows, where most runs of the
-        sorted pair list are single pairs; not the tiny ones; < 2^24 rows each; the 16 largest; RP_GRAD_SMP=0 turns it off."""
+        16.
+        BIG (round 6, rp_embed_grad_smp: the sample-major form): tables of at least B rows, where most runs of the sorted pair
+        list are single pairs; not the tiny ones; < 2^24 rows each; the 16 largest; batches of RP_SMP_MIN_BATCH and more."""
         sig = self._rows_sig()
         key = (sig, self.embedding_dim, B, tiny, big)
         cache = self.__dict__.setdefault("_forms_cache", {})
         forms = cache.get(key)
         if forms is not None:
             return forms
-        env, F = os.environ.get, len(sig)
+        F = len(sig)
         fits = self.embedding_dim == 64 and F <= 64
         t = b = None
-        if fits and env("RP_GRAD_TINY", "1") != "0":
+        if fits:
             pick, total = [], 0
             for f in sorted(range(F), key=lambda f: sig[f]):
                 if sig[f] <= 254 and total + sig[f] <= 224 and len(pick) < 16:
@@ -409,10 +409,9 @@ class EmbeddingLayer(nn.Module):
                 t = [(f, sum(sig[:f]), sig[f]) for f in sorted(pick)]
         # (batches below RP_SMP_MIN_BATCH keep round 5's single row-sorted launch: the three-form backward is 16 launches more,
         #  and a b = 8192 step — the per-GPU batch of a strong-scaling run — is bound by launches: 0.50 ms against 0.43)
-        if big and fits and env("RP_GRAD_SMP", "1") != "0" and B >= int(env("RP_SMP_MIN_BATCH", "32768")):
+        if big and fits and B >= int(os.environ.get("RP_SMP_MIN_BATCH", "32768")):
             taken = {x[0] for x in t or ()}
-            need = float(env("RP_SMP_MIN", "1.0")) * B
-            pick = sorted((f for f in range(F) if f not in taken and need <= sig[f] < (1 << 24)), key=lambda f: -sig[f])[:16]
+            pick = sorted((f for f in range(F) if f not in taken and B <= sig[f] < (1 << 24)), key=lambda f: -sig[f])[:16]
             if pick and len(pick) * B < (1 << 24) and sum(sig) < (1 << 31):
                 b = [(f, sum(sig[:f]), sig[f]) for f in sorted(pick)]
         t = t if tiny else None
@@ -420,8 +419,8 @@ class EmbeddingLayer(nn.Module):
         rest = skip != (1 << F) - 1
         # the streaming form (rp_embed_grad_ss) only beside the sample-major one; its unique-row lists are made with the sort
         # unless RP_SS_MARK_AHEAD=0 (then rp_embed_grad_ss makes its own)
-        ss = bool(b) and rest and env("RP_GRAD_SS", "1") != "0"
-        forms = cache[key] = GradForms(t, b, skip, rest, ss, ss and env("RP_SS_MARK_AHEAD", "1") != "0")
+        ss = bool(b) and rest
+        forms = cache[key] = GradForms(t, b, skip, rest, ss, ss and os.environ.get("RP_SS_MARK_AHEAD", "1") != "0")
         return forms
 
     def _mark_sorted(self, look: SortedLookup, force: bool = False) -> None:
@@ -574,7 +573,7 @@ class EmbeddingLayer(nn.Module):
         hit = self.__dict__.get("_glf_cache")
         if hit is not None and hit[0] == key:
             return hit[1]
-        ok = (os.environ.get("RP_GATHER_LINEAR", "1") != "0" and self._arena.is_cuda and D == 64 and linear.out_features == 64 and linear.in_features == d
+        ok = (self._arena.is_cuda and D == 64 and linear.out_features == 64 and linear.in_features == d
               and hip.get_matmul_precision() != "fp32"
               and hip.embed_gather_linear_fits(D, F, n_dense, 64, ldx, Fh._rows16(w)))
         self.__dict__["_glf_cache"] = (key, ok)
@@ -762,11 +761,11 @@ class EmbeddingLayer(nn.Module):
     def _sort_pairs(self, keys, out=None, workspace=None):
         """the (arena row, position) sort of a pair list that covers ALL fields of this layer in order, B pairs each: field
         segment by field segment (rp_sort_pairs_fields_i32: a table of r rows needs log2 r key bits, not the arena's — the same
-        result in 49 instead of 78 field-passes at Criteo shape); RP_SORT_FIELDS=0 / RP_SORT=rocprim: the plain sort"""
+        result in 49 instead of 78 field-passes at Criteo shape); a list that is not F equal segments: the plain sort"""
         from ... import hip
         F = len(self.emb_feature)
         n = keys.numel()
-        if n > 0 and n % F == 0 and os.environ.get("RP_SORT_FIELDS", "1") != "0" and os.environ.get("RP_SORT") != "rocprim":
+        if n > 0 and n % F == 0:
             return hip.sort_pairs_fields(keys, n // F, self._rows_sig(), out=out, workspace=workspace)
         return hip.sort_pairs(keys, end_bit=self._meta()[3], out=out, workspace=workspace)
 

@@ -673,8 +673,7 @@ def make_adam(model, lr, lazy_tables=True, replay=None, defer=None):
     """What RankTrainer.fit uses: fused HIP Adam for a HIP-resident model (lazy dense Adam on the embedding arenas by
     default), torch.optim.Adam on CPU (BASELINE config 0).  Hyper-parameters are the reference's (trainer.py:75).
     replay: how the lazy execution catches a row up — "closed" (default; closed-form replay, <= 1e-6 relative to the
-    serial one per replay, see LazyAdamRows) or "exact" (serial replay, bit-identical to dense execution);
-    the environment variable RP_LAZY_REPLAY overrides the default.
+    serial one per replay, see LazyAdamRows) or "exact" (serial replay, bit-identical to dense execution).
     defer: run a row's real step at its next touch, in the one launch that also replays its skipped steps (identical
     results after a flush — tests/test_hip_deferred_adam.py; one optimizer launch per step on the tables instead of two).
     Table .grad rows then hold gradients that are still waiting after step(), so anything that READS or rewrites table
@@ -685,7 +684,7 @@ def make_adam(model, lr, lazy_tables=True, replay=None, defer=None):
     params = list(model.parameters())
     if params and params[0].is_cuda:
         if replay is None:
-            replay = os.environ.get("RP_LAZY_REPLAY", "closed")
+            replay = "closed"
         if defer is None:
             defer = os.environ.get("RP_ADAM_DEFER", "1") != "0"
         return FusedAdam(params, lr=lr, betas=(0.9, 0.999), eps=1e-08, weight_decay=0, fuse_zero_grad=True,

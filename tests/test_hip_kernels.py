@@ -176,25 +176,6 @@ def test_sort_pairs_fields_equals_the_plain_sort(hip, rows, B):
         assert torch.equal(out[0].cpu(), ref_k) and torch.equal(out[1].cpu(), ref_p.to(torch.int32))
 
 
-def test_sort_pairs_rocprim_path():
-    """RP_SORT=rocprim (read once per process) keeps rocPRIM's radix sort selectable: same results"""
-    import subprocess, sys, os
-    code = (
-        "import torch\n"
-        "from rec_pangu_amd import hip\n"
-        "g = torch.Generator().manual_seed(3)\n"
-        "for n, hi in [(1000, 7), (100001, 1 << 20), (1703936, 33762603)]:\n"
-        "    keys = torch.randint(0, hi, (n,), generator=g, dtype=torch.int32)\n"
-        "    ko, po = hip.sort_pairs(keys.cuda(), end_bit=(hi - 1).bit_length())\n"
-        "    rk, rp = torch.sort(keys, stable=True)\n"
-        "    assert torch.equal(ko.cpu(), rk) and torch.equal(po.cpu(), rp.to(torch.int32))\n"
-        "print('ok')\n")
-    env = dict(os.environ, RP_SORT="rocprim")
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, "-c", code], cwd=root, env=env, capture_output=True, text=True, timeout=300)
-    assert r.returncode == 0 and "ok" in r.stdout, r.stderr[-2000:]
-
-
 @pytest.mark.parametrize("rows,D,B,with_fm,with_dx", [
     ([8, 4, 51, 12, 3], 8, 24, True, True),
     ([3, 4, 10, 5000, 27], 64, 4099, True, True),     # runs of >1000 equal rows: pieces chained across workgroups
@@ -970,40 +951,6 @@ def test_embed_gather_linear_vs_unfused(hip, rows, ND, B, biased):
         assert int(err[0]) != 0
     finally:
         hip.set_matmul_precision("auto")
-
-
-@pytest.mark.parametrize("M,F,ND", [(65536, 26, 13), (4096, 6, 0), (1000, 2, 16), (333, 4, 5)])
-@pytest.mark.parametrize("mode", ["auto", "bf16x6", "bf16x3"])
-def test_linear_wgrad_gather_equals_wgrad_on_the_stored_activation(M, F, ND, mode):
-    """rp_linear_wgrad_gather (the first layer's weight gradient gathering the embedding rows itself, so that the forward
-    need not store them) against rp_linear_wgrad on the materialised [M, F*64 + ND] activation: the same staging, the same
-    split plan, the same summation order — bit-identical, in every bf16 matrix-core mode."""
-    from rec_pangu_amd import hip
-    prev = hip.get_matmul_precision()
-    hip.set_matmul_precision(mode)
-    try:
-        _wgrad_gather_case(hip, M, F, ND)
-    finally:
-        hip.set_matmul_precision(prev)
-
-
-def _wgrad_gather_case(hip, M, F, ND):
-    g = torch.Generator().manual_seed(M + F)
-    R, D, K, Kg = 50000, 64, F * 64 + ND, F * 64
-    arena = torch.randn(R, D, generator=g).to(DEV)
-    keys = torch.randint(0, R, (F * M,), generator=g).to(torch.int32).to(DEV)
-    xd = torch.zeros(M, 64)
-    xd[:, :ND] = torch.rand(M, ND, generator=g)
-    xd = xd.to(DEV)
-    dy = (torch.randn(M, 64, generator=g) * (torch.rand(M, 64, generator=g) < 0.5)).to(DEV)
-    assert hip.linear_wgrad_gather_fits(M, 64, K, Kg) == (F % 2 == 0)
-    ld = (K + 63) // 64 * 64
-    x = torch.zeros(M, ld, device=DEV)
-    x[:, :Kg] = arena[keys.long().view(F, M).t().reshape(-1)].view(M, Kg)
-    x[:, Kg:K] = xd[:, :ND]
-    dw_ref, db_ref = hip.linear_wgrad(dy, x, K)
-    dw, db = hip.linear_wgrad_gather(dy, arena, keys, Kg, xd if ND else None, K)
-    assert torch.equal(dw, dw_ref) and torch.equal(db, db_ref)
 
 
 @pytest.mark.parametrize("rows,B,with_fm,accumulate", [
