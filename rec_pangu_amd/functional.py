@@ -5,7 +5,7 @@ nothing falls back: a missing librecpangu_hip.so raises from hip.lib().
 """
 import contextlib
 import os
-from typing import List, Sequence
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -423,27 +423,86 @@ class CINLink:
         self.dx0 = None
 
 
+class CINForm(NamedTuple):
+    """the kernel family that runs one CIN layer's forward, its gradient of X_0 / X_{k-1} and its weight gradient"""
+    fwd: str
+    bwd_x: str
+    bwd_w: str
+
+
+class CINPlan(NamedTuple):
+    layers: Tuple[CINForm, ...]  # one per layer
+    x0_contiguous: bool          # copy X_0 into 16-byte aligned rows first (the forms are then those of aligned rows)
+
+
+def cin_forms(H: int, units, D: int, precision: Optional[str], rows_aligned: bool, n_outputs: int = 1) -> Optional[CINPlan]:
+    """Which kernels run a CIN of `units` maps per layer over H fields of width D — the ONE place that decides it (the
+    autograd functions below and CompressedInteractionNet._forward_hip execute what it returns).  precision: the
+    matrix-core mode (None: the one in force); rows_aligned: x0.stride(0) % 4 == 0 and x0.data_ptr() % 16 == 0.
+    None: no kernel form, the module composes the CIN from device ops — more than 32 fields, more than one output, or a
+    WIDE middle layer (fed by more than 32 maps) without bf16.  bf16 below: precision is not "fp32" and D in {32, 64}.
+
+      layer   fwd, bwd_x, bwd_w    condition                      launches
+      first   pair, pair, pair     bf16, O <= 128, aligned rows   rp_cin_pair_pieces, rp_cin_pair_fwd; rp_cin_pair_bwd_x; _bwd_w
+              pair, pair, f32      bf16, O <= 128, misaligned     ... but the weight gradient by rp_cin_layer_bwd_w
+              bs, bs, bs           bf16, O > 128, aligned rows    rp_cin_bs_fwd; rp_cin_bs_bwd_x on W + W^T; rp_cin_bs_bwd_w
+              bs, bs, f32          bf16, O > 128, misaligned      ... but the weight gradient by rp_cin_layer_bwd_w
+              f32, f32, f32        no bf16                        rp_cin_layer_fwd; rp_cin_layer_bwd_x; rp_cin_layer_bwd_w
+      middle  chunked (all three)  bf16, aligned rows             per chunk of <= 32 input maps rp_cin_bs_fwd (+ rp_accumulate);
+                                                                  rp_cin_bs_bwd_x for X_0 and for X_{k-1}; rp_cin_bs_bwd_w
+              f32, f32, f32        otherwise (<= 32 input maps)   as the first layer's
+      last    head, last, last     L >= 2, rp_cin_last_fits       rp_cin_head_params_fwd + rp_cin_last_fwd + rp_add_scalars;
+                                                                  rp_cin_last_bwd_x; rp_cin_last_bwd_v, rp_sum_all, _head_params_bwd
+              last, last, last     L == 1, rp_cin_last_fits       rp_cin_last_* on X_{L-1} = X_0, weight-space arithmetic in torch
+              f32_1ch, f32, f32    otherwise (D > 64)             the f32 form with the one output channel V = c . W_L
+
+    (the bf16 operand pieces of bs and chunked come from hip.bf16_pieces, in front of each launch.)  A wide middle layer with
+    misaligned rows sets x0_contiguous, and every layer takes its aligned-rows form.  X_1 .. X_{L-1} are the kernels' own
+    allocations: always aligned.  The one run-time exception: a pair bwd_x whose g_out is not 16-byte aligned runs as bs
+    bwd_x (_CINLayer.backward: _pair_reads)."""
+    L = len(units)
+    bf16 = (hip.get_matmul_precision() if precision is None else precision) != "fp32" and hip.cin_bs_fits(H, H, D)
+    wide = any(u > 32 for u in units[:-2])
+    if H > 32 or n_outputs != 1 or (wide and not bf16):
+        return None
+    aligned, f32, forms = rows_aligned or wide, CINForm("f32", "f32", "f32"), []
+    if L >= 2:
+        x = "pair" if hip.cin_pair_fits(H, units[0], D) else "bs"
+        forms.append(CINForm(x, x, x if aligned else "f32") if bf16 else f32)
+        forms += [CINForm("chunked", "chunked", "chunked") if bf16 and aligned else f32] * (L - 2)
+    if hip.cin_last_fits(H, units[-2] if L >= 2 else H, D):
+        forms.append(CINForm("head" if L >= 2 else "last", "last", "last"))
+    else:
+        forms.append(CINForm("f32_1ch", "f32", "f32"))
+    return CINPlan(tuple(forms), wide and not rows_aligned)
+
+
+def _pair_reads(g_out) -> bool:
+    """rp_cin_pair_bwd_x loads g_out 16 bytes at a time"""
+    return g_out is None or g_out.data_ptr() % 16 == 0
+
+
 class _CINLayer(torch.autograd.Function):
+    """A CIN layer in the pair, bs or f32 form (form.fwd "f32_1ch": f32 with want_out=False); xp None: X_{k-1} = X_0."""
+
     @staticmethod
-    def forward(ctx, x0, xp, W, bias, H: int, M: int, D: int, want_out: bool, link=None):
+    def forward(ctx, x0, xp, W, bias, H: int, M: int, D: int, want_out: bool, form: CINForm, link=None):
         x0 = _unit_inner(x0)
         same = xp is None
         xp_t = x0 if same else _unit_inner(xp)
         W = W.contiguous()
         O = W.shape[0]
-        # first layers (X_{k-1} = X_0, <= 32 fields) run on the bf16 matrix core (rp_cin_bs_*)
-        bs = same and hip.get_matmul_precision() != "fp32" and hip.cin_bs_fits(H, M, D)
         wst = None
-        if bs and hip.cin_pair_fits(H, O, D):  # one GEMM over the H(H+1)/2 pair products
+        if form.fwd == "pair":  # one GEMM over the H(H+1)/2 pair products
             # (both layouts of the pair weights' bf16 pieces from one launch: the backward's is kept — the weights do not
             #  change between this forward and its backward)
             wsp, wst = hip.cin_pair_pieces(W.view(O, H, M), both=True)
             out, pooled = hip.cin_pair_fwd(x0, wsp, bias, H, O, D, want_out, True)
-        elif bs:
+        elif form.fwd == "bs":
             out, pooled = hip.cin_bs_fwd(x0, xp_t, hip.bf16_pieces(W.view(O, H, M)), bias, H, M, O, D, want_out, True)
         else:
             out, pooled = hip.cin_layer_fwd(x0, xp_t, W, bias, H, M, D, want_out, True)
-        ctx.cfg = (H, M, D, same, bias is not None, want_out, bs)
+        ctx.cfg = (H, M, D, same, bias is not None, want_out, form)
         ctx.link = link
         ctx.save_for_backward(x0, None if same else xp_t, W, wst)
         if want_out:
@@ -453,70 +512,61 @@ class _CINLayer(torch.autograd.Function):
     @staticmethod
     def backward(ctx, *grads):
         x0, xp, W, wst = ctx.saved_tensors
-        H, M, D, same, has_bias, want_out, bs = ctx.cfg
+        H, M, D, same, has_bias, want_out, form = ctx.cfg
         g_out, g_pool = (grads if want_out else (None, grads[0]))
         g_out = None if g_out is None else g_out.contiguous()
         g_pool = None if g_pool is None else _unit_inner(g_pool)
         extra = None
         if ctx.link is not None and ctx.link.dx0 is not None:
             extra, ctx.link.dx0 = ctx.link.dx0, None
-        if bs:
-            O = W.shape[0]
+        if form.bwd_x == "f32":
+            dx0, dxp, dW, db = hip.cin_layer_bwd(x0, x0 if same else xp, W, H, M, D, g_out, g_pool, has_bias)
+        else:
+            O, dxp = W.shape[0], None
             W3 = W.view(O, H, M)
             # X_0 enters in both roles: one pass with W[o,h,m] + W[o,m,h] gives its whole gradient
             gp = None if g_pool is None else g_pool.contiguous()  # [B, O] packed (it arrives as a slice of the cat)
-            if hip.cin_pair_fits(H, O, D) and (g_out is None or g_out.data_ptr() % 16 == 0):
+            if form.bwd_x == "pair" and _pair_reads(g_out):
                 # (the last layer's gradient of X_0, parked in the link: this launch adds its own into it)
-                dx0 = hip.cin_pair_bwd_x(x0, wst if wst is not None else hip.cin_pair_pieces(W3, transposed=True), g_out, gp,
-                                         H, O, D, like=x0, into=extra)
+                dx0 = hip.cin_pair_bwd_x(x0, wst, g_out, gp, H, O, D, like=x0, into=extra)
                 extra = None
             else:
                 dx0 = hip.cin_bs_bwd_x(x0, hip.bf16_pieces(W3 + W3.transpose(1, 2)), g_out, gp, H, M, O, D, like=x0)
-            if extra is not None:
-                hip.add_rows_to(extra, dx0[:, :extra.shape[1]])
-            if x0.stride(0) % 4 == 0 and x0.data_ptr() % 16 == 0:
-                if O <= 128:  # symmetric pair form: products formed once, 2.9x fewer matrix-core passes
-                    dW, db = hip.cin_pair_bwd_w(x0, g_out, gp, H, O, D, has_bias)
-                else:
-                    dW, db = hip.cin_bs_bwd_w(x0, x0, g_out, gp, H, M, O, D, has_bias)
-                dW = dW.view_as(W)
-            else:
-                dW, db = hip.cin_layer_bwd_w(x0, x0, W, H, M, D, g_out, g_pool, has_bias)
-            return dx0, None, dW, db, None, None, None, None, None
-        dx0, dxp, dW, db = hip.cin_layer_bwd(x0, x0 if same else xp, W, H, M, D, g_out, g_pool, has_bias)
         if extra is not None:
             hip.add_rows_to(extra, dx0[:, :extra.shape[1]])
-        return dx0, dxp, dW, db, None, None, None, None, None
+        if form.bwd_w == "pair":  # symmetric pair form: products formed once, 2.9x fewer matrix-core passes
+            dW, db = hip.cin_pair_bwd_w(x0, g_out, gp, H, O, D, has_bias)
+        elif form.bwd_w == "bs":
+            dW, db = hip.cin_bs_bwd_w(x0, x0, g_out, gp, H, M, O, D, has_bias)
+        elif form.bwd_x != "f32":  # (misaligned rows; the f32 bwd_x above came with its weight gradient)
+            dW, db = hip.cin_layer_bwd_w(x0, x0, W, H, M, D, g_out, g_pool, has_bias)
+        return dx0, dxp, dW.view_as(W), db, None, None, None, None, None, None
 
 
 class _CINLast(torch.autograd.Function):
-    """The collapsed last CIN layer: p[b] = sum_d sum_{h,m} V[h,m] X_0[b,h,d] X_{L-1}[b,m,d]  (rp_cin_last_*)."""
+    """The collapsed last CIN layer of a one-layer CIN (X_{L-1} = X_0, M = H): p[b] = sum_d sum_{h,m} V[h,m] X_0[b,h,d]
+    X_0[b,m,d]  (rp_cin_last_*)."""
 
     @staticmethod
-    def forward(ctx, x0, xp, V, H: int, M: int, D: int):
+    def forward(ctx, x0, V, H: int, D: int):
         x0 = _unit_inner(x0)
-        same = xp is None
-        xp_t = x0 if same else _unit_inner(xp)
-        vt = torch.zeros((M, 32), dtype=torch.float32, device=x0.device)
-        vt[:, :H] = V.reshape(H, M).t()
-        ctx.cfg = (H, M, D, same)
-        ctx.save_for_backward(x0, None if same else xp_t, vt)
-        return hip.cin_last_fwd(x0, xp_t, vt, H, M, D)
+        vt = torch.zeros((H, 32), dtype=torch.float32, device=x0.device)
+        vt[:, :H] = V.reshape(H, H).t()
+        ctx.cfg = (H, D)
+        ctx.save_for_backward(x0, vt)
+        return hip.cin_last_fwd(x0, x0, vt, H, H, D)
 
     @staticmethod
     def backward(ctx, gp):
-        x0, xp, vt = ctx.saved_tensors
-        H, M, D, same = ctx.cfg
-        dx0, dxp, dV = hip.cin_last_bwd(x0, x0 if same else xp, vt, gp.reshape(-1).contiguous(), H, M, D)
-        if same:  # first layer == last layer: both roles are X_0 (M == H, same row layout)
-            dx0 = dx0 + dxp
-            dxp = None
-        return dx0, dxp, dV.reshape(1, H * M), None, None, None
+        x0, vt = ctx.saved_tensors
+        H, D = ctx.cfg
+        dx0, dxp, dV = hip.cin_last_bwd(x0, x0, vt, gp.reshape(-1).contiguous(), H, H, D)
+        return dx0 + dxp, dV.reshape(1, H * H), None, None  # (both roles are X_0, same row layout)
 
 
-def cin_last(x0, xp, V, H: int, M: int, D: int):
-    """x0 [B, >=H*D], xp [B, M*D] or None (X_{L-1} = X_0), V [1, H*M] -> [B, 1]."""
-    return _CINLast.apply(x0, xp, V, H, M, D)
+def cin_last(x0, V, H: int, D: int):
+    """form "last": x0 [B, >=H*D], V [1, H*H] -> [B, 1]."""
+    return _CINLast.apply(x0, V, H, D)
 
 
 class _CINChunked(torch.autograd.Function):
@@ -571,21 +621,12 @@ class _CINChunked(torch.autograd.Function):
         return dx0, dxp, dW.view(O, H * M), db, None, None, None
 
 
-def cin_middle_fits(H: int, D: int, x0, xp) -> bool:
-    """can a middle CIN layer (any number of input maps) run on the chunked bf16 matrix-core form?"""
-    return (hip.get_matmul_precision() != "fp32" and hip.cin_bs_fits(H, min(32, H), D) and x0.stride(0) % 4 == 0
-            and x0.data_ptr() % 16 == 0 and xp.data_ptr() % 16 == 0)
-
-
-def cin_middle(x0, xp, W, bias, H: int, M: int, D: int):
-    """-> (X_k [B, O, D], pooled [B, O]) of a middle CIN layer on the bf16 matrix core (see _CINChunked)"""
-    return _CINChunked.apply(x0, xp, W, bias, H, M, D)
-
-
-def cin_layer(x0, xp, W, bias, H: int, M: int, D: int, want_out: bool = True, link=None):
-    """(X_k [B, O, D], pooled [B, O]) or pooled alone; link: a CINLink shared with cin_head (the collapsed last layer's
-    gradient of X_0 is added into this layer's inside its backward)"""
-    return _CINLayer.apply(x0, xp, W, bias, H, M, D, want_out, link)
+def cin_layer(x0, xp, W, bias, H: int, M: int, D: int, form: CINForm, want_out: bool = True, link=None):
+    """One CIN layer in the form cin_forms chose: (X_k [B, O, D], pooled [B, O]), or pooled alone.  link: a CINLink shared
+    with cin_head (the collapsed last layer's gradient of X_0 is added into the first layer's inside its backward)"""
+    if form.fwd == "chunked":
+        return _CINChunked.apply(x0, xp, W, bias, H, M, D)
+    return _CINLayer.apply(x0, xp, W, bias, H, M, D, want_out, form, link)
 
 
 class _CINHead(torch.autograd.Function):
@@ -621,8 +662,8 @@ class _CINHead(torch.autograd.Function):
 
 
 def cin_head(x0, xp, WL, bL, c, fcb, H: int, M: int, D: int, link=None):
-    """x0 [B, >= H D], xp = X_{L-1} [B, M D], WL [O, H M], bL [O] or None, c [1, O] (fc.weight's slice for the last layer's
-    pooling), fcb [1] or None -> [B, 1]"""
+    """form "head": x0 [B, >= H D], xp = X_{L-1} [B, M D], WL [O, H M], bL [O] or None, c [1, O] (fc.weight's slice for the
+    last layer's pooling), fcb [1] or None -> [B, 1]"""
     return _CINHead.apply(x0, xp, WL, bL, c, fcb, H, M, D, link)
 
 

@@ -1444,14 +1444,7 @@ def cin_layer_bwd(x0, xp, W, H: int, M: int, D: int, g_out, g_pool, want_bias: b
                                         W.data_ptr(), _ptr(g_out), _ptr(g_pool), ldgp, dx0.data_ptr(),
                                         _rowmajor(dx0, "dx0"), 0, _ptr(dxp), M * D, H, M, O, D, B, _stream()),
                "rp_cin_layer_bwd_x")
-    dW = _new_like(W)
-    db = _new((O,), torch.float32, x0.device) if want_bias else None
-    ws, nbytes = _workspace("cin_layer_bwd_w", B, H, M, O, device=x0.device)
-    with _Timed("cin_layer_bwd_w"):
-        _check(lib().rp_cin_layer_bwd_w(x0.data_ptr(), _rowmajor(x0, "x0"), xp.data_ptr(), _rowmajor(xp, "xp"),
-                                        _ptr(g_out), _ptr(g_pool), ldgp, dW.data_ptr(), _ptr(db), H, M, O, D, B,
-                                        ws.data_ptr(), nbytes, _stream()), "rp_cin_layer_bwd_w")
-    return dx0, dxp, dW, db
+    return (dx0, dxp) + cin_layer_bwd_w(x0, xp, W, H, M, D, g_out, g_pool, want_bias)
 
 
 def field_attention_fits(T: int, Din: int, H: int, a: int, has_res: bool) -> bool:
@@ -1553,34 +1546,6 @@ def cin_bs_bwd_w(x0, xp, g_out, g_pool, H: int, M: int, O: int, D: int, want_bia
 
 def cin_pair_fits(H: int, O: int, D: int) -> bool:
     return bool(lib().rp_cin_pair_fits(H, O, D))
-
-
-def _bf16_split3(full):
-    hi = full.to(torch.bfloat16)
-    r1 = full - hi.float()
-    mid = r1.to(torch.bfloat16)
-    lo = (r1 - mid.float()).to(torch.bfloat16)
-    return torch.stack((hi, mid, lo)).contiguous()
-
-
-def _cin_pair_ws(W3):
-    O, H, _ = W3.shape
-    iu = torch.triu_indices(H, H, device=W3.device)  # row-major upper triangle
-    return W3[:, iu[0], iu[1]] + W3[:, iu[1], iu[0]] * (iu[0] != iu[1]).to(W3.dtype)
-
-
-def cin_pair_pieces_torch(W3, transposed: bool = False):
-    """the torch formulation of cin_pair_pieces (rounds 3-5; kept as the tests' reference for rp_cin_pair_pieces)"""
-    O = W3.shape[0]
-    ws = _cin_pair_ws(W3)
-    npair = ws.shape[1]
-    if transposed:
-        full = _new(((npair + 127) // 128 * 128, 128), torch.float32, W3.device).zero_()
-        full[:npair, :O] = ws.t()
-    else:
-        full = _new((128, (npair + 31) // 32 * 32), torch.float32, W3.device).zero_()
-        full[:O, :npair] = ws
-    return _bf16_split3(full)
 
 
 def cin_pair_pieces(W3, transposed: bool = False, both: bool = False):

