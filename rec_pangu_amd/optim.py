@@ -561,6 +561,11 @@ class FusedAdam(torch.optim.Optimizer):
             lz.device_clock = on
             lz.tabs.t_dev.fill_(lz.t)
 
+    def sync_device_clock(self):
+        """eager steps ran between two replays: bring the device-resident step counters to the host's"""
+        self.set_device_clock(True)
+        self.set_device_clock(False)
+
     def _lr_of(self, lz):
         """the learning rate of the parameter group that owns the tables of this lazy state"""
         for store in self._stores.values():

@@ -696,7 +696,7 @@ class ShardedEmbeddingLayer(nn.Module):
     def route_into(self, X, pin) -> None:
         """Everything of X's lookup that does not depend on the weights — route, id exchange, owner-side sort of the rows
         asked for — into `pin` (library launches + one collective; under a plan recording the collective is a host mark).
-        The results are computed into fresh buffers and moved with ONE launch (rp_multi_copy)."""
+        Every list is written straight into its persistent buffer: no temporary copy of the results, no copy launch."""
         from . import hip
         if pin.capacity != self._capacity:
             raise RuntimeError("route_into: the exchange capacity changed since the buffers were made")

@@ -200,6 +200,50 @@ def test_a_recorded_first_layer_backward_holds_every_block_it_allocates(monkeypa
     _assert_bit_identical(results["eager"], results["graph"])
 
 
+RECORDED_PLAN_SHAPE = [(36, 13, 11, 1), (36, 13, 11, 1)]  # (nodes, side, inline, streams) per static batch
+RECORDED_LAUNCHES = [  # (kernel, section: 0 main stream, 1 side — the next batch's sort —, 2 inline side)
+    ("lazy_cf_table_kernel", 0), ("void lazy_adam_catchup_wave_kernel", 0), ("transpose_kernel", 0),
+    ("void embed_gather_linear_kernel", 0), ("void mlp_tail_fwd_kernel", 0), ("void mlp_tail_bwd_kernel", 0),
+    ("void embed_grad_smp_kernel", 0), ("embed_grad_tiny_partial_kernel", 2), ("embed_grad_tiny_finish_kernel", 2),
+    ("embed_grad_tiny_dw_kernel", 2), ("void embed_segsum_kernel", 0), ("void embed_ss_urows_kernel", 0),
+    ("embed_ss_dw_kernel", 0), ("embed_grad_smp_dw_kernel", 2), ("void embed_grad_reduce_kernel", 2),
+    ("void embed_grad_reduce_kernel", 2), ("void embed_grad_fix_kernel", 2), ("void linear_wgrad_bf16_kernel", 2),
+    ("wgrad_reduce_kernel", 2), ("loss_finish_kernel", 2), ("mlp_tail_reduce_kernel", 2), ("void adam_kernel", 0),
+    ("counters_add_kernel", 0), ("embed_keys_kernel", 1), ("sort_seg_hist_kernel", 1), ("sort_seg_scan_kernel", 1),
+    ("sort_seg_scatter_kernel", 1), ("sort_seg_hist_kernel", 1), ("sort_seg_scan_kernel", 1),
+    ("sort_seg_scatter_kernel", 1), ("embed_grad_smp_count_kernel", 1), ("embed_grad_smp_scan_kernel", 1),
+    ("embed_grad_smp_mark_kernel", 1), ("embed_ss_count_kernel", 1), ("embed_ss_scan_kernel", 1),
+    ("embed_ss_mark_kernel", 1)]
+
+
+def test_the_recorded_step_keeps_its_launch_sequence():
+    """What a capture records is pinned as literals: (nodes, side, inline, streams) of both static batches' plans and the
+    (kernel, section) sequence of the recorded launches — DeepFM D = 64, [64, 64, 64] on _enc(5, [3000, 17, 900, 4, 20000,
+    250]) at B = 384, two eager calls and two captured ones (RP_SMP_MIN_BATCH = 1: conftest).  The literals were recorded by
+    running these very lines on the parent commit of the change that split GraphedTrainStep's capture into pieces."""
+    from rec_pangu_amd.graph_step import GraphedTrainStep
+    from rec_pangu_amd.models.layers.embedding import EmbeddingLayer
+    from rec_pangu_amd.optim import FusedAdam
+    enc = _enc(5, [3000, 17, 900, 4, 20000, 250])
+    batches = _batches(enc, 384, 5, seed=4)
+    try:
+        model = _build("deepfm64", enc)
+        opt = FusedAdam(model.parameters(), lr=1e-3, fuse_zero_grad=True, lazy_tables=True, replay="closed", defer=True)
+        gstep = GraphedTrainStep(model, opt, backend="plan")
+        for i in range(4):
+            gstep(batches[i], batches[i + 1])
+        torch.cuda.synchronize()
+        assert gstep.backend_used == "plan", (gstep.backend_used, gstep.why_not_plan)
+        shape = [(pl.nodes, pl.side, pl.inline, pl.streams) for pl in gstep.plans]
+        launches = [(name.split("<")[0].split("(")[0], section) for name, section in gstep.launch_names()]
+        print("plan shapes:", shape)
+        print("launches:", launches)
+        assert shape == RECORDED_PLAN_SHAPE
+        assert launches == RECORDED_LAUNCHES
+    finally:
+        EmbeddingLayer.unpin_sorts()
+
+
 def test_graphed_step_falls_back_to_eager_for_the_unannounced_and_the_last_batch(backend):
     """a batch that was not announced by the previous call is staged and sorted on the spot; a call without a next batch
     (end of an epoch) runs eagerly; the run continues on the graphs afterwards — all bit-identical to the eager loop"""
@@ -409,6 +453,13 @@ def test_graphed_step_refuses_what_it_cannot_capture():
         torch.cuda.is_current_stream_capturing = real
 
 
+# (force_a2a, ahead) -> (LaunchPlan.seg_tags, which host calls are the replay's own): recorded on the parent commit of the
+# change that split GraphedTrainStep's capture into pieces
+RECORDED_SEGMENTS = {(False, True): ([0, 1, 0, 0], [False, False, True]),
+                     (True, True): ([0, 1, 1, 0, 0, 0, 0], [False, True, False, True, True, True]),
+                     (True, False): ([0, 0, 0, 0, 0], [True, True, True, True])}
+
+
 @pytest.mark.parametrize("force_a2a,ahead", [(False, True), (True, True), (True, False)])
 def test_graphed_step_with_row_sharded_tables_single_rank(force_a2a, ahead, backend, monkeypatch):
     """The captured step WITH its collectives: a DeepFM whose tables are row-sharded under a 1-rank RCCL group — route,
@@ -416,7 +467,8 @@ def test_graphed_step_with_row_sharded_tables_single_rank(force_a2a, ahead, back
     lazy Adam with device-resident counters — against the eager loop on the same batches: every prediction and the final
     weights bit-identical.  Replayed as a hipGraph (round 4: all_to_all_single as graph nodes) and, round 6, as a LAUNCH PLAN
     in segments: the plan is cut at every collective (rp_plan_host_mark) and the replay issues them itself in between —
-    which needs the whole sharded step to consist of library launches (no ATen fill / cast / cat / scale left in it)."""
+    which needs the whole sharded step to consist of library launches (no ATen fill / cast / cat / scale left in it).  The
+    plan's segments and the replay's own calls between them equal RECORDED_SEGMENTS."""
     import copy
     import socket
     import torch.distributed as dist
@@ -471,6 +523,8 @@ def test_graphed_step_with_row_sharded_tables_single_rank(force_a2a, ahead, back
                         assert sum(pl.seg_tags) == (2 if force_a2a else 1) and pl.ahead_stream is not None, pl.seg_tags
                     else:
                         assert sum(pl.seg_tags) == 0 and pl.ahead_stream is None, pl.seg_tags
+                    print("segments:", (force_a2a, ahead), pl.seg_tags, [fn is not None for fn in pl.host_calls])
+                    assert (pl.seg_tags, [fn is not None for fn in pl.host_calls]) == RECORDED_SEGMENTS[force_a2a, ahead]
             results[mode] = (preds, {k: v.clone() for k, v in model.state_dict().items()})
             del gstep
         for a, b in zip(results["eager"][0], results["graph"][0]):
