@@ -594,6 +594,34 @@ int rp_layernorm_bwd(const float *dy, int64_t lddy, float dy_scale, const float 
                      int N_pad, int accumulate, float *dmul, int64_t lddmul, float *dgamma, float *dbeta, int64_t M, int N,
                      void *workspace, size_t workspace_bytes, rp_stream_t stream);
 
+/* ---- AOANet's generalized interaction layer without its outer product (csrc/gin.hip) ------------------------------------------
+ * replaces GeneralizedInteraction.forward of ranking/aoanet.py:107-115, which builds the [B, P F, D, D] outer product of every
+ * (input subspace, field) pair before contracting it.  Factorised, with M[o,h,d] = W[o,h,d] h[o,d]:
+ *     T[b,o,p,h] = sum_d M[o,h,d] bi[b,p,d]     U[b,o,p,h] = sum_f alpha[p F + f, o] x0[b,f,h]     out[b,o,h] = sum_p T U
+ * x0 [B, ldx0] (F D columns used: the embedding block of a wider row buffer), bi [B, ldbi] (P D columns; layer 0: x0 itself,
+ * P = F), W [O, D, D], alpha [P F, O], h [O, D], out [B, ldo] (O D columns written), all fp32, row strides in floats, any
+ * alignment.  Neither T, U nor anything else of size B O P D is written to global memory: the backward rebuilds them from x0,
+ * bi and the parameters, a tile of samples at a time in LDS.  fp32 FMA on the vector ALU: no matrix-core mode applies.
+ *   rp_gin_fits(F, P, O, D)   1 when the kernels cover the shape: D in {8, 16, 20, 32, 64}, 1 <= F, P <= 64, 1 <= O <= 16
+ *                             (every such shape fits a tile of at least one sample in 144 KiB of LDS), else 0; outside it
+ *                             rp_gin_fwd / rp_gin_bwd return RP_ERR_UNSUPPORTED.
+ *   rp_gin_bwd   g = dout [B, lddo]:  dT = g U, dU = g T
+ *                dx0[b,f,h] (+)= sum_{o,p} alpha[pF+f,o] dU     (accumulate != 0: added to what dx0 [B, lddx0] holds)
+ *                dbi[b,p,d]  =  sum_{o,h} M[o,h,d] dT           (dbi [B, lddbi]; NULL only where bi is x0 itself — same
+ *                                                                pointer, stride and P == F — and then ADDED into dx0's rows)
+ *                dalpha[pF+f,o] = sum_{b,h} x0 dU,  dM[o,h,d] = sum_{b,p} dT bi,  dW = dM h,  dh[o,d] = sum_h dM W
+ *                the three batch reductions through per-workgroup partials in `workspace` over a grid-stride walk of the
+ *                sample tiles, summed in a fixed order by a second launch that also forms dW and dh from dM (no atomics:
+ *                bit-identical from run to run).  workspace: rp_gin_bwd_workspace_bytes(F, P, O, D), independent of B. */
+int rp_gin_fits(int F, int P, int O, int D);
+int rp_gin_fwd(const float *x0, int64_t ldx0, const float *bi, int64_t ldbi, const float *W, const float *alpha,
+               const float *h, float *out, int64_t ldo, int F, int P, int O, int D, int64_t B, rp_stream_t stream);
+int rp_gin_bwd_workspace_bytes(int F, int P, int O, int D, size_t *bytes);
+int rp_gin_bwd(const float *dout, int64_t lddo, const float *x0, int64_t ldx0, const float *bi, int64_t ldbi, const float *W,
+               const float *alpha, const float *h, float *dx0, int64_t lddx0, int accumulate, float *dbi, int64_t lddbi,
+               float *dW, float *dalpha, float *dh, int F, int P, int O, int D, int64_t B, void *workspace,
+               size_t workspace_bytes, rp_stream_t stream);
+
 /* ---- the narrow tail of the MLP as one launch each way (layers/deep.py:62-72 with hidden_units [.., 64, 64], output_dim 1:
  * DeepFM's dnn.net.{2,4,6}) --------------------------------------------------------------------------------------------
  *   hin [M, 64] (a ReLU output) -> [Linear 64x64 + ReLU] x n_hidden (1..3) -> Linear 64 -> 1 = logit [M]

@@ -1127,6 +1127,59 @@ def mask_block_stack(x, blocks, parallel: bool):
     return _MaskBlockStack.apply(x, bool(parallel), eps_in, eps_out, *params)
 
 
+class _GINStack(torch.autograd.Function):
+    """AOANet's whole GeneralizedInteractionNet (ranking/aoanet.py:81-115) on one autograd node:
+        B_0 = x0,  B_{i+1} = layer_i(x0, B_i)   with layer_i the factorised contraction of rp_gin_fwd
+    x0 [B, >= F D] with any row stride (the embedding block of the gather's row buffer); params: (W, alpha, h) per layer.
+    Returns B_L [B, O D].  The forward is one launch per layer and keeps the layer outputs ([B, O D] each); T and U are
+    rebuilt inside the backward launches.  x0 feeds every layer (layer 0 twice): those gradients are summed into ONE buffer
+    by the kernel's accumulate flag, in reverse layer order — autograd sees one gradient of x0."""
+
+    @staticmethod
+    def forward(ctx, x0, F: int, D: int, *params):
+        x0 = _unit_inner(x0)
+        nl = len(params) // 3
+        outs, bi = [], x0
+        for i in range(nl):
+            W, alpha, h = params[3 * i:3 * i + 3]
+            bi = hip.gin_fwd(x0, bi, W, alpha, h, F)
+            outs.append(bi)
+        ctx.F, ctx.D, ctx.nl = F, D, nl
+        ctx.save_for_backward(x0, *params, *outs[:-1])
+        return outs[-1]
+
+    @staticmethod
+    def backward(ctx, dout):
+        F, D, nl = ctx.F, ctx.D, ctx.nl
+        saved = ctx.saved_tensors
+        x0, params, outs = saved[0], saved[1:1 + 3 * nl], saved[1 + 3 * nl:]
+        if x0.shape[1] > F * D:  # columns the layers never read: their gradient is zero (the library's own fill)
+            dx0 = hip.zeros(tuple(x0.shape), torch.float32, x0.device)
+        else:
+            dx0 = torch.empty(tuple(x0.shape), dtype=torch.float32, device=x0.device)
+        grads = [None] * (3 * nl)
+        g = _unit_inner(dout)
+        for i in reversed(range(nl)):
+            W, alpha, h = params[3 * i:3 * i + 3]
+            g, dW, dalpha, dh = hip.gin_bwd(g, x0, x0 if i == 0 else outs[i - 1], W, alpha, h, F, dx0,
+                                            accumulate=i < nl - 1, bi_is_x0=i == 0)
+            grads[3 * i:3 * i + 3] = [dW, dalpha, dh]
+        return (dx0 if ctx.needs_input_grad[0] else None, None, None, *grads)
+
+
+def gin_stack(x0_rows, F: int, D: int, layers):
+    """the GeneralizedInteraction modules `layers` (the first over F input subspaces: B_0 in both roles) applied to the rows
+    x0_rows [B, >= F D] (see _GINStack); -> [B, O D] of the last layer.  Every layer must satisfy hip.gin_fits."""
+    params = []
+    for i, l in enumerate(layers):
+        P, O = l.input_subspaces, l.W.shape[0]
+        if (i == 0 and P != F) or l.num_fields != F or l.embedding_dim != D or not hip.gin_fits(F, P, O, D):
+            raise RuntimeError(f"gin_stack: layer {i} (F={l.num_fields}, P={P}, O={O}, D={l.embedding_dim}) over {F} fields of "
+                               f"width {D}: no kernel form (hip.gin_fits)")
+        params += [l.W, l.alpha, l.h]
+    return _GINStack.apply(x0_rows, F, D, *params)
+
+
 class _DiceGate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, xhat, alpha):

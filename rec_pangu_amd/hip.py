@@ -164,6 +164,11 @@ _SIGNATURES = {
     "rp_layernorm_bwd_workspace_bytes": (C.c_int, [_i32, C.POINTER(_sz)]),
     "rp_layernorm_bwd": (C.c_int, [_vp, _i64, _f32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp,
                                    _vp, _i64, _i32, _vp, _sz, _vp]),
+    "rp_gin_fits": (C.c_int, [_i32, _i32, _i32, _i32]),
+    "rp_gin_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _vp]),
+    "rp_gin_bwd_workspace_bytes": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_sz)]),
+    "rp_gin_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp,
+                             _i32, _i32, _i32, _i32, _i64, _vp, _sz, _vp]),
     "rp_dice_gate_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp]),
     "rp_dice_gate_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
     "rp_mlp_tail_fits": (C.c_int, [_i32, _i32, _i64]),
@@ -1898,6 +1903,61 @@ def layernorm_bwd(dy, x, stats, gamma, beta, mul=None, dy_scale: float = 1.0, dx
                                       dgamma.data_ptr(), dbeta.data_ptr(), M, N, ws.data_ptr(), nbytes, _stream()),
                "rp_layernorm_bwd")
     return dx, dmul, dgamma, dbeta
+
+
+def gin_fits(F: int, P: int, O: int, D: int) -> bool:
+    """do rp_gin_fwd / rp_gin_bwd cover a generalized interaction layer over F fields, P input and O output subspaces of
+    width D?  (rp_gin_fits: D in {8, 16, 20, 32, 64}, F and P up to 64, O up to 16)"""
+    return bool(lib().rp_gin_fits(F, P, O, D))
+
+
+def _gin_dims(x0, bi, W, alpha, h, F: int):
+    O, D = W.shape[0], W.shape[1]
+    P = alpha.shape[0] // F
+    if W.shape != (O, D, D) or alpha.shape != (P * F, O) or h.numel() != O * D or x0.shape[1] < F * D or bi.shape[1] < P * D \
+            or bi.shape[0] != x0.shape[0]:
+        raise RuntimeError(f"gin: x0 {tuple(x0.shape)} / bi {tuple(bi.shape)} / W {tuple(W.shape)} / alpha {tuple(alpha.shape)} "
+                           f"/ h {tuple(h.shape)} over {F} fields")
+    for t, name in ((x0, "x0"), (bi, "bi"), (W, "W"), (alpha, "alpha"), (h, "h")):
+        _req(t, torch.float32, name)
+    for t, name in ((W, "W"), (alpha, "alpha"), (h, "h")):
+        if not t.is_contiguous():
+            raise RuntimeError(f"gin: {name} must be contiguous")
+    return P, O, D
+
+
+def gin_fwd(x0, bi, W, alpha, h, F: int):
+    """-> out [B, O D] of one generalized interaction layer (rp_gin_fwd): x0 [B, >= F D] and bi [B, >= P D] with any row
+    strides, W [O, D, D], alpha [P F, O], h [O, D, 1]"""
+    P, O, D = _gin_dims(x0, bi, W, alpha, h, F)
+    B = x0.shape[0]
+    out = _new((B, O * D), torch.float32, x0.device)
+    with _Timed("gin_fwd", f"{B}x{F}.{P}.{O}.{D}", 4 * B * (F * D + P * D + O * D), 2 * B * O * P * D * (D + F + 1)):
+        _check(lib().rp_gin_fwd(x0.data_ptr(), _rowmajor(x0, "x0"), bi.data_ptr(), _rowmajor(bi, "bi"), W.data_ptr(),
+                                alpha.data_ptr(), h.data_ptr(), out.data_ptr(), O * D, F, P, O, D, B, _stream()), "rp_gin_fwd")
+    return out
+
+
+def gin_bwd(dout, x0, bi, W, alpha, h, F: int, dx0, accumulate: bool, bi_is_x0: bool = False):
+    """-> (dbi, dW, dalpha, dh) of gin_fwd for the incoming dout [B, >= O D]; the gradient of x0 is written (accumulate: added)
+    into the given dx0 [B, >= F D].  bi_is_x0 (layer 0: bi is the very tensor x0): bi's gradient joins dx0 and dbi is None."""
+    P, O, D = _gin_dims(x0, bi, W, alpha, h, F)
+    _req(dout, torch.float32, "dout")
+    _req(dx0, torch.float32, "dx0")
+    B, dev = x0.shape[0], x0.device
+    if dout.shape[0] != B or dout.shape[1] < O * D or dx0.shape[0] != B or dx0.shape[1] < F * D:
+        raise RuntimeError(f"gin_bwd: dout {tuple(dout.shape)} / dx0 {tuple(dx0.shape)} for B = {B}, O D = {O * D}, F D = {F * D}")
+    dbi = None if bi_is_x0 else _new((B, P * D), torch.float32, dev)
+    dW, dalpha, dh = _new_like(W), _new_like(alpha), _new_like(h)
+    ws, nbytes = _workspace("gin_bwd", F, P, O, D, device=dev)
+    with _Timed("gin_bwd", f"{B}x{F}.{P}.{O}.{D}", 4 * B * (2 * F * D + 2 * P * D + O * D + bool(accumulate) * F * D),
+                2 * B * O * P * D * (3 * D + 3 * F + 2)):
+        _check(lib().rp_gin_bwd(dout.data_ptr(), _rowmajor(dout, "dout"), x0.data_ptr(), _rowmajor(x0, "x0"), bi.data_ptr(),
+                                _rowmajor(bi, "bi"), W.data_ptr(), alpha.data_ptr(), h.data_ptr(), dx0.data_ptr(),
+                                _rowmajor(dx0, "dx0"), int(accumulate), _ptr(dbi), P * D if dbi is not None else 0,
+                                dW.data_ptr(), dalpha.data_ptr(), dh.data_ptr(), F, P, O, D, B, ws.data_ptr(), nbytes,
+                                _stream()), "rp_gin_bwd")
+    return dbi, dW, dalpha, dh
 
 
 def dice_gate_fwd(x, xhat, alpha):

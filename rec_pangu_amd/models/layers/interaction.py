@@ -1,6 +1,7 @@
 """Feature-interaction blocks of the hot path — drop-ins for rec_pangu/models/layers/interaction.py:
 InnerProductLayer (:12-52, the two pooling outputs the ranking models use), FM_Layer (:225-235),
-CrossInteractionLayer / CrossNet (:119-141), CompressedInteractionNet (:144-171), MaskBlock (:254-283).
+CrossInteractionLayer / CrossNet (:119-141), CompressedInteractionNet (:144-171), MaskBlock (:254-283); GeneralizedInteractionNet / GeneralizedInteraction, which the
+reference keeps beside its model (ranking/aoanet.py:81-115).
 Parameter names/shapes follow the reference so its checkpoints load.
 """
 import torch
@@ -219,3 +220,64 @@ class MaskBlock(nn.Module):
             return Fh.layer_norm(hidden, self._layer_norm).reshape(*lead, -1)
         masked = self._input_layer_norm(net) * self._mask_layer(mask_input)
         return self._layer_norm(self._hidden_layer(masked))
+
+
+class GeneralizedInteraction(nn.Module):
+    """One layer of AOANet's generalized interaction net (ranking/aoanet.py:97-115): B_0 [B, F, D] against B_i [B, P, D]
+    (P = input_subspaces) -> [B, O, D].  The reference builds the outer product of every (subspace, field) pair —
+    [B, P F, D, D] — and then contracts it with alpha, W and h; the same result factorises, with M[o,h,d] = W[o,h,d] h[o,d]:
+        T[b,o,p,h] = sum_d M[o,h,d] B_i[b,p,d]    U[b,o,p,h] = sum_f alpha[p F + f, o] B_0[b,f,h]    out[b,o,h] = sum_p T U
+    (the alpha row is p F + f: the reference's repeat / view pair).  forward() computes that form; on a HIP device the whole
+    net runs as functional.gin_stack (rp_gin_fwd / rp_gin_bwd), this module alone composes it from device ops (counted)."""
+
+    def __init__(self, input_subspaces, output_subspaces, num_fields, embedding_dim):
+        super(GeneralizedInteraction, self).__init__()
+        self.input_subspaces = input_subspaces
+        self.num_fields = num_fields
+        self.embedding_dim = embedding_dim
+        self.W = nn.Parameter(torch.eye(embedding_dim, embedding_dim).unsqueeze(0).repeat(output_subspaces, 1, 1))
+        self.alpha = nn.Parameter(torch.ones(input_subspaces * num_fields, output_subspaces))
+        self.h = nn.Parameter(torch.ones(output_subspaces, embedding_dim, 1))
+
+    def factorised(self, B_0, B_i):
+        M = self.W * self.h.squeeze(-1).unsqueeze(1)
+        T = torch.einsum("ohd,bpd->boph", M, B_i)
+        U = torch.einsum("pfo,bfh->boph", self.alpha.view(self.input_subspaces, self.num_fields, -1), B_0)
+        return (T * U).sum(dim=2)
+
+    def forward(self, B_0, B_i):
+        if B_0.is_cuda:
+            from ... import hip
+            hip.note_torch_path("GeneralizedInteraction called on its own (the kernels run the whole net: "
+                                "GeneralizedInteractionNet / functional.gin_stack)")
+        return self.factorised(B_0, B_i)
+
+
+class GeneralizedInteractionNet(nn.Module):
+    """B_{i+1} = layer_i(B_0, B_i), B_0 = the field embeddings (ranking/aoanet.py:81-94); layer 0 has F input subspaces, the
+    others num_subspaces.  On a HIP device the stack is one autograd node, one launch per layer each way
+    (functional.gin_stack).  B_0 is [B, F, D] and the result [B, O, D], as in the reference."""
+
+    def __init__(self, num_layers, num_subspaces, num_fields, embedding_dim):
+        super(GeneralizedInteractionNet, self).__init__()
+        self.num_fields, self.embedding_dim = num_fields, embedding_dim
+        self.layers = nn.ModuleList([GeneralizedInteraction(num_fields if i == 0 else num_subspaces, num_subspaces,
+                                                            num_fields, embedding_dim) for i in range(num_layers)])
+
+    def hip_supported(self) -> bool:
+        from ... import hip
+        return len(self.layers) > 0 and all(hip.gin_fits(l.num_fields, l.input_subspaces, l.W.shape[0], l.embedding_dim)
+                                            for l in self.layers)
+
+    def forward(self, B_0):
+        F, D = self.num_fields, self.embedding_dim
+        if B_0.is_cuda and B_0.dtype == torch.float32 and len(self.layers) > 0:
+            from ... import functional as Fh, hip
+            if self.hip_supported():
+                return Fh.gin_stack(B_0.reshape(B_0.shape[0], F * D), F, D, self.layers).view(B_0.shape[0], -1, D)
+            hip.note_torch_path(f"GeneralizedInteractionNet over {F} fields, D={D}, {self.layers[0].W.shape[0]} subspaces "
+                                "(outside hip.gin_fits)")
+        B_i = B_0
+        for layer in self.layers:
+            B_i = layer.factorised(B_0, B_i)
+        return B_i

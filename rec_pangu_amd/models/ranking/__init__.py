@@ -7,5 +7,6 @@ from .wdl import WDL
 from .nfm import NFM
 from .lr import LR
 from .masknet import MaskNet
+from .aoanet import AOANet
 
-__all__ = ["DeepFM", "xDeepFM", "DCN", "AutoInt", "FM", "WDL", "NFM", "LR", "MaskNet"]
+__all__ = ["DeepFM", "xDeepFM", "DCN", "AutoInt", "FM", "WDL", "NFM", "LR", "MaskNet", "AOANet"]
