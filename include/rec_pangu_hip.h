@@ -622,6 +622,35 @@ int rp_gin_bwd(const float *dout, int64_t lddo, const float *x0, int64_t ldx0, c
                float *dW, float *dalpha, float *dh, int F, int P, int O, int D, int64_t B, void *workspace,
                size_t workspace_bytes, rp_stream_t stream);
 
+/* ---- CCPM's conv + k-max-pooling + tanh stack as one launch each way (csrc/ccpm.hip) --------------------------------------------
+ * replaces CCPM_ConvLayer.forward of ranking/ccpm.py:77-107: per layer l (C_in -> C_out channels, kernel (kh, 1), pooling size k)
+ *     y[b,co,p,d] = bias[co] + sum_{ci,j} W[co,ci,j] xpad[b,ci,p+j,d]      (kh - 1 zero rows on either side: L_out = L_in + kh - 1)
+ *     a[b,co,:,d] = tanh(the k largest of y[b,co,:,d], in their original order)              (L_in of the next layer = k)
+ * No step mixes two embedding columns, so one thread runs the whole stack for one (b, d), its activations in LDS; nothing of
+ * size B C L D is written to global memory, and the forward saves nothing but its output.  fp32 FMA on the vector ALU.
+ * Selection: position i is kept iff #{j : y_j > y_i or (y_j == y_i and j < i)} < k — exact ties go to the LOWER index (torch's
+ * topk leaves its tie order unspecified: the two may differ on exact ties, and only there).
+ * x [B, ldx] (F D columns used, read in place: the embedding block of a wider row buffer), W[l] [C_out, C_in, kh(, 1)] and
+ * bias[l] [C_out] contiguous, out [B, ldo] (C_last k_last D columns written, index c (k_last D) + j D + d: the reference's
+ * flatten(conv_out, 1)), all fp32, row strides in floats, any alignment.  W / bias / dW / db: HOST arrays of n_layers device
+ * pointers, channels / heights / ks: HOST arrays of n_layers ints (C_out, kh, k per layer); all are copied into the launch.
+ *   rp_ccpm_fits   1 when the kernels cover the stack: 1 <= n_layers <= 3, every C_out in 1..4, kh in 1..8, 1 <= F <= 64,
+ *                  1 <= D <= 65536, every L_out <= 64 and k in 1..L_out (L_out < k, where the reference's topk raises, is
+ *                  refused), and the per-wave working set of either direction within 144 KiB of LDS; else 0, and
+ *                  rp_ccpm_fwd / rp_ccpm_bwd return RP_ERR_UNSUPPORTED.
+ *   rp_ccpm_bwd    from dout [B, lddo] and x alone (the forward and its selections are rebuilt per column): dx [B, lddx] (F D
+ *                  columns written), dW[l], db[l].  The parameter gradients go through one partial per workgroup (at most 512
+ *                  workgroups of 64 columns, walking the B D columns with the stride of the grid), summed in workgroup order by a
+ *                  finishing launch: no floating-point atomics, bit-identical from run to run.
+ *                  workspace: rp_ccpm_bwd_workspace_bytes(n_layers, channels, heights), independent of B. */
+int rp_ccpm_fits(int F, int D, int n_layers, const int *channels, const int *heights, const int *ks);
+int rp_ccpm_fwd(const float *x, int64_t ldx, const float *const *W, const float *const *bias, float *out, int64_t ldo, int F,
+                int D, int n_layers, const int *channels, const int *heights, const int *ks, int64_t B, rp_stream_t stream);
+int rp_ccpm_bwd_workspace_bytes(int n_layers, const int *channels, const int *heights, size_t *bytes);
+int rp_ccpm_bwd(const float *dout, int64_t lddo, const float *x, int64_t ldx, const float *const *W, const float *const *bias,
+                float *dx, int64_t lddx, float *const *dW, float *const *db, int F, int D, int n_layers, const int *channels,
+                const int *heights, const int *ks, int64_t B, void *workspace, size_t workspace_bytes, rp_stream_t stream);
+
 /* ---- the narrow tail of the MLP as one launch each way (layers/deep.py:62-72 with hidden_units [.., 64, 64], output_dim 1:
  * DeepFM's dnn.net.{2,4,6}) --------------------------------------------------------------------------------------------
  *   hin [M, 64] (a ReLU output) -> [Linear 64x64 + ReLU] x n_hidden (1..3) -> Linear 64 -> 1 = logit [M]

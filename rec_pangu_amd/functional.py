@@ -1180,6 +1180,45 @@ def gin_stack(x0_rows, F: int, D: int, layers):
     return _GINStack.apply(x0_rows, F, D, *params)
 
 
+class _CCPMStack(torch.autograd.Function):
+    """CCPM's whole conv stack (ranking/ccpm.py:77-107: [ZeroPad2d -> Conv2d (kh, 1) -> KMaxPooling -> Tanh] x L) on one
+    autograd node, one launch each way.  x [B, >= F D] with any row stride (the gather's row buffer, read in place); params:
+    every layer's conv weight, then every bias.  Returns [B, C_last k_last D] laid out as flatten(conv_out, 1).  Nothing but
+    x and the parameters is saved: rp_ccpm_bwd rebuilds the activations and the selections per column."""
+
+    @staticmethod
+    def forward(ctx, x, F: int, D: int, ks, *params):
+        x = _unit_inner(x)
+        nl = len(params) // 2
+        weights, biases = [w.contiguous() for w in params[:nl]], list(params[nl:])
+        ctx.F, ctx.D, ctx.ks, ctx.nl = F, D, ks, nl
+        ctx.save_for_backward(x, *weights, *biases)
+        return hip.ccpm_fwd(x, weights, biases, F, D, ks)
+
+    @staticmethod
+    def backward(ctx, dout):
+        F, D, nl = ctx.F, ctx.D, ctx.nl
+        saved = ctx.saved_tensors
+        x, weights, biases = saved[0], list(saved[1:1 + nl]), list(saved[1 + nl:])
+        if x.shape[1] > F * D:  # columns the stack never reads: their gradient is zero (the library's own fill)
+            dx = hip.zeros(tuple(x.shape), torch.float32, x.device)
+        else:
+            dx = None
+        dx, dWs, dbs = hip.ccpm_bwd(_unit_inner(dout), x, weights, biases, F, D, ctx.ks, dx=dx)
+        return (dx if ctx.needs_input_grad[0] else None, None, None, None, *dWs, *dbs)
+
+
+def ccpm_conv_stack(rows, F: int, D: int, conv_layer):
+    """the CCPM_ConvLayer `conv_layer` applied to the rows [B, >= F D] (see _CCPMStack) -> [B, C_last k_last D].  The stack
+    must satisfy hip.ccpm_fits (conv_layer.hip_supported)."""
+    convs, ks = conv_layer.convs(), tuple(conv_layer.ks)
+    channels, heights = [c.out_channels for c in convs], [c.kernel_size[0] for c in convs]
+    if conv_layer.num_fields != F or not hip.ccpm_fits(F, D, channels, heights, ks):
+        raise RuntimeError(f"ccpm_conv_stack: channels {channels}, heights {heights}, ks {list(ks)} over {F} fields of width "
+                           f"{D}: no kernel form (hip.ccpm_fits)")
+    return _CCPMStack.apply(rows, F, D, ks, *[c.weight for c in convs], *[c.bias for c in convs])
+
+
 class _DiceGate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, xhat, alpha):

@@ -22,6 +22,7 @@ ACT_NONE, ACT_RELU, ACT_MASK, ACT_TANH, ACT_SIGMOID, ACT_LEAKY = 0, 1, 2, 3, 4, 
 _lib = None
 
 _i64, _i32, _f32, _vp, _sz = C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_size_t
+_ip = C.POINTER(C.c_int)  # a host array of ints the library copies into its launch
 _f64 = C.c_double
 _SIGNATURES = {
     "rp_version": (C.c_int, []),
@@ -169,6 +170,11 @@ _SIGNATURES = {
     "rp_gin_bwd_workspace_bytes": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_sz)]),
     "rp_gin_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp,
                              _i32, _i32, _i32, _i32, _i64, _vp, _sz, _vp]),
+    "rp_ccpm_fits": (C.c_int, [_i32, _i32, _i32, _ip, _ip, _ip]),
+    "rp_ccpm_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _ip, _ip, _ip, _i64, _vp]),
+    "rp_ccpm_bwd_workspace_bytes": (C.c_int, [_i32, _ip, _ip, C.POINTER(_sz)]),
+    "rp_ccpm_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _ip, _ip, _ip, _i64, _vp,
+                              _sz, _vp]),
     "rp_dice_gate_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp]),
     "rp_dice_gate_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
     "rp_mlp_tail_fits": (C.c_int, [_i32, _i32, _i64]),
@@ -1958,6 +1964,106 @@ def gin_bwd(dout, x0, bi, W, alpha, h, F: int, dx0, accumulate: bool, bi_is_x0: 
                                 dW.data_ptr(), dalpha.data_ptr(), dh.data_ptr(), F, P, O, D, B, ws.data_ptr(), nbytes,
                                 _stream()), "rp_gin_bwd")
     return dbi, dW, dalpha, dh
+
+
+def _ccpm_ints(vals):
+    return (C.c_int * max(len(vals), 1))(*[int(v) for v in vals])
+
+
+def ccpm_fits(F: int, D: int, channels, heights, ks) -> bool:
+    """do rp_ccpm_fwd / rp_ccpm_bwd cover a CCPM conv stack over F fields of width D with these output channels, kernel
+    heights and pooling sizes per layer?  (rp_ccpm_fits: 1 to 3 layers, channels 1..4, heights 1..8, F <= 64, D <= 65536,
+    every conv line L_out = L_in + kh - 1 <= 64 with 1 <= k <= L_out — L_out < k, where the reference's topk raises, is
+    refused — and the working set of a wave within 144 KiB of LDS)"""
+    n = len(channels)
+    if n == 0 or len(heights) != n or len(ks) != n:
+        return False
+    return bool(lib().rp_ccpm_fits(int(F), int(D), n, _ccpm_ints(channels), _ccpm_ints(heights), _ccpm_ints(ks)))
+
+
+def _ccpm_dims(x, weights, biases, F: int, D: int, ks):
+    """the checks that need no GPU (shapes, dtypes, contiguity, widths, the range), then the device check; -> channels,
+    heights"""
+    n = len(weights)
+    if n == 0 or len(biases) != n or len(ks) != n:
+        raise RuntimeError(f"ccpm: {n} weights / {len(biases)} biases / {len(ks)} pooling sizes")
+    channels, heights, cin = [], [], 1
+    for l, (w, b) in enumerate(zip(weights, biases)):
+        if w.dim() not in (3, 4) or w.shape[1] != cin or (w.dim() == 4 and w.shape[3] != 1) or b.shape != (w.shape[0],):
+            raise RuntimeError(f"ccpm: layer {l}: weight {tuple(w.shape)} / bias {tuple(b.shape)} over {cin} input channels "
+                               "(need [C_out, C_in, kh, 1] and [C_out])")
+        for t, name in ((w, "weight"), (b, "bias")):
+            if t.dtype != torch.float32:
+                raise RuntimeError(f"ccpm: layer {l} {name}: expected torch.float32, got {t.dtype}")
+            if not t.is_contiguous():
+                raise RuntimeError(f"ccpm: layer {l} {name} must be contiguous")
+        channels.append(w.shape[0])
+        heights.append(w.shape[2])
+        cin = w.shape[0]
+    if x.dtype != torch.float32:
+        raise RuntimeError(f"ccpm: x: expected torch.float32, got {x.dtype}")
+    if x.dim() != 2 or x.shape[1] < F * D or (x.shape[0] > 1 and x.stride(0) < F * D):
+        raise RuntimeError(f"ccpm: x {tuple(x.shape)} / strides {x.stride()}: rows narrower than F D = {F * D}")
+    lin = F
+    for l, (kh, k) in enumerate(zip(heights, ks)):
+        if lin + kh - 1 < k:
+            raise RuntimeError(f"ccpm: layer {l}: L_out = {lin} + {kh} - 1 < k = {k} (topk would raise)")
+        lin = k
+    if not ccpm_fits(F, D, channels, heights, ks):
+        raise RuntimeError(f"ccpm: F={F} D={D} channels={channels} heights={heights} ks={list(ks)}: outside rp_ccpm_fits")
+    _req(x, torch.float32, "x")
+    for t in list(weights) + list(biases):
+        _req(t, torch.float32, "ccpm parameter")
+    return channels, heights
+
+
+def _ccpm_cost(B, F, D, channels, heights, ks):
+    """(bytes, flops) of the forward: x in, the last layer out; 2 flops per conv FMA"""
+    lin, cin, fma = F, 1, 0
+    for co, kh, k in zip(channels, heights, ks):
+        fma += co * cin * kh * (lin + kh - 1)
+        lin, cin = k, co
+    return 4 * B * D * (F + channels[-1] * ks[-1]), 2 * B * D * fma
+
+
+def ccpm_fwd(x, weights, biases, F: int, D: int, ks):
+    """-> out [B, C_last k_last D] of the whole CCPM conv stack in one launch (rp_ccpm_fwd): x [B, >= F D] with any row
+    stride, weights[l] [C_out, C_in, kh, 1], biases[l] [C_out], ks[l] the pooling size of layer l"""
+    channels, heights = _ccpm_dims(x, weights, biases, F, D, ks)
+    B, n = x.shape[0], len(weights)
+    width = channels[-1] * int(ks[-1]) * D
+    out = _new((B, width), torch.float32, x.device)
+    nbytes, flops = _ccpm_cost(B, F, D, channels, heights, ks)
+    with _Timed("ccpm_fwd", f"{B}x{F}.{D}", nbytes, flops):
+        _check(lib().rp_ccpm_fwd(x.data_ptr(), _rowmajor(x, "x"), _ptr_array(weights), _ptr_array(biases), out.data_ptr(),
+                                 width, F, D, n, _ccpm_ints(channels), _ccpm_ints(heights), _ccpm_ints(ks), B, _stream()),
+               "rp_ccpm_fwd")
+    return out
+
+
+def ccpm_bwd(dout, x, weights, biases, F: int, D: int, ks, dx=None):
+    """-> (dx, dWs, dbs) of ccpm_fwd for the incoming dout [B, >= C_last k_last D], rebuilt from x alone (rp_ccpm_bwd).  dx: a
+    [B, >= F D] buffer to write the first F D columns of (the others are left alone); a fresh [B, F D] one otherwise."""
+    channels, heights = _ccpm_dims(x, weights, biases, F, D, ks)
+    B, n, dev = x.shape[0], len(weights), x.device
+    width = channels[-1] * int(ks[-1]) * D
+    if dout.dtype != torch.float32 or dout.dim() != 2 or dout.shape[0] != B or dout.shape[1] < width:
+        raise RuntimeError(f"ccpm_bwd: dout {tuple(dout.shape)} {dout.dtype} for B = {B}, width {width}")
+    _req(dout, torch.float32, "dout")
+    if dx is None:
+        dx = _new((B, F * D), torch.float32, dev)
+    _req(dx, torch.float32, "dx")
+    if dx.dim() != 2 or dx.shape[0] != B or dx.shape[1] < F * D:
+        raise RuntimeError(f"ccpm_bwd: dx {tuple(dx.shape)} for B = {B}, F D = {F * D}")
+    dWs, dbs = [_new_like(w) for w in weights], [_new_like(b) for b in biases]
+    ws, wbytes = _workspace("ccpm_bwd", n, _ccpm_ints(channels), _ccpm_ints(heights), device=dev)
+    nbytes, flops = _ccpm_cost(B, F, D, channels, heights, ks)
+    with _Timed("ccpm_bwd", f"{B}x{F}.{D}", nbytes + 4 * B * D * 2 * F, 4 * flops):
+        _check(lib().rp_ccpm_bwd(dout.data_ptr(), _rowmajor(dout, "dout"), x.data_ptr(), _rowmajor(x, "x"), _ptr_array(weights),
+                                 _ptr_array(biases), dx.data_ptr(), _rowmajor(dx, "dx"), _ptr_array(dWs), _ptr_array(dbs), F, D,
+                                 n, _ccpm_ints(channels), _ccpm_ints(heights), _ccpm_ints(ks), B, ws.data_ptr(), wbytes,
+                                 _stream()), "rp_ccpm_bwd")
+    return dx, dWs, dbs
 
 
 def dice_gate_fwd(x, xhat, alpha):

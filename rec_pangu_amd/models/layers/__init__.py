@@ -6,9 +6,9 @@ from .interaction import (InnerProductLayer, FM_Layer, CrossInteractionLayer, Cr
                           CompressedInteractionNet, MaskBlock, GeneralizedInteractionNet,
                           GeneralizedInteraction)
 from .attention import ScaledDotProductAttention, MultiHeadAttention, MultiHeadSelfAttention
-from .sequence import MaskedAveragePooling, MaskedSumPooling
+from .sequence import MaskedAveragePooling, MaskedSumPooling, KMaxPooling
 
 __all__ = ["Dice", "get_activation", "EmbeddingLayer", "MLP", "LR_Layer", "InnerProductLayer", "FM_Layer",
            "CrossInteractionLayer", "CrossNet", "CompressedInteractionNet", "MaskBlock", "GeneralizedInteractionNet",
            "GeneralizedInteraction", "ScaledDotProductAttention",
-           "MultiHeadAttention", "MultiHeadSelfAttention", "MaskedAveragePooling", "MaskedSumPooling"]
+           "MultiHeadAttention", "MultiHeadSelfAttention", "MaskedAveragePooling", "MaskedSumPooling", "KMaxPooling"]

@@ -8,5 +8,6 @@ from .nfm import NFM
 from .lr import LR
 from .masknet import MaskNet
 from .aoanet import AOANet
+from .ccpm import CCPM
 
-__all__ = ["DeepFM", "xDeepFM", "DCN", "AutoInt", "FM", "WDL", "NFM", "LR", "MaskNet", "AOANet"]
+__all__ = ["DeepFM", "xDeepFM", "DCN", "AutoInt", "FM", "WDL", "NFM", "LR", "MaskNet", "AOANet", "CCPM"]
