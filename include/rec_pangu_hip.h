@@ -651,6 +651,39 @@ int rp_ccpm_bwd(const float *dout, int64_t lddo, const float *x, int64_t ldx, co
                 float *dx, int64_t lddx, float *const *dW, float *const *db, int F, int D, int n_layers, const int *channels,
                 const int *heights, const int *ks, int64_t B, void *workspace, size_t workspace_bytes, rp_stream_t stream);
 
+/* ---- FiBiNet's SENET + bilinear interaction, written straight into the MLP's input (csrc/bilinear.hip) ----------------------------
+ * replaces SENET_Layer + BilinearInteractionLayer (twice) + the two cats of ranking/fibinet.py:58-68 (= ranking/afm.py):
+ *     Z = mean_d E,  A = relu(W2 relu(W1 Z))            (W1 [R, F], W2 [F, R], no biases; R = 0: no SENET, ONE branch)
+ *     T[b,p,:] = (W_w(p) E[b,i,:]) * E[b,j,:]           pair p = (i, j), i < j, in itertools.combinations order, P = F (F - 1) / 2
+ *     out[b, :] = T[b] (P D) | A_i A_j T[b] (P D, only with R > 0) | dense (n_dense)
+ * The second branch is the reference's bilinear layer on V = E * A: a per-(sample, pair) scalar times the first, so the
+ * matrix-vector product is formed once and V never.  fp32 FMA on the vector ALU (the forward is bound by what it writes).
+ * x [B, ldx]: F D embedding columns, then n_dense dense columns, read in place; out [B, ldo]: only the columns above are
+ * written; all fp32, row strides in floats, any alignment.  type: which pairs share a matrix; W: DEVICE array of NW device
+ * pointers to contiguous [D, D] matrices (nn.Linear layout: W[d_out, d_in]), NW = 1 / F / P; wmap: DEVICE array of P ints,
+ * the matrix of pair p (0 / i / p for the three types; values are clamped to 0 .. NW - 1).
+ *   rp_bilinear_fits   1 for 2 <= F <= 40, D in {8, 16, 32, 64}, 0 <= R <= F and a known type; else 0, and the entry points
+ *                      return RP_ERR_UNSUPPORTED.
+ *   rp_bilinear_bwd    from dout [B, lddo] and x alone (A, U and T are rebuilt): dx [B, lddx], F D columns written (or added
+ *                      to, accumulate != 0) — the bilinear and the SENET contributions summed; dW [NW, D, D] contiguous (a
+ *                      matrix no pair uses gets zeros), dW1 [R, F], dW2 [F, R].  A sample-major launch (dx, per-workgroup
+ *                      SENET partials), a pair-major launch (per (pair, batch slice) partials of dW) and a finishing launch
+ *                      that sums slices, then the pairs of a matrix, then the SENET partials, all in a fixed order: no
+ *                      floating-point atomics, bit-identical from run to run.  The batch is walked in chunks of 16384 samples
+ *                      (two launches each), so the workspace — rp_bilinear_bwd_workspace_bytes(F, D, R, type) — is independent
+ *                      of B. */
+#define RP_BILINEAR_ALL 0         /* "field_all": one matrix */
+#define RP_BILINEAR_EACH 1        /* "field_each": matrix i for the pairs (i, .) */
+#define RP_BILINEAR_INTERACTION 2 /* "field_interaction": one matrix per pair */
+int rp_bilinear_fits(int F, int D, int R, int type);
+int rp_bilinear_fwd(const float *x, int64_t ldx, const float *W1, const float *W2, const float *const *W, const int *wmap,
+                    float *out, int64_t ldo, int F, int D, int R, int type, int n_dense, int64_t B, rp_stream_t stream);
+int rp_bilinear_bwd_workspace_bytes(int F, int D, int R, int type, size_t *bytes);
+int rp_bilinear_bwd(const float *dout, int64_t lddo, const float *x, int64_t ldx, const float *W1, const float *W2,
+                    const float *const *W, const int *wmap, float *dx, int64_t lddx, int accumulate, float *dW, float *dW1,
+                    float *dW2, int F, int D, int R, int type, int n_dense, int64_t B, void *workspace, size_t workspace_bytes,
+                    rp_stream_t stream);
+
 /* ---- the narrow tail of the MLP as one launch each way (layers/deep.py:62-72 with hidden_units [.., 64, 64], output_dim 1:
  * DeepFM's dnn.net.{2,4,6}) --------------------------------------------------------------------------------------------
  *   hin [M, 64] (a ReLU output) -> [Linear 64x64 + ReLU] x n_hidden (1..3) -> Linear 64 -> 1 = logit [M]

@@ -1219,6 +1219,55 @@ def ccpm_conv_stack(rows, F: int, D: int, conv_layer):
     return _CCPMStack.apply(rows, F, D, ks, *[c.weight for c in convs], *[c.bias for c in convs])
 
 
+class _SenetBilinear(torch.autograd.Function):
+    """FiBiNet's SENET + both bilinear branches + the cat with the dense columns (ranking/fibinet.py:60-67) on one autograd
+    node: rows [B, >= F D + n_dense] with any row stride (the gather's row buffer, read in place) -> the MLP's input
+    [B, ld] = T(E) | A_i A_j T(E) | dense | padding (not written).  params: W1, W2 of the SENET when R > 0, then the [D, D]
+    matrices.  Nothing but the rows and the parameters is saved: rp_bilinear_bwd rebuilds A, U and T."""
+
+    @staticmethod
+    def forward(ctx, rows, F: int, D: int, R: int, btype: int, n_dense: int, ld: int, *params):
+        rows = _unit_inner(rows)
+        params = [p.contiguous() for p in params]
+        senet, weights = (tuple(params[:2]), params[2:]) if R > 0 else (None, params)
+        ctx.geom = (F, D, R, btype, n_dense)
+        ctx.save_for_backward(rows, *params)
+        out = hip._new((rows.shape[0], ld), torch.float32, rows.device)
+        return hip.bilinear_fwd(rows, F, D, weights, btype, senet, n_dense, out=out)
+
+    @staticmethod
+    def backward(ctx, dout):
+        F, D, R, btype, n_dense = ctx.geom
+        rows, params = ctx.saved_tensors[0], list(ctx.saved_tensors[1:])
+        senet, weights = (tuple(params[:2]), params[2:]) if R > 0 else (None, params)
+        if rows.shape[1] > F * D:  # columns that carry no gradient (dense, padding): the library's own fill
+            dx = hip.zeros(tuple(rows.shape), torch.float32, rows.device)
+        else:
+            dx = None
+        dx, dW, dW1, dW2 = hip.bilinear_bwd(_unit_inner(dout), rows, F, D, weights, btype, senet, n_dense, dx=dx)
+        # field_each: the last field opens no pair, its matrix takes no part (the reference leaves its .grad None)
+        used = len(weights) - 1 if btype == hip.BILINEAR_TYPES["field_each"] else len(weights)
+        grads = [dW[k] if k < used else None for k in range(len(weights))]
+        return (dx if ctx.needs_input_grad[0] else None, None, None, None, None, None, None,
+                *((dW1, dW2) if R > 0 else ()), *grads)
+
+
+def senet_bilinear(rows, F: int, D: int, senet, bilinear, dense: int = 0, pad_to: int = 64):
+    """the MLP input of FiBiNet from the rows [B, >= F D + dense] of the gather (embedding columns, then `dense` dense
+    columns): bilinear(E) | bilinear(senet(E)) | dense, as [B, ld] with ld the width rounded up to pad_to (the padding
+    columns are not written; the Linear that follows reads its in_features columns).  senet: a SENET_Layer or None (one
+    branch); bilinear: a BilinearInteractionLayer.  The shape must satisfy hip.bilinear_fits."""
+    btype = hip.BILINEAR_TYPES.get(bilinear.bilinear_type, -1)
+    R = 0 if senet is None else senet.excitation[0].weight.shape[0]
+    if not hip.bilinear_fits(F, D, R, btype):
+        raise RuntimeError(f"senet_bilinear: {F} fields of width {D}, {R} SENET units, {bilinear.bilinear_type!r}: no kernel "
+                           "form (hip.bilinear_fits)")
+    width = (2 if R else 1) * (F * (F - 1) // 2) * D + dense
+    ld = (width + pad_to - 1) // pad_to * pad_to if pad_to > 1 else width
+    params = [] if senet is None else [senet.excitation[0].weight, senet.excitation[2].weight]
+    return _SenetBilinear.apply(rows, F, D, R, btype, dense, ld, *params, *bilinear.weights())
+
+
 class _DiceGate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, xhat, alpha):

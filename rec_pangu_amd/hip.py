@@ -175,6 +175,11 @@ _SIGNATURES = {
     "rp_ccpm_bwd_workspace_bytes": (C.c_int, [_i32, _ip, _ip, C.POINTER(_sz)]),
     "rp_ccpm_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _ip, _ip, _ip, _i64, _vp,
                               _sz, _vp]),
+    "rp_bilinear_fits": (C.c_int, [_i32, _i32, _i32, _i32]),
+    "rp_bilinear_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _vp]),
+    "rp_bilinear_bwd_workspace_bytes": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_sz)]),
+    "rp_bilinear_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32,
+                                  _i32, _i32, _i64, _vp, _sz, _vp]),
     "rp_dice_gate_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp]),
     "rp_dice_gate_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
     "rp_mlp_tail_fits": (C.c_int, [_i32, _i32, _i64]),
@@ -2064,6 +2069,132 @@ def ccpm_bwd(dout, x, weights, biases, F: int, D: int, ks, dx=None):
                                  n, _ccpm_ints(channels), _ccpm_ints(heights), _ccpm_ints(ks), B, ws.data_ptr(), wbytes,
                                  _stream()), "rp_ccpm_bwd")
     return dx, dWs, dbs
+
+
+BILINEAR_TYPES = {"field_all": 0, "field_each": 1, "field_interaction": 2}  # RP_BILINEAR_*
+_BIL_TABLES: dict = {}
+_BIL_WMAPS: dict = {}
+
+
+def _bilinear_type(bilinear_type) -> int:
+    """the RP_BILINEAR_* code of a type given by name or code; -1 for one the library does not know"""
+    if isinstance(bilinear_type, str):
+        return BILINEAR_TYPES.get(bilinear_type, -1)
+    return int(bilinear_type) if int(bilinear_type) in BILINEAR_TYPES.values() else -1
+
+
+def bilinear_fits(F: int, D: int, R: int, bilinear_type) -> bool:
+    """do rp_bilinear_fwd / rp_bilinear_bwd cover F fields of width D with a SENET of R hidden units (0: none) and this weight
+    sharing?  (rp_bilinear_fits: 2 <= F <= 40, D in {8, 16, 32, 64}, 0 <= R <= F, field_all / field_each / field_interaction)"""
+    t = _bilinear_type(bilinear_type)
+    return t >= 0 and bool(lib().rp_bilinear_fits(int(F), int(D), int(R), t))
+
+
+def bilinear_weight_count(F: int, bilinear_type) -> int:
+    t = _bilinear_type(bilinear_type)
+    return {0: 1, 1: F, 2: F * (F - 1) // 2}[t]
+
+
+def _bilinear_tables(weights, F: int, t: int, device):
+    """(device array of the matrices' addresses, device array pair -> matrix), each built once: per address tuple (the
+    parameters stay where they are from step to step, so a recorded step holds the array's address) / per (F, type)"""
+    key = (F, t, str(device))
+    wmap = _BIL_WMAPS.get(key)
+    if wmap is None:
+        pairs = [(i, j) for i in range(F) for j in range(i + 1, F)]  # itertools.combinations order
+        wmap = _BIL_WMAPS[key] = torch.tensor([0 if t == 0 else i if t == 1 else p for p, (i, _) in enumerate(pairs)],
+                                              dtype=torch.int32, device=device)
+    ptrs = (str(device),) + tuple([w.data_ptr() for w in weights])
+    tab = _BIL_TABLES.get(ptrs)
+    if tab is None:
+        if len(_BIL_TABLES) >= 4096:  # (a few KB each; a recorded step replays with its array's address, so they are kept)
+            _BIL_TABLES.clear()
+        tab = _BIL_TABLES[ptrs] = torch.tensor(list(ptrs[1:]), dtype=torch.int64, device=device)
+    return tab, wmap
+
+
+def _bilinear_dims(x, F: int, D: int, weights, bilinear_type, senet, n_dense: int, wide=(), dx=None):
+    """the checks that need no GPU (dtypes, contiguity, shapes, row widths, the range), then the device check; -> (type
+    code, R, P, columns of the output).  wide: (name, tensor) pairs that must hold [B, >= width]; dx: [B, >= F D]"""
+    t = _bilinear_type(bilinear_type)
+    if t < 0:
+        raise RuntimeError(f"bilinear: unknown bilinear_type {bilinear_type!r}")
+    R = 0 if senet is None else int(senet[0].shape[0])
+    params = list(weights) + ([] if senet is None else list(senet))
+    for k, w in enumerate(params):
+        if w.dtype != torch.float32:
+            raise RuntimeError(f"bilinear: parameter {k}: expected torch.float32, got {w.dtype}")
+        if not w.is_contiguous():
+            raise RuntimeError(f"bilinear: parameter {k} must be contiguous")
+    if x.dtype != torch.float32:
+        raise RuntimeError(f"bilinear: x: expected torch.float32, got {x.dtype}")
+    need = F * D + n_dense
+    if x.dim() != 2 or x.shape[1] < need or (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < need):
+        raise RuntimeError(f"bilinear: x {tuple(x.shape)} / strides {x.stride()}: rows narrower than F D + dense = {need}")
+    if F < 2 or len(weights) != bilinear_weight_count(F, t) or any(tuple(w.shape) != (D, D) for w in weights):
+        raise RuntimeError(f"bilinear: {len(weights)} matrices for F = {F}, D = {D}, type {bilinear_type!r} "
+                           "(need 1 / F / F (F - 1) / 2 of shape [D, D])")
+    if senet is not None and (tuple(senet[0].shape) != (R, F) or tuple(senet[1].shape) != (F, R)):
+        raise RuntimeError(f"bilinear: SENET weights {tuple(senet[0].shape)} / {tuple(senet[1].shape)} for F = {F} "
+                           "(need [R, F] and [F, R])")
+    if not bilinear_fits(F, D, R, t):
+        raise RuntimeError(f"bilinear: F={F} D={D} R={R} type={bilinear_type!r}: outside rp_bilinear_fits")
+    P = F * (F - 1) // 2
+    width = (2 if R else 1) * P * D + n_dense
+    for name, buf, cols in [(n, b, width) for n, b in wide] + ([("dx", dx, F * D)] if dx is not None else []):
+        if buf.dtype != torch.float32 or buf.dim() != 2 or buf.shape[0] != x.shape[0] or buf.shape[1] < cols:
+            raise RuntimeError(f"bilinear: {name} {tuple(buf.shape)} {buf.dtype} for B = {x.shape[0]}: rows narrower than {cols}")
+    _req(x, torch.float32, "x")
+    for w in params:
+        _req(w, torch.float32, "bilinear parameter")
+    for name, buf in list(wide) + ([("dx", dx)] if dx is not None else []):
+        _req(buf, torch.float32, name)
+    return t, R, P, width
+
+
+def bilinear_fwd(x, F: int, D: int, weights, bilinear_type, senet=None, n_dense: int = 0, out=None):
+    """-> out [B, P D | P D | n_dense]: the bilinear products of the field pairs, the same scaled by A_i A_j of the SENET
+    (senet = (W1 [R, F], W2 [F, R]); None: that branch is absent), and the dense columns, in one launch (rp_bilinear_fwd).
+    x [B, >= F D + n_dense] with any row stride, weights: the [D, D] matrices (1 / F / P of them for field_all / field_each /
+    field_interaction).  out: a [B, >= width] buffer whose first `width` columns are written."""
+    t, R, P, width = _bilinear_dims(x, F, D, weights, bilinear_type, senet, n_dense,
+                                    wide=[("out", out)] if out is not None else [])
+    B, dev = x.shape[0], x.device
+    if out is None:
+        out = _new((B, width), torch.float32, dev)
+    tab, wmap = _bilinear_tables(weights, F, t, dev)
+    w1, w2 = (None, None) if senet is None else senet
+    with _Timed("bilinear_fwd", f"{B}x{F}.{D}.{R}", 4 * (B * (F * D + 2 * n_dense + width - n_dense) + len(weights) * D * D),
+                B * P * D * (2 * D + (3 if R else 1))):
+        _check(lib().rp_bilinear_fwd(x.data_ptr(), _rowmajor(x, "x"), _ptr(w1), _ptr(w2), tab.data_ptr(), wmap.data_ptr(),
+                                     out.data_ptr(), _rowmajor(out, "out"), F, D, R, t, n_dense, B, _stream()),
+               "rp_bilinear_fwd")
+    return out
+
+
+def bilinear_bwd(dout, x, F: int, D: int, weights, bilinear_type, senet=None, n_dense: int = 0, dx=None,
+                 accumulate: bool = False):
+    """-> (dx, dW [NW, D, D], dW1, dW2) of bilinear_fwd for the incoming dout [B, >= width], rebuilt from x alone
+    (rp_bilinear_bwd).  dx: a [B, >= F D] buffer whose first F D columns are written, or added to with accumulate (the others
+    are left alone); a fresh [B, F D] one otherwise.  dW1 / dW2 are None without a SENET."""
+    if dx is None and accumulate:
+        raise RuntimeError("bilinear_bwd: accumulate needs the dx buffer to add to")
+    t, R, P, width = _bilinear_dims(x, F, D, weights, bilinear_type, senet, n_dense, wide=[("dout", dout)], dx=dx)
+    B, dev = x.shape[0], x.device
+    if dx is None:
+        dx = _new((B, F * D), torch.float32, dev)
+    dW = _new((len(weights), D, D), torch.float32, dev)
+    dW1, dW2 = (None, None) if senet is None else (_new_like(senet[0]), _new_like(senet[1]))
+    tab, wmap = _bilinear_tables(weights, F, t, dev)
+    w1, w2 = (None, None) if senet is None else senet
+    ws, wbytes = _workspace("bilinear_bwd", F, D, R, t, device=dev)
+    with _Timed("bilinear_bwd", f"{B}x{F}.{D}.{R}", 4 * (B * (2 * F * D + width - n_dense) + 2 * len(weights) * D * D),
+                B * P * D * (6 * D + (8 if R else 3))):
+        _check(lib().rp_bilinear_bwd(dout.data_ptr(), _rowmajor(dout, "dout"), x.data_ptr(), _rowmajor(x, "x"), _ptr(w1),
+                                     _ptr(w2), tab.data_ptr(), wmap.data_ptr(), dx.data_ptr(), _rowmajor(dx, "dx"),
+                                     int(bool(accumulate)), dW.data_ptr(), _ptr(dW1), _ptr(dW2), F, D, R, t, n_dense, B,
+                                     ws.data_ptr(), wbytes, _stream()), "rp_bilinear_bwd")
+    return dx, dW, dW1, dW2
 
 
 def dice_gate_fwd(x, xhat, alpha):

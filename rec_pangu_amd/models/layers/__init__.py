@@ -4,11 +4,11 @@ from .deep import MLP
 from .shallow import LR_Layer
 from .interaction import (InnerProductLayer, FM_Layer, CrossInteractionLayer, CrossNet,
                           CompressedInteractionNet, MaskBlock, GeneralizedInteractionNet,
-                          GeneralizedInteraction)
+                          GeneralizedInteraction, BilinearInteractionLayer, SENET_Layer)
 from .attention import ScaledDotProductAttention, MultiHeadAttention, MultiHeadSelfAttention
 from .sequence import MaskedAveragePooling, MaskedSumPooling, KMaxPooling
 
 __all__ = ["Dice", "get_activation", "EmbeddingLayer", "MLP", "LR_Layer", "InnerProductLayer", "FM_Layer",
            "CrossInteractionLayer", "CrossNet", "CompressedInteractionNet", "MaskBlock", "GeneralizedInteractionNet",
-           "GeneralizedInteraction", "ScaledDotProductAttention",
+           "GeneralizedInteraction", "BilinearInteractionLayer", "SENET_Layer", "ScaledDotProductAttention",
            "MultiHeadAttention", "MultiHeadSelfAttention", "MaskedAveragePooling", "MaskedSumPooling", "KMaxPooling"]

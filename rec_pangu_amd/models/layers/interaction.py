@@ -1,9 +1,12 @@
 """Feature-interaction blocks of the hot path — drop-ins for rec_pangu/models/layers/interaction.py:
 InnerProductLayer (:12-52, the two pooling outputs the ranking models use), FM_Layer (:225-235),
-CrossInteractionLayer / CrossNet (:119-141), CompressedInteractionNet (:144-171), MaskBlock (:254-283); GeneralizedInteractionNet / GeneralizedInteraction, which the
-reference keeps beside its model (ranking/aoanet.py:81-115).
+CrossInteractionLayer / CrossNet (:119-141), CompressedInteractionNet (:144-171), MaskBlock (:254-283), BilinearInteractionLayer
+(:55-81), SENET_Layer (:238-251); GeneralizedInteractionNet / GeneralizedInteraction, which the reference keeps beside its model
+(ranking/aoanet.py:81-115).
 Parameter names/shapes follow the reference so its checkpoints load.
 """
+from itertools import combinations
+
 import torch
 from torch import nn
 
@@ -281,3 +284,78 @@ class GeneralizedInteractionNet(nn.Module):
         for layer in self.layers:
             B_i = layer.factorised(B_0, B_i)
         return B_i
+
+
+class BilinearInteractionLayer(nn.Module):
+    """T[b, p, :] = (W_w(p) E[b, i, :]) * E[b, j, :] for the field pairs p = (i, j), i < j, in itertools.combinations order ->
+    [B, P, D]  (interaction.py:55-81).  "field_all": one matrix (`bilinear_layer.weight`); "field_each": matrix i for the pairs
+    (i, .) — num_fields modules, the last one unused, as upstream; "field_interaction": one per pair
+    (`bilinear_layer.{p}.weight`).  On a HIP device the layer is one launch each way (functional.senet_bilinear without a
+    SENET: rp_bilinear_fwd with R = 0); FiBiNet runs it fused with its SENET_Layer instead of calling it twice."""
+
+    def __init__(self, num_fields, embedding_dim, bilinear_type="field_interaction"):
+        super(BilinearInteractionLayer, self).__init__()
+        self.bilinear_type = bilinear_type
+        if self.bilinear_type == "field_all":
+            self.bilinear_layer = nn.Linear(embedding_dim, embedding_dim, bias=False)
+        elif self.bilinear_type == "field_each":
+            self.bilinear_layer = nn.ModuleList([nn.Linear(embedding_dim, embedding_dim, bias=False)
+                                                 for i in range(num_fields)])
+        elif self.bilinear_type == "field_interaction":
+            self.bilinear_layer = nn.ModuleList([nn.Linear(embedding_dim, embedding_dim, bias=False)
+                                                 for i, j in combinations(range(num_fields), 2)])
+        else:
+            raise NotImplementedError()
+
+    def weights(self):
+        """the [D, D] matrices in the order the kernels number them"""
+        if self.bilinear_type == "field_all":
+            return [self.bilinear_layer.weight]
+        return [m.weight for m in self.bilinear_layer]
+
+    def torch_pairs(self, feature_emb):
+        """the reference's formulation over torch ops, wherever feature_emb lives"""
+        feature_emb_list = torch.split(feature_emb, 1, dim=1)
+        if self.bilinear_type == "field_all":
+            bilinear_list = [self.bilinear_layer(v_i) * v_j for v_i, v_j in combinations(feature_emb_list, 2)]
+        elif self.bilinear_type == "field_each":
+            bilinear_list = [self.bilinear_layer[i](feature_emb_list[i]) * feature_emb_list[j]
+                             for i, j in combinations(range(len(feature_emb_list)), 2)]
+        else:
+            bilinear_list = [self.bilinear_layer[i](v[0]) * v[1] for i, v in enumerate(combinations(feature_emb_list, 2))]
+        return torch.cat(bilinear_list, dim=1)
+
+    def forward(self, feature_emb):
+        if feature_emb.is_cuda and feature_emb.dtype == torch.float32 and feature_emb.dim() == 3:
+            from ... import functional as Fh, hip
+            B, F, D = feature_emb.shape
+            if hip.bilinear_fits(F, D, 0, self.bilinear_type) and len(self.weights()) == hip.bilinear_weight_count(
+                    F, self.bilinear_type):
+                return Fh.senet_bilinear(feature_emb.reshape(B, F * D), F, D, None, self, pad_to=1).view(B, -1, D)
+            hip.note_torch_path(f"BilinearInteractionLayer over {F} fields, D={D}, {self.bilinear_type} (outside hip.bilinear_fits)")
+        return self.torch_pairs(feature_emb)
+
+
+class SENET_Layer(nn.Module):
+    """V = E * A[..., None] with A = relu(W2 relu(W1 mean_d E)), no biases, reduced size max(1, int(F / ratio))
+    (interaction.py:238-251; `excitation.{0,2}.weight`).  FiBiNet on a HIP device never forms V: A_i A_j scales the bilinear
+    products inside rp_bilinear_fwd (functional.senet_bilinear).  Called on its own with a HIP tensor the layer composes V from
+    device ops (counted: hip.note_torch_path)."""
+
+    def __init__(self, num_fields, reduction_ratio=3):
+        super(SENET_Layer, self).__init__()
+        reduced_size = max(1, int(num_fields / reduction_ratio))
+        self.excitation = nn.Sequential(nn.Linear(num_fields, reduced_size, bias=False),
+                                        nn.ReLU(),
+                                        nn.Linear(reduced_size, num_fields, bias=False),
+                                        nn.ReLU())
+
+    def weights_A(self, feature_emb):
+        return self.excitation(torch.mean(feature_emb, dim=-1))
+
+    def forward(self, feature_emb):
+        if feature_emb.is_cuda:
+            from ... import hip
+            hip.note_torch_path("SENET_Layer called on its own (the kernels run it inside the bilinear interaction: "
+                                "functional.senet_bilinear)")
+        return feature_emb * self.weights_A(feature_emb).unsqueeze(-1)

@@ -9,5 +9,7 @@ from .lr import LR
 from .masknet import MaskNet
 from .aoanet import AOANet
 from .ccpm import CCPM
+from .fibinet import FiBiNet
+from .afm import AFM
 
-__all__ = ["DeepFM", "xDeepFM", "DCN", "AutoInt", "FM", "WDL", "NFM", "LR", "MaskNet", "AOANet", "CCPM"]
+__all__ = ["DeepFM", "xDeepFM", "DCN", "AutoInt", "FM", "WDL", "NFM", "LR", "MaskNet", "AOANet", "CCPM", "FiBiNet", "AFM"]
