@@ -499,6 +499,24 @@ int rp_attention_core_bwd(const float *qkvr, int64_t ldq, int nproj, const float
                           const float *stats, int T, int H, int a, float scale, float *dqkvr, int64_t lddq,
                           float *dxres, int64_t lddr, int64_t B, rp_stream_t stream);
 
+/* ---- K7 (wide form): self-attention over few tokens with one wide head; the complement of rp_attention_core_* -------------
+ * replaces attention.py:20-33,73-94 + a following torch.sum(., dim=1) where H == 1 and the head is wider than the core's 16
+ * (AITM, multi_task/aitm.py:33,64-66: T = 2 tokens, a = 400, no W_res).  Operands as above with nproj == 3: qkv [B*T, ldq] with
+ * columns Q | K | V (each a wide), xres [B*T, ldr] = the layer's input.  Per sample
+ *   S[t,s] = q_t . k_s (/scale; scale == 0: none), P = softmax_s, O_t = sum_s P[t,s] v_s, Y_t = relu(O_t + xres_t)
+ *   out = Y [B*T, a] (sum_tokens == 0) or sum_t Y_t [B, a] (sum_tokens != 0), contiguous.
+ * Lanes run along a (one wave per sample, dwordx4 where a, the strides and the addresses are multiples of 16 bytes), the
+ * T x T scores live in registers, no LDS, no workspace.  Backward: dout shaped like out; S, P and the ReLU mask are recomputed
+ * from qkv and xres; writes dqkv [B*T, lddq] (Q | K | V) and dxres [B*T, lddr] = dY_t [Y_t > 0] (the residual's gradient; the
+ * caller adds it to the dgrad GEMM's result).  One writer per element, no atomics: bit-identical from run to run.
+ * Range (rp_attention_wide_fits): H == 1, 2 <= T <= 4, 1 <= a <= 65536; B >= 1. */
+int rp_attention_wide_fits(int T, int H, int a);
+int rp_attention_wide_fwd(const float *qkv, int64_t ldq, const float *xres, int64_t ldr, int T, int H, int a, float scale,
+                          int sum_tokens, float *out, int64_t B, rp_stream_t stream);
+int rp_attention_wide_bwd(const float *qkv, int64_t ldq, const float *xres, int64_t ldr, const float *dout, int T, int H,
+                          int a, float scale, int sum_tokens, float *dqkv, int64_t lddq, float *dxres, int64_t lddr,
+                          int64_t B, rp_stream_t stream);
+
 /* dgrad with a fused row-scaled periodic addend (the DeepFM gather backward's FM term folded into dX):
  *   out[M,N] = a[M,K] . w[N,K]^T + row_scale[m] * row_add[m, n % 64]  for n < add_cols   (no bias / activation)
  * Only K <= 64 (multiple of 4), M % 128 == 0, N % 64 == 0, add_cols % 64 == 0, 16-byte aligned rows and a split-bf16
@@ -760,6 +778,23 @@ int rp_loss_finish(const float *partial, int n, float scale, float *loss, rp_str
 /* dz[b] = gloss[0] * weight/B * dBCE/dp * (apply_sigmoid ? p(1-p) : 1) */
 int rp_sigmoid_bce_bwd(const float *pred, const float *label, const float *gloss, int64_t B, float p_eps,
                        float weight, int apply_sigmoid, float *dz, rp_stream_t stream);
+
+/* ---- two-task loss heads that couple the tasks ---------------------------------------------------------------------------
+ * replaces multi_task/essm.py:69-75 and multi_task/aitm.py:84-100 (and the two sigmoids in front of them).
+ *   p_i = sigmoid(z_i) (apply_sigmoid) or z_i;  BCE = mean over the batch, ATen's form (logs clamped at -100)
+ *   RP_PAIR_ESSM: loss = BCE(p1 p2, y2) + coef BCE(p1, y1)
+ *   RP_PAIR_AITM: loss = BCE(p1, y1) + BCE(p2, y2) + coef sum_b max(p2 - p1, 0)       (a sum, not a mean)
+ * p1, p2: float[B] out;  partial: float[3 * rp_loss_partials(B)] workspace (per-workgroup sums of the two BCE terms and of the
+ * constraint, added in a fixed order by a one-block finish that scales them only then: no atomics);  loss: device float[1].
+ * Backward: dz_i = gloss[0] dloss/dz_i from (p1, p2, y1, y2); ESSM with q = p1 p2: dp1 = dq p2 + coef bce'(p1, y1), dp2 = dq p1;
+ * AITM: dp2 = bce'(p2, y2) + coef s, dp1 = bce'(p1, y1) - coef s with s = 1 / 0 / 0.5 for p2 > / < / == p1 (ATen's maximum);
+ * bce'(p, y) = (p - y) / max((1 - p) p, 1e-12) / B. */
+#define RP_PAIR_ESSM 0
+#define RP_PAIR_AITM 1
+int rp_pair_loss_fwd(const float *z1, const float *z2, const float *y1, const float *y2, int64_t B, int mode, float coef,
+                     int apply_sigmoid, float *p1, float *p2, float *partial, float *loss, rp_stream_t stream);
+int rp_pair_loss_bwd(const float *p1, const float *p2, const float *y1, const float *y2, const float *gloss, int64_t B,
+                     int mode, float coef, int apply_sigmoid, float *dz1, float *dz2, rp_stream_t stream);
 
 /* ---- multi-id ("bag") lookups with pooling: the CSR / segmented embedding gather + sum-pool of the north star ----------
  * replaces EmbeddingLayer.forward(X, name="<col>_seq") (rec_pangu/models/layers/embedding.py:64-71: [B, L] ids ->

@@ -769,6 +769,88 @@ def field_attention_split(X, W, T: int, Din: int, H: int, a: int, has_res: bool,
     return out.view(B, T, H * a)
 
 
+class _AttentionWide(torch.autograd.Function):
+    """The whole layer as ONE node, so that the two uses of its input (the projection GEMM and the residual) meet in a library
+    launch (rp_add_rows) instead of autograd's ATen add: x2 [B*T, a] -> QKV (rp_linear_fwd on the stacked weights) -> the
+    wide-head core (rp_attention_wide_fwd).  Saved: x2, W and the QKV the forward wrote; the backward recomputes the rest."""
+
+    @staticmethod
+    def forward(ctx, x2, W, T: int, a: int, scale: float, sum_tokens: bool):
+        x2 = _unit_inner(x2)
+        qkv = hip.linear_fwd(x2, _rows16(W), None, ACT_NONE, K=a)
+        out = hip.attention_wide_fwd(qkv, x2, T, a, scale, sum_tokens)
+        ctx.cfg = (T, a, scale, sum_tokens)
+        ctx.save_for_backward(x2, W, qkv)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        x2, W, qkv = ctx.saved_tensors
+        T, a, scale, sum_tokens = ctx.cfg
+        dqkv, dxres = hip.attention_wide_bwd(qkv, x2, dout.contiguous(), T, a, scale, sum_tokens)
+        dx = dW = None
+        if ctx.needs_input_grad[0]:
+            dx = hip.linear_fwd(dqkv, hip.transpose(W), None, ACT_NONE)  # [B*T, a]
+            hip.add_rows_to(dxres, dx)                                     # + the residual's gradient
+        if ctx.needs_input_grad[1]:
+            dW, _ = hip.linear_wgrad(dqkv, x2, a, want_bias=False)
+        return dx, dW, None, None, None, None
+
+
+def attention_wide(X, W, T: int, a: int, scale: float = 0.0, sum_tokens: bool = False):
+    """Self-attention over T <= 4 tokens with one head as wide as the input (no W_res), split form: X [B, T, a], W =
+    stack_rows([Wq, Wk, Wv]) [3a, a] -> relu(softmax(Q K^T [/scale]) V + X) [B, T, a], or its sum over the tokens [B, a]
+    (sum_tokens: AITM's torch.sum(ait, dim=1); the [B, T, a] tensor is then never written)."""
+    B = X.shape[0]
+    out = _AttentionWide.apply(X.reshape(B * T, a), W, T, a, float(scale), bool(sum_tokens))
+    return out if sum_tokens else out.view(B, T, a)
+
+
+class _FanOut(torch.autograd.Function):
+    """x -> n aliases of it, one per consumer; the consumers' gradients are summed by library launches (rp_add_rows) instead of
+    autograd's ATen adds, which would keep a recorded step from replaying as a launch plan.  2-D fp32 x (a shared tower input)."""
+
+    @staticmethod
+    def forward(ctx, x, n: int):
+        x = _unit_inner(x)
+        return tuple(x.detach() for _ in range(n))
+
+    @staticmethod
+    def backward(ctx, *gs):
+        gs = [g for g in gs if g is not None]
+        if not gs:
+            return None, None
+        total = _unit_inner(gs[0])
+        for g in gs[1:]:
+            hip.add_rows_to(_unit_inner(g), total)  # (in place: the first consumer's gradient buffer is this node's to keep)
+        return total, None
+
+
+def fan_out(x, n: int):
+    return _FanOut.apply(x, n)
+
+
+class _StackTokens(torch.autograd.Function):
+    """n matrices [B, a] -> one [B, n, a] buffer (token i = matrix i), by rp_copy_rows into its row-strided slices: torch.cat of the
+    unsqueezed matrices without the ATen launch; the gradients leave as the slices of the incoming one."""
+
+    @staticmethod
+    def forward(ctx, *xs):
+        B, a = xs[0].shape
+        out = torch.empty((B, len(xs), a), dtype=torch.float32, device=xs[0].device)
+        for i, x in enumerate(xs):
+            hip.copy_rows_to(_unit_inner(x), out[:, i, :])
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        return tuple(g[:, i, :] for i in range(g.shape[1]))
+
+
+def stack_tokens(xs):
+    return _StackTokens.apply(*xs)
+
+
 def field_attention(x, W, T: int, Din: int, H: int, a: int, has_res: bool, scale: float = 0.0):
     """x [B, >=T*Din] -> relu(attention + residual) [B, T, H*a];  W = cat(Wq, Wk, Wv[, Wres]) [(3|4)*H*a, Din]."""
     return _FieldAttention.apply(x, W, T, Din, H, a, has_res, scale)
@@ -1390,6 +1472,43 @@ def sigmoid_bce_multi(logits: Sequence[torch.Tensor], labels: Sequence[torch.Ten
     T = len(logits)
     out = _SigmoidBCEMulti.apply(T, apply_sigmoid, float(p_eps), tuple(float(w) for w in weights), *labels, *logits)
     return list(out[:T]), out[T]
+
+
+class _PairLoss(torch.autograd.Function):
+    """The two-task loss heads that couple the tasks (rp_pair_loss_*): ESSM's BCE(p1 p2, y2) + w BCE(p1, y1) and AITM's
+    BCE(p1, y1) + BCE(p2, y2) + c sum max(p2 - p1, 0), the sigmoids included when the inputs are logits."""
+
+    @staticmethod
+    def forward(ctx, z1, z2, y1, y2, mode: int, coef: float, apply_sigmoid: bool):
+        ctx.set_materialize_grads(False)  # the predictions are normally not differentiated
+        y1, y2 = y1.reshape(-1).contiguous(), y2.reshape(-1).contiguous()
+        p1, p2, loss = hip.pair_loss_fwd(z1.reshape(-1).contiguous(), z2.reshape(-1).contiguous(), y1, y2, mode, coef,
+                                         apply_sigmoid)
+        ctx.cfg = (mode, coef, apply_sigmoid, tuple(z1.shape), tuple(z2.shape))
+        ctx.save_for_backward(p1, p2, y1, y2)
+        return p1.view(z1.shape), p2.view(z2.shape), loss
+
+    @staticmethod
+    def backward(ctx, dp1, dp2, dloss):
+        p1, p2, y1, y2 = ctx.saved_tensors
+        mode, coef, apply_sigmoid, s1, s2 = ctx.cfg
+        dz1 = dz2 = None
+        if dloss is not None:
+            dz1, dz2 = hip.pair_loss_bwd(p1, p2, y1, y2, dloss, mode, coef, apply_sigmoid)
+        for k, (dp, p) in enumerate(((dp1, p1), (dp2, p2))):
+            if dp is not None:  # someone differentiated through a prediction itself (rare): torch ops on device
+                extra = dp.reshape(-1) * (p * (1 - p) if apply_sigmoid else 1.0)
+                if k == 0:
+                    dz1 = extra if dz1 is None else dz1 + extra
+                else:
+                    dz2 = extra if dz2 is None else dz2 + extra
+        return (None if dz1 is None else dz1.view(s1), None if dz2 is None else dz2.view(s2), None, None, None, None, None)
+
+
+def pair_loss(z1, z2, y1, y2, mode: int, coef: float, apply_sigmoid: bool = True):
+    """(p1, p2, loss): p = sigmoid(z) (apply_sigmoid) or z, shaped like z1 / z2; mode hip.PAIR_ESSM: loss = BCE(p1 p2, y2) +
+    coef BCE(p1, y1); hip.PAIR_AITM: loss = BCE(p1, y1) + BCE(p2, y2) + coef sum_b max(p2 - p1, 0)"""
+    return _PairLoss.apply(z1, z2, y1, y2, int(mode), float(coef), bool(apply_sigmoid))
 
 
 class _SigmoidSum(torch.autograd.Function):

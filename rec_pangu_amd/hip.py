@@ -147,6 +147,10 @@ _SIGNATURES = {
     "rp_attention_core_fwd": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _f32, _vp, _vp, _i64, _vp]),
     "rp_attention_core_bwd": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _i64, _vp, _i64, _i64,
                                         _vp]),
+    "rp_attention_wide_fits": (C.c_int, [_i32, _i32, _i32]),
+    "rp_attention_wide_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp]),
+    "rp_attention_wide_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp, _i64, _i64,
+                                        _vp]),
     "rp_set_matmul_precision": (C.c_int, [_i32]),
     "rp_get_matmul_precision": (C.c_int, []),
     "rp_fm_pool_fwd": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
@@ -200,6 +204,8 @@ _SIGNATURES = {
     "rp_sigmoid_bce_fwd": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp]),
     "rp_sigmoid_bce_fwd_accum": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp]),
     "rp_sigmoid_bce_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp]),
+    "rp_pair_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "rp_pair_loss_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp, _vp]),
     "rp_adam_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _f64, _f64, _f64, _f64, _i64, _i32, _vp, _vp, _vp]),
     "rp_counter_add": (C.c_int, [_vp, _i32, _vp]),
     "rp_counters_add": (C.c_int, [_vp, _i32, _i32, _vp]),
@@ -1764,6 +1770,48 @@ def attention_core_bwd(qkvr, nproj: int, out, dout, stats, T: int, H: int, a: in
     return dqkvr, dxres
 
 
+def attention_wide_fits(T: int, H: int, a: int) -> bool:
+    """the few-token, one-wide-head form of the attention core (rp_attention_wide_*): H == 1, 2 <= T <= 4, a <= 65536"""
+    return bool(lib().rp_attention_wide_fits(T, H, a))
+
+
+def _attention_wide_dims(qkv, xres, T: int, a: int):
+    _req(qkv, torch.float32, "qkv")
+    _req(xres, torch.float32, "xres")
+    ldq, ldr = _rowmajor(qkv, "qkv"), _rowmajor(xres, "xres")
+    BT = qkv.shape[0]
+    if BT % T != 0 or BT == 0 or xres.shape[0] != BT or qkv.shape[1] < 3 * a or xres.shape[1] < a:
+        raise RuntimeError(f"attention_wide: qkv {tuple(qkv.shape)} / xres {tuple(xres.shape)} do not hold B*{T} token rows of "
+                           f"3*{a} / {a} columns")
+    return BT // T, ldq, ldr
+
+
+def attention_wide_fwd(qkv, xres, T: int, a: int, scale: float, sum_tokens: bool):
+    """qkv [B*T, >=3a] (Q|K|V), xres [B*T, >=a] -> relu(softmax(Q K^T [/scale]) V + xres): [B*T, a], or its sum over the
+    tokens [B, a] when sum_tokens"""
+    B, ldq, ldr = _attention_wide_dims(qkv, xres, T, a)
+    out = _new((B if sum_tokens else B * T, a), torch.float32, qkv.device)
+    with _Timed("attention_wide_fwd", f"{B}x{T}x{a}", 4 * (4 * B * T * a + out.numel())):
+        _check(lib().rp_attention_wide_fwd(qkv.data_ptr(), ldq, xres.data_ptr(), ldr, T, 1, a, scale, int(sum_tokens),
+                                           out.data_ptr(), B, _stream()), "rp_attention_wide_fwd")
+    return out
+
+
+def attention_wide_bwd(qkv, xres, dout, T: int, a: int, scale: float, sum_tokens: bool):
+    """-> (dqkv [B*T, 3a], dxres [B*T, a]) from the cotangent dout (shaped like attention_wide_fwd's result, contiguous)"""
+    B, ldq, ldr = _attention_wide_dims(qkv, xres, T, a)
+    _req(dout, torch.float32, "dout")
+    if not dout.is_contiguous() or dout.numel() != (B if sum_tokens else B * T) * a:
+        raise RuntimeError("attention_wide_bwd: dout must be contiguous and shaped like the forward's result")
+    dqkv = _new((B * T, 3 * a), torch.float32, qkv.device)
+    dxres = _new((B * T, a), torch.float32, qkv.device)
+    with _Timed("attention_wide_bwd", f"{B}x{T}x{a}", 4 * (6 * B * T * a + dout.numel() + 4 * B * T * a)):
+        _check(lib().rp_attention_wide_bwd(qkv.data_ptr(), ldq, xres.data_ptr(), ldr, dout.data_ptr(), T, 1, a, scale,
+                                           int(sum_tokens), dqkv.data_ptr(), 3 * a, dxres.data_ptr(), a, B, _stream()),
+               "rp_attention_wide_bwd")
+    return dqkv, dxres
+
+
 def mmoe_combine_fwd(z, K: int, E: int, T: int):
     """z [B, >=K*E+T*E] -> (out [T,B,K], gate [B,T*E])."""
     _req(z, torch.float32, "z")
@@ -2264,6 +2312,45 @@ def sigmoid_bce_bwd(pred, label, gloss, apply_sigmoid: bool = True, p_eps: float
         _check(lib().rp_sigmoid_bce_bwd(pred.data_ptr(), label.data_ptr(), gloss.data_ptr(), B, p_eps, weight,
                                     int(apply_sigmoid), dz.data_ptr(), _stream()), "rp_sigmoid_bce_bwd")
     return dz
+
+
+PAIR_ESSM, PAIR_AITM = 0, 1  # RP_PAIR_*
+
+
+def _pair_vectors(tensors, names):
+    B = tensors[0].numel()
+    for t, name in zip(tensors, names):
+        _req(t, torch.float32, name)
+        if t.numel() != B or not t.is_contiguous():
+            raise RuntimeError(f"pair_loss: {name} must be contiguous with B = {B} elements")
+    if B < 1:
+        raise RuntimeError("pair_loss: empty batch")
+    return B
+
+
+def pair_loss_fwd(z1, z2, y1, y2, mode: int, coef: float, apply_sigmoid: bool = True):
+    """-> (p1 [B], p2 [B], loss []): RP_PAIR_ESSM BCE(p1 p2, y2) + coef BCE(p1, y1); RP_PAIR_AITM BCE(p1, y1) + BCE(p2, y2) +
+    coef sum_b max(p2 - p1, 0), with p = sigmoid(z) or z itself"""
+    B = _pair_vectors((z1, z2, y1, y2), ("z1", "z2", "y1", "y2"))
+    dev = z1.device
+    p1, p2 = _new((B,), torch.float32, dev), _new((B,), torch.float32, dev)
+    partial = _new((3 * lib().rp_loss_partials(B),), torch.float32, dev)
+    loss = _new((), torch.float32, dev)
+    with _Timed("pair_loss_fwd"):
+        _check(lib().rp_pair_loss_fwd(z1.data_ptr(), z2.data_ptr(), y1.data_ptr(), y2.data_ptr(), B, mode, coef,
+                                      int(apply_sigmoid), p1.data_ptr(), p2.data_ptr(), partial.data_ptr(), loss.data_ptr(),
+                                      _stream()), "rp_pair_loss_fwd")
+    return p1, p2, loss
+
+
+def pair_loss_bwd(p1, p2, y1, y2, gloss, mode: int, coef: float, apply_sigmoid: bool = True):
+    B = _pair_vectors((p1, p2, y1, y2), ("p1", "p2", "y1", "y2"))
+    dz1, dz2 = _new((B,), torch.float32, p1.device), _new((B,), torch.float32, p1.device)
+    gloss = gloss.reshape(1).contiguous()
+    with _Timed("pair_loss_bwd"):
+        _check(lib().rp_pair_loss_bwd(p1.data_ptr(), p2.data_ptr(), y1.data_ptr(), y2.data_ptr(), gloss.data_ptr(), B, mode,
+                                      coef, int(apply_sigmoid), dz1.data_ptr(), dz2.data_ptr(), _stream()), "rp_pair_loss_bwd")
+    return dz1, dz2
 
 
 _weight_epoch = 0

@@ -8,8 +8,9 @@ always applied last (:94).
 
 On a HIP device the AutoInt configuration (self-attention, align_to="output", no mask / dropout / LayerNorm,
 residual on) runs as ONE launch per layer (rp_field_attention_fwd): projections, raw-view head split, scores,
-softmax, PV, residual and ReLU for a sample all stay in LDS.  Any other configuration of the general
-MultiHeadAttention module is composed from device ops as written in `_compose`.
+softmax, PV, residual and ReLU for a sample all stay in LDS — or split into one projection GEMM and a per-sample core
+(rp_attention_core_*: heads up to 16 wide; rp_attention_wide_*: one wide head over 2..4 tokens, AITM).  Any other
+configuration of the general MultiHeadAttention module is composed from device ops as written in `_compose`.
 """
 import numpy as np
 import torch
@@ -75,17 +76,25 @@ class MultiHeadAttention(nn.Module):
                 and self._fits_lds(query.shape[1]))
 
     def _fits_lds(self, T) -> bool:
-        """Either HIP form of the layer applies: the split form (projection GEMM + per-sample T x T core: head width
-        <= 16, a sample's Q/K/V within 64 KB of LDS) or the older one-launch layer (everything, weights included, in
-        the CU's 160 KB LDS).  Configurations neither covers are composed from device ops."""
+        """One of the HIP forms of the layer applies: the split form (projection GEMM + per-sample T x T core: head width
+        <= 16, a sample's Q/K/V within 64 KB of LDS), the wide form (projection GEMM + a core whose lanes run along one
+        wide head: H = 1, 2 <= T <= 4, no W_res — AITM) or the older one-launch layer (everything, weights included, in
+        the CU's 160 KB LDS).  Configurations none of them covers are composed from device ops."""
         from ... import hip
         key = (T, self.input_dim, self.num_heads, self.attention_dim, self.W_res is not None)
         if getattr(self, "_fit_key", None) != key:
             self._fit_key = key
-            self._fit = hip.attention_core_fits(T, self.num_heads, self.attention_dim) or hip.field_attention_fits(*key)
+            self._fit = (hip.attention_core_fits(T, self.num_heads, self.attention_dim) or self._wide(T)
+                         or hip.field_attention_fits(*key))
         return self._fit
 
-    def _fused(self, X):
+    def _wide(self, T) -> bool:
+        """the wide form applies, and the split form (which keeps its configurations) does not"""
+        from ... import hip
+        return (self.W_res is None and not hip.attention_core_fits(T, self.num_heads, self.attention_dim)
+                and hip.attention_wide_fits(T, self.num_heads, self.attention_dim))
+
+    def _fused(self, X, sum_tokens: bool = False):
         B, T, Din = X.shape
         ws = [self.W_q.weight, self.W_k.weight, self.W_v.weight]
         if self.W_res is not None:
@@ -94,11 +103,15 @@ class MultiHeadAttention(nn.Module):
         W = Fh.stack_rows(ws) if all(w.dim() == 2 and w.dtype is torch.float32 for w in ws) else torch.cat(ws, dim=0)
         if hip.attention_core_fits(T, self.num_heads, self.attention_dim):
             # projections on the matrix core as one GEMM over all B*T tokens + the T x T core per sample
-            return Fh.field_attention_split(X, W, T, Din, self.num_heads, self.attention_dim, self.W_res is not None,
-                                            float(self.scale or 0.0))
+            out = Fh.field_attention_split(X, W, T, Din, self.num_heads, self.attention_dim, self.W_res is not None,
+                                           float(self.scale or 0.0))
+            return out.sum(dim=1) if sum_tokens else out
+        if self._wide(T):
+            # the same split with the core for one wide head; the sum over the tokens rides in its epilogue
+            return Fh.attention_wide(X, W, T, self.attention_dim, float(self.scale or 0.0), sum_tokens)
         out = Fh.field_attention(X.reshape(B, T * Din), W, T, Din, self.num_heads,
                                  self.attention_dim, self.W_res is not None, float(self.scale or 0.0))
-        return out  # [B, T, H*a]
+        return out.sum(dim=1) if sum_tokens else out  # [B, T, H*a]
 
     def _compose(self, query, key, value, mask):
         """Any configuration the HIP layer does not cover (and every CPU call): the same layer from device ops.  Heads are
@@ -126,6 +139,14 @@ class MultiHeadAttention(nn.Module):
             hip.note_torch_path("MultiHeadAttention outside the fused layer's configurations (mask, distinct q/k/v, "
                                 "layer_norm, train-mode dropout, align_to='input' or a shape the kernels' LDS budget does not hold)")
         return self._compose(query, key, value, mask)
+
+
+    def self_attention_sum(self, X):
+        """torch.sum(self(X, X, X)[0], dim=1) (multi_task/aitm.py:64-66).  In the wide form the sum over the tokens is part
+        of the core's launch and the [B, T, H*a] tensor is never written."""
+        if self._fused_ok(X, X, X, None):
+            return self._fused(X, sum_tokens=True)
+        return MultiHeadAttention.forward(self, X, X, X)[0].sum(dim=1)
 
 
 class MultiHeadSelfAttention(MultiHeadAttention):
