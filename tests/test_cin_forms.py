@@ -30,6 +30,7 @@ FORMS = {
     (16, 40, (8, 8), "auto", True): (False, (F32, HEAD)),
     (5, 8, (7,), "auto", True): (False, (("last",) * 3,)),
     (4, 80, (3,), "auto", True): (False, (("f32_1ch", "f32", "f32"),)),
+    (26, 80, (40, 3), "auto", True): (False, (F32, ("f32_1ch", "f32", "f32"))),
     (26, 40, (40, 40, 8), "auto", True): None,
     (33, 64, (16, 16), "auto", True): None,
     (33, 8, (7,), "auto", True): None,

@@ -91,10 +91,13 @@ def test_cin_vs_reference_fixture():
 
 
 # [40, 70, 16] / [128, 128, 128]: middle layers fed by MORE than 32 maps — the chunked bf16 matrix-core form
-# (functional._CINChunked: chunks of 32 + 8, 32 + 32 + 6, 4 x 32 maps), through the misaligned-row fallback here
+# (functional._CINChunked: chunks of 32 + 8, 32 + 32 + 6, 4 x 32 maps), through the misaligned-row fallback here.
+# D = 80 (three 32-column tiles): no collapsed-last-layer kernel, the f32 form with one output channel (f32_1ch) — alone,
+# and behind a first layer of 40 maps (26 x 40 weights per channel: more than the f32 kernels prefetch into registers)
 @pytest.mark.parametrize("B,H,D,units", [(300, 26, 64, [128, 128]), (257, 26, 64, [16, 16, 16]), (130, 16, 40, [8, 8]),
                                           (64, 5, 8, [7]), (100, 26, 32, [32, 24, 9]), (300, 26, 64, [40, 70, 16]),
-                                          (130, 26, 64, [128, 128, 128]), (96, 7, 32, [33, 5]), (96, 26, 64, [136, 8])])
+                                          (130, 26, 64, [128, 128, 128]), (96, 7, 32, [33, 5]), (96, 26, 64, [136, 8]),
+                                          (96, 4, 80, [3]), (33, 26, 80, [40, 3])])
 def test_cin_vs_oracle(B, H, D, units, ld=None):
     """ld: the row stride of the buffer X_0 is a view of; H*D + 13 (rows that are not 16-byte aligned) unless given"""
     from rec_pangu_amd.models.layers import CompressedInteractionNet
