@@ -796,6 +796,42 @@ int rp_pair_loss_fwd(const float *z1, const float *z2, const float *y1, const fl
 int rp_pair_loss_bwd(const float *p1, const float *p2, const float *y1, const float *y2, const float *gloss, int64_t B,
                      int mode, float coef, int apply_sigmoid, float *dz1, float *dz2, rp_stream_t stream);
 
+/* ---- AFN's logarithmic transformation layer + both BatchNorms (csrc/lognet.hip) --------------------------------------------
+ * replaces ranking/afn.py:93-102:  x = log(max(|e|, 1e-5f));  y = BN1(x), channel = field, statistics over (b, d);
+ * z[b,l,d] = sum_f W[l,f] y[b,f,d];  c = exp(z);  out = BN2(c), channel = neuron.
+ *   x    [B, ldx >= F D]  the gather's rows, read in place;  W [L, F];  z [B, L D] (written, saved for the backward);
+ *   out  [B, ldo >= L D]  L D columns written.  x, y and c never exist in global memory.
+ *   rp_lognet_fits   1 for 1 <= F <= 64, 1 <= D <= 256, 1 <= L <= 8 (the shapes whose kernels use no scratch); else 0, and the
+ *                    entry points return RP_ERR_UNSUPPORTED.  B D < 2^31.
+ *   rp_lognet_plan   the partial workgroups (<= 512) of every reduction over the B D (sample, column) pairs and their run.
+ *   train != 0       batch statistics: mean1 / var1 [F] and mean2 / var2 [L] (biased) are WRITTEN (two-stage, fixed order,
+ *                    per-workgroup (mean, M2) pairs merged: centred); 5 launches.  The running buffers are the caller's
+ *                    (rp_batchnorm_update_running with M = B D).
+ *   train == 0       the four vectors are read (running statistics); 1 launch.
+ *   rp_lognet_bwd    from dout [B, lddo], x and z, with the statistics the forward used: dx [B, lddx] (F D columns written:
+ *                    BN1'(W^T dz) / e where |e| >= 1e-5f, exactly 0 elsewhere), dW [L, F], dgamma1 / dbeta1 [F], dgamma2 /
+ *                    dbeta2 [L]; train == 0: the statistics are constants.  5 launches, every sum two-stage in a fixed order;
+ *                    workspace rp_lognet_workspace_bytes(F, L), independent of B. */
+int rp_lognet_fits(int F, int D, int L);
+int rp_lognet_plan(int64_t B, int D, int *nblk, int64_t *chunk);
+int rp_lognet_workspace_bytes(int F, int L, size_t *bytes);
+int rp_lognet_fwd(const float *x, int64_t ldx, const float *W, const float *gamma1, const float *beta1, float *mean1,
+                  float *var1, float eps1, const float *gamma2, const float *beta2, float *mean2, float *var2, float eps2,
+                  float *z, float *out, int64_t ldo, int64_t B, int F, int D, int L, int train, void *workspace,
+                  size_t workspace_bytes, rp_stream_t stream);
+int rp_lognet_bwd(const float *dout, int64_t lddo, const float *x, int64_t ldx, const float *z, const float *W,
+                  const float *gamma1, const float *beta1, const float *mean1, const float *var1, float eps1,
+                  const float *gamma2, const float *mean2, const float *var2, float eps2, float *dx, int64_t lddx, float *dW,
+                  float *dgamma1, float *dbeta1, float *dgamma2, float *dbeta2, int64_t B, int F, int D, int L, int train,
+                  void *workspace, size_t workspace_bytes, rp_stream_t stream);
+/* AFN's ensemble head (afn.py:81, nn.Linear(2, 1) over cat[a, d]):  z[b] = w[0] a[b] + w[1] d[b] + bias[0], and its backward
+ * da = w[0] dz, dd = w[1] dz, dw [2] = (sum dz a, sum dz d), dbias [1] = sum dz (per-workgroup partials + a fixed-order
+ * finish; partial: float[rp_pair_fc_partials(B)]). */
+int rp_pair_fc_partials(int64_t B);
+int rp_pair_fc_fwd(const float *a, const float *d, const float *w, const float *bias, float *z, int64_t B, rp_stream_t stream);
+int rp_pair_fc_bwd(const float *dz, const float *a, const float *d, const float *w, float *da, float *dd, float *dw,
+                   float *dbias, float *partial, int64_t B, rp_stream_t stream);
+
 /* ---- multi-id ("bag") lookups with pooling: the CSR / segmented embedding gather + sum-pool of the north star ----------
  * replaces EmbeddingLayer.forward(X, name="<col>_seq") (rec_pangu/models/layers/embedding.py:64-71: [B, L] ids ->
  * [B, L, D]) FOLLOWED BY MaskedSumPooling (layers/sequence.py:38-59: sum over dim 1) or MaskedAveragePooling

@@ -1350,6 +1350,99 @@ def senet_bilinear(rows, F: int, D: int, senet, bilinear, dense: int = 0, pad_to
     return _SenetBilinear.apply(rows, F, D, R, btype, dense, ld, *params, *bilinear.weights())
 
 
+class _LogarithmicNet(torch.autograd.Function):
+    """AFN's logarithmic transformation layer with both BatchNorms (ranking/afn.py:93-102) on one autograd node: rows
+    [B, >= F D] with any row stride (the gather's row buffer, read in place) -> the MLP's input [B, ld], L D columns written.
+    stats: () with batch statistics — the node then also returns them (mean1, var1 [F], mean2, var2 [L], biased, not
+    differentiable) for the running buffers — or the four running vectors.  Saved: the rows, z [B, L D], the statistics and the
+    parameters; rp_lognet_bwd rebuilds y from the rows and c from z."""
+
+    @staticmethod
+    def forward(ctx, rows, F: int, D: int, ld: int, eps1: float, eps2: float, W, g1, b1, g2, b2, *stats):
+        rows = _unit_inner(rows)
+        W, g1, b1, g2, b2 = (t.contiguous() for t in (W, g1, b1, g2, b2))
+        train = len(stats) == 0
+        L, dev = W.shape[0], rows.device
+        if train:
+            stats = (hip._new((F,), torch.float32, dev), hip._new((F,), torch.float32, dev),
+                     hip._new((L,), torch.float32, dev), hip._new((L,), torch.float32, dev))
+        m1, v1, m2, v2 = stats
+        out = hip._new((rows.shape[0], ld), torch.float32, dev)
+        out, z = hip.lognet_fwd(rows, F, D, W, g1, b1, m1, v1, eps1, g2, b2, m2, v2, eps2, train, out)
+        ctx.geom = (F, D, eps1, eps2, train)
+        ctx.save_for_backward(rows, z, W, g1, b1, g2, m1, v1, m2, v2)
+        if not train:
+            return out
+        ctx.mark_non_differentiable(m1, v1, m2, v2)
+        ctx.set_materialize_grads(False)
+        return out, m1, v1, m2, v2
+
+    @staticmethod
+    def backward(ctx, dout, *_):
+        F, D, eps1, eps2, train = ctx.geom
+        rows, z, W, g1, b1, g2, m1, v1, m2, v2 = ctx.saved_tensors
+        if dout is None:
+            return (None,) * (11 + (0 if train else 4))
+        if rows.shape[1] > F * D:  # columns that carry no gradient (dense, padding): the library's own fill
+            dx = hip.zeros(tuple(rows.shape), torch.float32, rows.device)
+        else:
+            dx = None
+        dx, dW, dg1, db1, dg2, db2 = hip.lognet_bwd(_unit_inner(dout), rows, z, F, D, W, g1, b1, m1, v1, eps1, g2, m2, v2, eps2,
+                                                    train, dx=dx)
+        return (dx if ctx.needs_input_grad[0] else None, None, None, None, None, None, dW, dg1, db1, dg2, db2,
+                *(() if train else (None,) * 4))
+
+
+def logarithmic_net(rows, F: int, D: int, coefficient_W, log_bn, exp_bn, pad_to: int = 64):
+    """the input of AFN's dense_layer from the rows [B, >= F D] of the gather: exp_bn(exp(coefficient_W log_bn(log max(|E|,
+    1e-5)))) flattened, as [B, ld] with ld = L D rounded up to pad_to (the padding columns are not written; the Linear that
+    follows reads its in_features columns).  coefficient_W: the bias-free Linear(F, L); log_bn / exp_bn: affine
+    nn.BatchNorm1d(F) / (L), whose running statistics are updated in training mode exactly like nn.BatchNorm1d's (the count
+    is B D).  The shape must satisfy hip.lognet_fits."""
+    W = coefficient_W.weight
+    L = W.shape[0]
+    if coefficient_W.bias is not None or W.shape[1] != F or not hip.lognet_fits(F, D, L):
+        raise RuntimeError(f"logarithmic_net: {F} fields of width {D}, {L} neurons (bias: {coefficient_W.bias is not None}): "
+                           "no kernel form (hip.lognet_fits)")
+    for bn, n in ((log_bn, F), (exp_bn, L)):
+        if type(bn) is not torch.nn.BatchNorm1d or bn.weight is None or bn.bias is None or bn.num_features != n:
+            raise RuntimeError(f"logarithmic_net: an affine nn.BatchNorm1d({n}), got {bn}")
+    batch = [bn.training or not bn.track_running_stats or bn.running_mean is None for bn in (log_bn, exp_bn)]
+    if batch[0] != batch[1]:
+        raise RuntimeError("logarithmic_net: one BatchNorm on batch statistics and one on running statistics")
+    ld = (L * D + pad_to - 1) // pad_to * pad_to if pad_to > 1 else L * D
+    head = (rows, F, D, ld, float(log_bn.eps), float(exp_bn.eps), W, log_bn.weight, log_bn.bias, exp_bn.weight, exp_bn.bias)
+    if not batch[0]:
+        return _LogarithmicNet.apply(*head, log_bn.running_mean, log_bn.running_var, exp_bn.running_mean, exp_bn.running_var)
+    out, m1, v1, m2, v2 = _LogarithmicNet.apply(*head)
+    M = rows.shape[0] * D
+    for bn, m, v in ((log_bn, m1, v1), (exp_bn, m2, v2)):
+        if bn.training and bn.track_running_stats and bn.running_mean is not None:
+            hip.batchnorm_update_running(m, v, bn, M)
+    return out
+
+
+class _PairFC(torch.autograd.Function):
+    """AFN's ensemble head fc(cat[a, d]) for a Linear(2, 1) (ranking/afn.py:81) without the cat: rp_pair_fc_*"""
+
+    @staticmethod
+    def forward(ctx, a, d, w, bias):
+        a, d, w = a.contiguous(), d.contiguous(), w.contiguous()
+        ctx.save_for_backward(a, d, w)
+        return hip.pair_fc_fwd(a, d, w, bias)
+
+    @staticmethod
+    def backward(ctx, dz):
+        a, d, w = ctx.saved_tensors
+        da, dd, dw, db = hip.pair_fc_bwd(dz.contiguous(), a, d, w)
+        return da.view(a.shape), dd.view(d.shape), dw, db
+
+
+def pair_fc(a, d, fc: torch.nn.Linear):
+    """fc(cat[a, d], dim=-1) for a, d [B, 1] and fc = nn.Linear(2, 1), as one launch each way plus the sums' finish"""
+    return _PairFC.apply(a, d, fc.weight, fc.bias)
+
+
 class _DiceGate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, xhat, alpha):

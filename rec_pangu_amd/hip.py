@@ -184,6 +184,16 @@ _SIGNATURES = {
     "rp_bilinear_bwd_workspace_bytes": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_sz)]),
     "rp_bilinear_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32,
                                   _i32, _i32, _i64, _vp, _sz, _vp]),
+    "rp_lognet_fits": (C.c_int, [_i32, _i32, _i32]),
+    "rp_lognet_plan": (C.c_int, [_i64, _i32, _ip, C.POINTER(_i64)]),
+    "rp_lognet_workspace_bytes": (C.c_int, [_i32, _i32, C.POINTER(_sz)]),
+    "rp_lognet_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i64, _i64, _i32, _i32,
+                                _i32, _i32, _vp, _sz, _vp]),
+    "rp_lognet_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _f32, _vp, _i64, _vp, _vp,
+                                _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "rp_pair_fc_partials": (C.c_int, [_i64]),
+    "rp_pair_fc_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "rp_pair_fc_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
     "rp_dice_gate_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp]),
     "rp_dice_gate_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
     "rp_mlp_tail_fits": (C.c_int, [_i32, _i32, _i64]),
@@ -2243,6 +2253,113 @@ def bilinear_bwd(dout, x, F: int, D: int, weights, bilinear_type, senet=None, n_
                                      int(bool(accumulate)), dW.data_ptr(), _ptr(dW1), _ptr(dW2), F, D, R, t, n_dense, B,
                                      ws.data_ptr(), wbytes, _stream()), "rp_bilinear_bwd")
     return dx, dW, dW1, dW2
+
+
+def lognet_fits(F: int, D: int, L: int) -> bool:
+    """do rp_lognet_fwd / rp_lognet_bwd cover F fields of width D and L logarithmic neurons?  (rp_lognet_fits: 1 <= F <= 64,
+    1 <= D <= 256, 1 <= L <= 8 — the shapes whose kernels compile without scratch)"""
+    return bool(lib().rp_lognet_fits(int(F), int(D), int(L)))
+
+
+def lognet_plan(B: int, D: int):
+    """-> (partial workgroups of every reduction of rp_lognet_* over the B D (sample, column) pairs, pairs per workgroup)"""
+    nblk, chunk = C.c_int(0), _i64(0)
+    _check(lib().rp_lognet_plan(int(B), int(D), C.byref(nblk), C.byref(chunk)), "rp_lognet_plan")
+    return nblk.value, chunk.value
+
+
+def _lognet_dims(x, F: int, D: int, W, vecs1, vecs2, wide=()):
+    """the checks rp_lognet_fwd / rp_lognet_bwd share (shapes and types first, the device last) -> L"""
+    for name, t in (("x", x), ("W", W)):
+        if t.dtype is not torch.float32:
+            raise RuntimeError(f"lognet: {name}: expected torch.float32, got {t.dtype}")
+    if W.dim() != 2 or W.shape[1] != F or not W.is_contiguous():
+        raise RuntimeError(f"lognet: W {tuple(W.shape)} for F = {F}: expected a contiguous [L, F]")
+    L = W.shape[0]
+    if x.dim() != 2 or x.shape[1] < F * D or (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < F * D):
+        raise RuntimeError(f"lognet: x {tuple(x.shape)} / strides {x.stride()}: rows narrower than F D = {F * D}")
+    for n, vecs in ((F, vecs1), (L, vecs2)):
+        for v in vecs:
+            if v.dtype is not torch.float32 or v.numel() != n or not v.is_contiguous():
+                raise RuntimeError(f"lognet: a BatchNorm vector of {v.numel()} {v.dtype} elements, expected {n} contiguous "
+                                   "torch.float32")
+    for name, buf, cols in wide:
+        if buf.dtype is not torch.float32 or buf.dim() != 2 or buf.shape[0] != x.shape[0] or buf.shape[1] < cols \
+                or (buf.shape[1] > 1 and buf.stride(1) != 1):
+            raise RuntimeError(f"lognet: {name} {tuple(buf.shape)} {buf.dtype} for B = {x.shape[0]}: rows narrower than {cols}")
+    if not lognet_fits(F, D, L):
+        raise RuntimeError(f"lognet: F={F} D={D} L={L}: outside rp_lognet_fits")
+    for t in (x, W, *vecs1, *vecs2, *[buf for _, buf, _ in wide]):
+        _req(t, torch.float32, "lognet")
+    return L
+
+
+def lognet_fwd(x, F: int, D: int, W, gamma1, beta1, mean1, var1, eps1: float, gamma2, beta2, mean2, var2, eps2: float,
+               train: bool, out):
+    """AFN's logarithmic net on the rows x [B, >= F D] (read in place): out[:, :L D] = BN2(exp(W BN1(log max(|x|, 1e-5)))) and
+    z [B, L D] (for the backward).  train: mean1 / var1 [F] and mean2 / var2 [L] are WRITTEN with the batch statistics
+    (biased variances); otherwise they are read.  rp_lognet_fwd: 5 launches with batch statistics, 1 without."""
+    L = _lognet_dims(x, F, D, W, (gamma1, beta1, mean1, var1), (gamma2, beta2, mean2, var2), wide=[("out", out, W.shape[0] * D)])
+    B, dev = x.shape[0], x.device
+    z = _new((B, L * D), torch.float32, dev)
+    ws, wbytes = _workspace("lognet", F, L, device=dev)
+    with _Timed("lognet_fwd", f"{B}x{F}.{D}.{L}", 4 * B * (F * D + L * D)):
+        _check(lib().rp_lognet_fwd(x.data_ptr(), _rowmajor(x, "x"), W.data_ptr(), gamma1.data_ptr(), beta1.data_ptr(),
+                                   mean1.data_ptr(), var1.data_ptr(), eps1, gamma2.data_ptr(), beta2.data_ptr(), mean2.data_ptr(),
+                                   var2.data_ptr(), eps2, z.data_ptr(), out.data_ptr(), _rowmajor(out, "out"), B, F, D, L,
+                                   int(train), ws.data_ptr(), wbytes, _stream()), "rp_lognet_fwd")
+    return out, z
+
+
+def lognet_bwd(dout, x, z, F: int, D: int, W, gamma1, beta1, mean1, var1, eps1: float, gamma2, mean2, var2, eps2: float,
+               train: bool, dx=None):
+    """-> (dx, dW [L, F], dgamma1, dbeta1 [F], dgamma2, dbeta2 [L]) of lognet_fwd with the statistics it used (rp_lognet_bwd).
+    dx: a [B, >= F D] buffer whose first F D columns are written (the others are the caller's)."""
+    L = _lognet_dims(x, F, D, W, (gamma1, beta1, mean1, var1), (gamma2, mean2, var2),
+                     wide=[("dout", dout, W.shape[0] * D)] + ([("dx", dx, F * D)] if dx is not None else []))
+    B, dev = x.shape[0], x.device
+    if z.shape != (B, L * D) or not z.is_contiguous():
+        raise RuntimeError(f"lognet_bwd: z {tuple(z.shape)} for B = {B}, L D = {L * D}")
+    if dx is None:
+        dx = _new((B, F * D), torch.float32, dev)
+    dW = _new((L, F), torch.float32, dev)
+    dg1, db1 = _new((F,), torch.float32, dev), _new((F,), torch.float32, dev)
+    dg2, db2 = _new((L,), torch.float32, dev), _new((L,), torch.float32, dev)
+    ws, wbytes = _workspace("lognet", F, L, device=dev)
+    with _Timed("lognet_bwd", f"{B}x{F}.{D}.{L}", 4 * B * (2 * F * D + 2 * L * D)):
+        _check(lib().rp_lognet_bwd(dout.data_ptr(), _rowmajor(dout, "dout"), x.data_ptr(), _rowmajor(x, "x"), z.data_ptr(),
+                                   W.data_ptr(), gamma1.data_ptr(), beta1.data_ptr(), mean1.data_ptr(), var1.data_ptr(), eps1,
+                                   gamma2.data_ptr(), mean2.data_ptr(), var2.data_ptr(), eps2, dx.data_ptr(), _rowmajor(dx, "dx"),
+                                   dW.data_ptr(), dg1.data_ptr(), db1.data_ptr(), dg2.data_ptr(), db2.data_ptr(), B, F, D, L,
+                                   int(train), ws.data_ptr(), wbytes, _stream()), "rp_lognet_bwd")
+    return dx, dW, dg1, db1, dg2, db2
+
+
+def pair_fc_fwd(a, d, w, bias):
+    """z [B, 1] = w[0, 0] a + w[0, 1] d + bias: nn.Linear(2, 1) over cat[a, d] without the cat (rp_pair_fc_fwd)"""
+    B = _pair_vectors((a, d), ("a", "d"))
+    _req(w, torch.float32, "pair_fc: weight")
+    _req(bias, torch.float32, "pair_fc: bias")
+    if w.numel() != 2 or bias.numel() != 1 or not w.is_contiguous():
+        raise RuntimeError(f"pair_fc: weight {tuple(w.shape)} / bias {tuple(bias.shape)}: expected a Linear(2, 1)")
+    z = _new((B, 1), torch.float32, a.device)
+    with _Timed("pair_fc_fwd"):
+        _check(lib().rp_pair_fc_fwd(a.data_ptr(), d.data_ptr(), w.data_ptr(), bias.data_ptr(), z.data_ptr(), B, _stream()),
+               "rp_pair_fc_fwd")
+    return z
+
+
+def pair_fc_bwd(dz, a, d, w):
+    """-> (da [B, 1], dd [B, 1], dw [1, 2], dbias [1]) of pair_fc_fwd (rp_pair_fc_bwd: deterministic two-stage sums)"""
+    B = _pair_vectors((dz, a, d), ("dz", "a", "d"))
+    dev = a.device
+    da, dd = _new((B, 1), torch.float32, dev), _new((B, 1), torch.float32, dev)
+    dw, db = _new((1, 2), torch.float32, dev), _new((1,), torch.float32, dev)
+    partial = _new((lib().rp_pair_fc_partials(B),), torch.float32, dev)
+    with _Timed("pair_fc_bwd"):
+        _check(lib().rp_pair_fc_bwd(dz.data_ptr(), a.data_ptr(), d.data_ptr(), w.data_ptr(), da.data_ptr(), dd.data_ptr(),
+                                    dw.data_ptr(), db.data_ptr(), partial.data_ptr(), B, _stream()), "rp_pair_fc_bwd")
+    return da, dd, dw, db
 
 
 def dice_gate_fwd(x, xhat, alpha):

@@ -11,5 +11,7 @@ from .aoanet import AOANet
 from .ccpm import CCPM
 from .fibinet import FiBiNet
 from .afm import AFM
+from .afn import AFN
 
-__all__ = ["DeepFM", "xDeepFM", "DCN", "AutoInt", "FM", "WDL", "NFM", "LR", "MaskNet", "AOANet", "CCPM", "FiBiNet", "AFM"]
+__all__ = ["DeepFM", "xDeepFM", "DCN", "AutoInt", "FM", "WDL", "NFM", "LR", "MaskNet", "AOANet", "CCPM", "FiBiNet", "AFM",
+           "AFN"]
