@@ -779,6 +779,40 @@ int rp_loss_finish(const float *partial, int n, float scale, float *loss, rp_str
 int rp_sigmoid_bce_bwd(const float *pred, const float *label, const float *gloss, int64_t B, float p_eps,
                        float weight, int apply_sigmoid, float *dz, rp_stream_t stream);
 
+/* ---- epoch metrics: binary ROC-AUC as an exact rational + the float64 log-loss sum (csrc/metrics.hip) ----------------------
+ * replaces the .cpu() of every prediction + sklearn's roc_auc_score / log_loss at the end of model_pipeline.py's loops.
+ *   pred, label  float[n] on the device, 1 <= n < 2^31 - 1
+ *   two_u        sum over the positives (label == 1) of #negatives (label == 0) with a smaller prediction
+ *                + #negatives with a smaller or equal one: AUC = two_u / (2 P N), ties counted as halves, exact integers
+ *   P, N         counts of label == 1 / label == 0
+ *   unsupported  elements whose prediction is not finite or whose label is neither 0 nor 1 (the caller then takes its
+ *                host path: the other fields are computed all the same but mean nothing)
+ *   logloss_sum  sum of -(label == 1 ? log q : log(1 - q)), q = min(max((double)pred, eps), 1 - eps), in float64, added in
+ *                a fixed order (no atomics): two calls give the same bits.  Divide by n for the mean.
+ * flags: RP_METRIC_AUC | RP_METRIC_LOGLOSS, what to compute (the counts always are; log-loss alone skips the sort and
+ * leaves two_u = 0).  RP_METRICS_STAGE_* bits, for measurements only: issue just those launches (none = all of them);
+ * stages issued one call after the other over the same workspace give the result of one whole call.
+ * Kernel launches only, on `stream`; result is device memory (8-byte aligned) — one 40-byte copy brings everything back.
+ * Nothing is allocated: workspace from rp_metrics_workspace_bytes(n) (~21 n bytes).  pred, label, result and the workspace
+ * must not overlap. */
+typedef struct {
+    int64_t two_u, P, N, unsupported;
+    double logloss_sum;
+} rp_binary_metrics_result;
+#define RP_METRIC_AUC 1
+#define RP_METRIC_LOGLOSS 2
+#define RP_METRICS_STAGE_KEY 0x100
+#define RP_METRICS_STAGE_SORT 0x200
+#define RP_METRICS_STAGE_TILE_SUMS 0x400
+#define RP_METRICS_STAGE_TILE_SCAN 0x800
+#define RP_METRICS_STAGE_GROUP_NEG 0x1000
+#define RP_METRICS_STAGE_RANK 0x2000
+#define RP_METRICS_STAGE_FINISH 0x4000
+#define RP_METRICS_STAGE_ALL 0x7F00
+int rp_metrics_workspace_bytes(int64_t n, size_t *bytes);
+int rp_binary_metrics(void *workspace, size_t workspace_bytes, const float *pred, const float *label, int64_t n, double eps,
+                      int flags, rp_binary_metrics_result *result, rp_stream_t stream);
+
 /* ---- two-task loss heads that couple the tasks ---------------------------------------------------------------------------
  * replaces multi_task/essm.py:69-75 and multi_task/aitm.py:84-100 (and the two sigmoids in front of them).
  *   p_i = sigmoid(z_i) (apply_sigmoid) or z_i;  BCE = mean over the batch, ATen's form (logs clamped at -100)

@@ -243,6 +243,8 @@ _SIGNATURES = {
     "rp_seq_pool_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "rp_lazy_adam_cf_terms": (C.c_int, [_f64, C.POINTER(C.c_int)]),
     "rp_lazy_adam_cf_table": (C.c_int, [_vp, _i64, _i64, _f64, _f64, _vp, _i64, _i64, _vp, _vp]),
+    "rp_metrics_workspace_bytes": (C.c_int, [_i64, C.POINTER(_sz)]),
+    "rp_binary_metrics": (C.c_int, [_vp, _sz, _vp, _vp, _i64, _f64, _i32, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 
@@ -599,6 +601,50 @@ def sort_pairs(keys: torch.Tensor, end_bit: int = 32, out=None, workspace=None):
         _check(lib().rp_sort_pairs_i32(ws.data_ptr(), nbytes, keys.data_ptr(), ko.data_ptr(), po.data_ptr(), n,
                                    end_bit, _stream()), "rp_sort_pairs_i32")
     return ko, po
+
+
+METRIC_AUC, METRIC_LOGLOSS = 1, 2
+# the launches of rp_binary_metrics in issue order: name -> RP_METRICS_STAGE_* bit (a measurement issues them one by one)
+METRICS_STAGES = {"key": 0x100, "sort": 0x200, "tile_sums": 0x400, "tile_scan": 0x800, "group_neg": 0x1000, "rank": 0x2000,
+                  "finish": 0x4000}
+
+
+def metrics_workspace(n: int, device) -> torch.Tensor:
+    return _workspace("metrics", n, device=device)[0]
+
+
+def metrics_stage_bytes(n: int, flags: int = METRIC_AUC | METRIC_LOGLOSS) -> dict:
+    """algorithmic bytes of each launch group of rp_binary_metrics over n elements (csrc/metrics.hip; T = tiles of 4096)"""
+    T = -(-n // 4096)
+    auc = bool(flags & METRIC_AUC)
+    out = {"key": n * (8 + (4 if auc else 0)) + 20 * T, "finish": (20 + (8 if auc else 0)) * T + 40}
+    if auc:
+        # the sort: 4 digit passes, each reads the keys twice (histogram, scatter) and the values once (implicit in the
+        # first pass) and writes both columns
+        out.update({"sort": n * 4 * (4 * 2 + 3 + 4 * 2), "tile_sums": n * (4 + 4 + 4 + 1) + 8 * T, "tile_scan": 16 * T,
+                    "group_neg": n * (4 + 1 + 4) + 8 * T, "rank": n * (4 + 1 + 4) + 12 * T})
+    return out
+
+
+def binary_metrics(pred: torch.Tensor, label: torch.Tensor, flags: int = METRIC_AUC | METRIC_LOGLOSS, eps: float = 1e-7,
+                   workspace=None, result=None, stages=None) -> torch.Tensor:
+    """rp_binary_metrics over float32 [n] device tensors -> the DEVICE result, int64 [5] = (two_u, P, N, unsupported, the
+    bits of the float64 log-loss sum); nothing here waits for the device — the caller's one copy of the 40 bytes does.
+    stages: names from METRICS_STAGES, issued as one call each under their own timing rows (measurements; needs the same
+    workspace and result across the calls)."""
+    _req(pred, torch.float32, "pred")
+    _req(label, torch.float32, "label")
+    n = pred.numel()
+    if label.numel() != n or not pred.is_contiguous() or not label.is_contiguous():
+        raise RuntimeError("binary_metrics: pred and label must be contiguous and of one length")
+    ws, _ = _workspace("metrics", n, device=pred.device, given=workspace)
+    res = _new((5,), torch.int64, pred.device) if result is None else result
+    sizes = metrics_stage_bytes(n, flags)
+    for tag, bits in ([(None, 0)] if stages is None else [(s, METRICS_STAGES[s]) for s in stages]):
+        with _Timed("binary_metrics", tag, sizes.get(tag, 0) if tag else sum(sizes.values())):
+            _check(lib().rp_binary_metrics(ws.data_ptr(), ws.numel(), pred.data_ptr(), label.data_ptr(), n, eps, flags | bits,
+                                           res.data_ptr(), _stream()), "rp_binary_metrics")
+    return res
 
 
 _SORT_FIELDS: dict = {}

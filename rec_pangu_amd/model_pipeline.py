@@ -5,7 +5,8 @@ same returned keys (`train_roc_auc_score`, `train_log_loss`, `roc_auc_score`, `l
 `train_task{i}_*`, `test_task{i}_*`), same 4-decimal rounding and log-loss clipping (eps=1e-7).
 Two things differ, neither changes a returned number: predictions stay on the device until the end of
 the epoch (the reference does a .cpu() round trip every iteration, model_pipeline.py:60-61), and the
-running "last 1000" AUC is only computed on the iterations that log it.
+running "last 1000" AUC is only computed on the iterations that log it.  Predictions on the HIP device
+do not come back at all: their epoch metrics are computed there (rec_pangu_amd/metrics.py).
 """
 import logging
 import time
@@ -15,6 +16,8 @@ import numpy as np
 import torch
 from sklearn.metrics import roc_auc_score
 from sklearn.metrics import log_loss as _sk_log_loss
+
+from . import metrics as _device_metrics
 
 logger = logging.getLogger("rec_pangu_amd")
 SUPPORTED_METRICS = ['roc_auc_score', 'log_loss']
@@ -37,6 +40,19 @@ def _to_host(chunks):
     if not chunks:
         return np.zeros((0,), dtype=np.float32)
     return torch.cat([c.reshape(-1) for c in chunks]).cpu().numpy()
+
+
+def _epoch_metrics(label_chunks, pred_chunks, metric_list) -> dict:
+    """{metric: its 4-decimal value} over one task's chunks of an epoch.  Chunks on the HIP device are joined there and go
+    to rec_pangu_amd.metrics (40 bytes come back instead of every prediction; what the kernels do not define — one-class
+    labels, a NaN — takes the host path inside it, on the same data); host chunks take the host path as ever."""
+    if pred_chunks and all(c.is_cuda for c in pred_chunks) and all(c.is_cuda for c in label_chunks):
+        y = torch.cat([c.reshape(-1) for c in label_chunks])
+        p = torch.cat([c.reshape(-1) for c in pred_chunks])
+        vals = _device_metrics.binary_metrics(y, p, metric_list)
+        return {metric: round(vals[metric], 4) for metric in metric_list}
+    y, p = _to_host(label_chunks), _to_host(pred_chunks)
+    return {metric: _metric(metric, y, p) for metric in metric_list}
 
 
 def _move(data, device):
@@ -105,10 +121,10 @@ def train_model(model, train_loader, optimizer, device, metric_list: List[str] =
     _check_indices(model)
     res = dict()
     for i in tasks:
-        y, p = _to_host(labels[i]), _to_host(preds[i])
+        vals = _epoch_metrics(labels[i], preds[i], metric_list)
         for metric in metric_list:
             key = f'train_{metric}' if num_task == 1 else f'train_task{i + 1}_{metric}'
-            res[key] = _metric(metric, y, p)
+            res[key] = vals[metric]
     return res
 
 
@@ -128,10 +144,10 @@ def _train_model_graphed(model, train_loader, device, metric_list, num_task, log
     _check_indices(model)
     res = dict()
     for i in tasks:
-        y, p = _to_host(labels[i]), _to_host(preds[i])
+        vals = _epoch_metrics(labels[i], preds[i], metric_list)
         for metric in metric_list:
             key = f'train_{metric}' if num_task == 1 else f'train_task{i + 1}_{metric}'
-            res[key] = _metric(metric, y, p)
+            res[key] = vals[metric]
     return res
 
 
@@ -151,10 +167,10 @@ def test_model(model, test_loader, device, metric_list: List[str] = ['roc_auc_sc
     _check_indices(model)
     res = dict()
     for i in tasks:
-        y, p = _to_host(labels[i]), _to_host(preds[i])
+        vals = _epoch_metrics(labels[i], preds[i], metric_list)
         for metric in metric_list:
             key = metric if num_task == 1 else f'test_task{i + 1}_{metric}'
-            res[key] = _metric(metric, y, p)
+            res[key] = vals[metric]
     return res
 
 
