@@ -25,6 +25,7 @@ import torch
 from torch import nn
 
 from ... import functional as Fh
+from ...grad_arena import GradArena
 
 
 class SortedLookup:
@@ -193,10 +194,7 @@ class EmbeddingLayer(nn.Module):
                 self.embedding_layer.update({col: emb})
                 off += r
         self._arena = arena
-        self._grad_arena: Optional[torch.Tensor] = None
-        self._touched: Optional[torch.Tensor] = None  # sorted keys written by the last backward
-        self._grad_clean = True  # gradient arena known to be all zero
-        self._noclear_ok = True  # every gradient launch of this layer writes ALL rows of its key list (LazyAdamRows.replay)
+        self.grads = GradArena(overwrites=True)  # (every gradient launch of this layer writes ALL rows of its key list)
         self._dev_meta = None
         self._lazy = None        # optim.LazyAdamRows when the optimiser runs the exact lazy dense Adam
         self._presorted = None   # the SortedLookup of the batch being looked up
@@ -252,7 +250,7 @@ class EmbeddingLayer(nn.Module):
         memo[id(self)] = new
         new.__setstate__({k: copy.deepcopy(v, memo) for k, v in self.__dict__.items()})
         new._point_at(new._arena)  # (same values: the arena copy and the table clones were taken from the same memory)
-        if new._grad_arena is not None and self._grads_are_ours():
+        if new.grads.buf is not None and self._grads_are_ours():
             new._attach_grads()
         return new
 
@@ -263,10 +261,9 @@ class EmbeddingLayer(nn.Module):
         self._point_at(fn(self._arena))
         if self._lazy is not None:
             self._lazy.apply(fn)
-        if self._grad_arena is not None:
-            self._grad_arena = fn(self._grad_arena)
+        self.grads.apply(fn)
+        if self.grads.buf is not None:
             self._attach_grads()
-        self._touched = None if self._touched is None else fn(self._touched)
         if self.__dict__.get("_shadow") is not None:
             self._shadow_stamp = None  # (rebuilt from the moved tables at the next training forward)
         return self
@@ -299,7 +296,7 @@ class EmbeddingLayer(nn.Module):
                               dim=0).contiguous()
         self.embedding_dim = arena.shape[1]
         self._point_at(arena)
-        self._grad_arena, self._touched, self._grad_clean = None, None, True
+        self.grads.drop()
         self._rows_sig_cache = None
         if self._lazy is not None and self._lazy.m.shape != arena.shape:
             self._lazy = None
@@ -338,14 +335,14 @@ class EmbeddingLayer(nn.Module):
         for p in self._tables():
             r = p.shape[0]
             if p.requires_grad:  # a frozen table (set_weights(trainable=False)) never shows a gradient
-                view = self._grad_arena[off:off + r]
+                view = self.grads.buf[off:off + r]
                 # (deferred lazy Adam: the rows of other steps wait in this arena — computing with the view raises)
                 p.grad = view.as_subclass(DeferredGradView) if guard else view
             off += r
 
     @property
     def grad_arena(self):
-        return self._grad_arena
+        return self.grads.buf
 
     def grads_are_arena(self) -> bool:
         """True when every table's .grad is the matching view of the gradient arena."""
@@ -353,10 +350,10 @@ class EmbeddingLayer(nn.Module):
 
     def grads_were_zeroed(self):
         """FusedAdam(fuse_zero_grad) cleared the whole gradient arena."""
-        self._touched, self._grad_clean = None, True
+        self.grads.zeroed()
 
     def _grads_are_ours(self) -> bool:
-        g, D = self._grad_arena, self.embedding_dim
+        g, D = self.grads.buf, self.embedding_dim
         if g is None:
             return False
         off = 0
@@ -435,37 +432,19 @@ class EmbeddingLayer(nn.Module):
         if forms is not None and forms.big:
             look.mark(n // F, forms.big, forms.skip if forms.ss_ahead else None)
 
-    # The three backward passes below share their opening and closing.  Invariant kept between steps: the gradient arena is
-    # zero everywhere except the rows listed in `_touched`, so a fresh gradient costs a sparse re-zero, not an 8.6 GB fill.
+    # The three backward passes below share their opening and closing: the protocol of the gradient arena (grad_arena.py).
     def _grad_begin(self, keys, presorted):
-        """the gradient arena allocated or sparsely re-zeroed, the sort taken or made -> (the SortedLookup, whether the tables'
-        .grad views have to be attached at the end)"""
+        """the gradient arena allocated or sparsely re-zeroed, the sort taken or made, the catch-up launch's promise settled
+        -> (the SortedLookup, whether the tables' .grad views have to be attached at the end, whether the launches accumulate)"""
         from ... import hip
         fresh = not self._grads_are_ours()
-        if self._grad_arena is None or self._grad_arena.shape != self._arena.shape \
-                or self._grad_arena.device != self._arena.device:
-            self._grad_arena = torch.zeros_like(self._arena)
-            self._touched, self._grad_clean = None, True
-        elif fresh and not self._grad_clean:
-            # zero_grad() dropped the .grad views: clear the rows the previous backward wrote
-            if self._touched is not None:
-                hip.zero_rows(self._touched, self.embedding_dim, self._grad_arena)
-            else:
-                self._grad_arena.zero_()
-            self._touched, self._grad_clean = None, True
+        acc = self.grads.open(self._arena, fresh)
         look = presorted if presorted is not None else SortedLookup(keys, *hip.sort_pairs(keys, end_bit=self._meta()[3]))
-        if self._lazy is not None and self._lazy._noclear is not None:
-            # the catch-up launch in front of this step's forward left its applied gradient rows uncleared, counting on
-            # THIS launch to overwrite them (LazyAdamRows.replay): kept if it writes that key list without accumulating
-            self._lazy.resolve_noclear(self, look.sk if self._grad_clean else None)
-        return look, fresh
+        self.grads.settle(look.sk)
+        return look, fresh, acc
 
     def _grad_end(self, sk, fresh: bool) -> None:
-        if self._touched is None:
-            self._touched, self._touched_unsorted = sk, False
-        else:  # several backward passes before one optimiser step: the union is no longer sorted
-            self._touched, self._touched_unsorted = torch.cat([self._touched, sk]), True
-        self._grad_clean = False
+        self.grads.close(sk)
         if fresh:
             self._attach_grads()
 
@@ -474,9 +453,9 @@ class EmbeddingLayer(nn.Module):
         (aten::embedding_dense_backward: every table gets a full [V+1, D] gradient, zeros where no
         sample looked) — the plain segmented reduce of dx [B, ldx]."""
         from ... import hip
-        look, fresh = self._grad_begin(keys, presorted)
-        hip.embed_grad_reduce(look.sk, look.sp, B, self.embedding_dim, dx, gfm, ssum, self._arena, self._grad_arena,
-                              accumulate=not self._grad_clean)
+        look, fresh, acc = self._grad_begin(keys, presorted)
+        hip.embed_grad_reduce(look.sk, look.sp, B, self.embedding_dim, dx, gfm, ssum, self._arena, self.grads.buf,
+                              accumulate=acc)
         self._grad_end(look.sk, fresh)
 
     def pool_grad(self, field: int, ids, g, inv, bag, L: int, presorted=None):
@@ -485,9 +464,8 @@ class EmbeddingLayer(nn.Module):
         from ... import hip
         keys = None if presorted is not None else \
             hip.embed_keys(self.row_base[field:field + 1], self.row_count[field:field + 1], [ids], self.err_flag)
-        look, fresh = self._grad_begin(keys, presorted)
-        hip.embed_pool_bwd(look.sk, look.sp, self.embedding_dim, g, inv, bag, L, self._grad_arena,
-                           accumulate=not self._grad_clean)
+        look, fresh, acc = self._grad_begin(keys, presorted)
+        hip.embed_pool_bwd(look.sk, look.sp, self.embedding_dim, g, inv, bag, L, self.grads.buf, accumulate=acc)
         self._grad_end(look.sk, fresh)
 
     def first_layer_grad(self, keys, B: int, dh, wt, gfm, ssum, presorted=None, dx=None, w=None, dw=None):
@@ -513,11 +491,10 @@ class EmbeddingLayer(nn.Module):
         if dw is not None and not field_major:
             raise RuntimeError("the fused first layer stored no activation, but its backward is not the field-major "
                                "single-device form rp_embed_grad_seg covers")
-        look, fresh = self._grad_begin(keys, presorted)
+        look, fresh, acc = self._grad_begin(keys, presorted)
         # the tiny form only for the field-major all-fields call; the big one only with (w, dw) and where dh suits the kernel
         forms = self._forms(B, tiny=field_major, big=dw is not None and hip.embed_grad_smp_fits(D, 64, dh))
-        acc = not self._grad_clean
-        to = (gfm, ssum, self._arena, self._grad_arena)
+        to = (gfm, ssum, self._arena, self.grads.buf)
 
         def tiny():
             hip.embed_grad_tiny(keys, B, forms.tiny, dh, wt, *to, accumulate=acc, dw=dw)

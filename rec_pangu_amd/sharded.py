@@ -33,6 +33,7 @@ import torch.distributed as dist
 from torch import nn
 
 from . import functional as Fh
+from .grad_arena import GradArena
 
 
 _STAGED: dict = {}
@@ -506,8 +507,10 @@ class ShardedEmbeddingLayer(nn.Module):
         self.lbits = max(1, int((self.total_rows + world - 1) // world).bit_length())  # bits of a local row id
         self.register_buffer("_row_base", torch.tensor(base, dtype=torch.int64, device=device), persistent=False)
         self.register_buffer("_row_count", torch.tensor(rows, dtype=torch.int64, device=device), persistent=False)
-        self._touched, self._touched_unsorted = None, False
-        self._grad_buf = None
+        # the owner-side gradient launch (rp_embed_grad_reduce over the sorted rows this rank was asked for) writes EVERY row of
+        # its key list — the list the catch-up launch in front of the lookup stamped: that launch may leave the gradient rows it
+        # applied uncleared, as on the single-device path (grad_arena.py)
+        self.grads = GradArena(overwrites=True)
         self._lazy = None
         self._served_sorted = None  # (sorted local rows, positions) of the requests being served, reused in backward
         self._err = None
@@ -519,10 +522,6 @@ class ShardedEmbeddingLayer(nn.Module):
         self._capacity = None  # per-owner slots of the fixed-capacity exchange (check_indices == "deferred", HIP)
         self._capacity_n = 0   # requests of the (largest) batch the capacity was measured on
         self._prepared = None  # (route, requested rows, their sort) of the batch about to be looked up, as far as prepared ahead
-        # the owner-side gradient launch (rp_embed_grad_reduce over the sorted rows this rank was asked for) writes EVERY row of
-        # its key list — the list the catch-up launch in front of the lookup stamped: that launch may leave the gradient rows it
-        # applied uncleared (1 of its 8 row transfers; LazyAdamRows.replay, as on the single-device path)
-        self._noclear_ok = True
         self._scaled = None     # per-lookup flag shared by _ShardedRows and _RowsToLinear (who applies the 1/G)
         self._announced = None  # the batch of the next step (prefetch_sort), until its route is started
         self._ahead = None      # (id tensors, versions, route, event[, requested rows, their sort]) prepared on the side stream
@@ -560,7 +559,7 @@ class ShardedEmbeddingLayer(nn.Module):
     # ---- the "store" protocol FusedAdam / LazyAdamRows use (same as EmbeddingLayer) ------------------------
     @property
     def grad_arena(self):
-        return self._grad_buf
+        return self.grads.buf
 
     def table_parameters(self):
         return [self.local_arena]
@@ -569,16 +568,11 @@ class ShardedEmbeddingLayer(nn.Module):
         return (None, None, None, max(1, int(self.local_arena.shape[0] - 1).bit_length()))
 
     def grads_are_arena(self) -> bool:
-        g = self.local_arena.grad
-        return g is not None and self._grad_buf is not None and g.data_ptr() == self._grad_buf.data_ptr()
+        g, buf = self.local_arena.grad, self.grads.buf
+        return g is not None and buf is not None and g.data_ptr() == buf.data_ptr()
 
     def grads_were_zeroed(self):
-        self._touched, self._touched_unsorted = None, False
-
-    @property
-    def _grad_clean(self) -> bool:
-        """the next owner-side gradient launch overwrites (no backward has written since the last zero_grad / fused step)"""
-        return self._grad_buf is not None and self._touched is None
+        self.grads.zeroed()
 
     def flush_lazy(self):
         if self._lazy is not None:
@@ -767,30 +761,18 @@ class ShardedEmbeddingLayer(nn.Module):
         if p.is_cuda:
             from . import hip
             fresh = not self.grads_are_arena()
-            if self._grad_buf is None or self._grad_buf.shape != p.shape or self._grad_buf.device != p.device:
-                self._grad_buf = torch.zeros_like(p)
-                self._touched, self._touched_unsorted = None, False
-            elif fresh and self._touched is not None:
-                hip.zero_rows(self._touched, self.embedding_dim, self._grad_buf)  # zero_grad() dropped the old rows
-                self._touched, self._touched_unsorted = None, False
-            clean = self._touched is None
+            acc = self.grads.open(p, fresh)
             if rows_idx.numel():
                 if presorted is not None:
                     sk, sp = presorted
                 else:
                     sk, sp = hip.sort_pairs(self._rows_i32(rows_idx), end_bit=self._meta()[3])
-                if self._lazy is not None and self._lazy._noclear is not None:
-                    # the catch-up in front of this step's lookup left its applied gradient rows uncleared, counting on THIS
-                    # launch to overwrite them: kept if it writes that very key list without accumulating
-                    self._lazy.resolve_noclear(self, sk if clean else None)
+                self.grads.settle(sk)
                 hip.embed_grad_reduce(sk, sp, rows_idx.numel(), self.embedding_dim, g, None, None, None,
-                                      self._grad_buf, accumulate=not clean)
-                if self._touched is None:
-                    self._touched, self._touched_unsorted = sk, False
-                else:
-                    self._touched, self._touched_unsorted = torch.cat([self._touched, sk]), True
+                                      self.grads.buf, accumulate=acc)
+                self.grads.close(sk)
             if fresh:
-                p.grad = self._grad_buf
+                p.grad = self.grads.buf
         else:
             upd = torch.zeros_like(p).index_add_(0, rows_idx, g)
             p.grad = upd if p.grad is None else p.grad + upd

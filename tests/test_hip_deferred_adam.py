@@ -232,8 +232,7 @@ def test_uncleared_catchup_rows_when_the_promised_backward_does_not_come():
                 plain_launches.append(hip.launch_count() - n0)
             preds.append(out["pred"].detach().clone())
         if defer:
-            lz = model.embedding_layer._lazy
-            assert lz._noclear is None
+            assert model.embedding_layer.grads.promised is None
             assert len(set(plain_launches)) == 1, plain_launches  # (no clearing launch sneaks into a plain step)
         runs.append((preds, _state(model, opt)))
         if defer:

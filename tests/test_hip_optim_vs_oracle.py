@@ -26,19 +26,24 @@ def _gpu():
 
 
 class _Store:
-    """the "store" protocol LazyAdamRows drives (what EmbeddingLayer / ShardedEmbeddingLayer implement)"""
+    """the store protocol LazyAdamRows drives (rec_pangu_amd/grad_arena.py: what EmbeddingLayer / ShardedEmbeddingLayer
+    implement), as far as LazyAdamRows itself uses it.  Its backward is an index_add_: it ACCUMULATES, so the catch-up launch
+    may never leave a row uncleared (overwrites=False)."""
 
     def __init__(self, p):
+        from rec_pangu_amd.grad_arena import GradArena
         self.arena = p
-        self.grad_arena = torch.zeros_like(p)
         self.embedding_dim = p.shape[1]
-        self._touched, self._touched_unsorted, self._lazy = None, False, None
+        self.grads, self._lazy = GradArena(overwrites=False), None
+        self.grads.open(p, fresh=False)
+
+    grad_arena = property(lambda self: self.grads.buf)
 
     def _meta(self):
         return (None, None, None, max(1, int(self.arena.shape[0] - 1).bit_length()))
 
     def grads_were_zeroed(self):
-        self._touched, self._touched_unsorted = None, False
+        self.grads.zeroed()
 
 
 def _schedule(R, D, steps, seed):
@@ -84,11 +89,10 @@ def test_device_lazy_adam_follows_the_protocol_oracle(defer, replay, steps, R, D
 
     def backward(rows, g_rows, sk):
         oracle.backward(rows, g_rows)
+        store.grads.open(store.arena, fresh=False)
+        store.grads.settle(sk)
         store.grad_arena.index_add_(0, rows.to(DEV), g_rows.to(DEV))
-        if store._touched is None:
-            store._touched, store._touched_unsorted = sk, False
-        else:
-            store._touched, store._touched_unsorted = torch.cat([store._touched, sk]), True
+        store.grads.close(sk)
 
     for i, s in enumerate(_schedule(R, D, steps, seed=3)):
         sk = forward(s["rows"], True)
