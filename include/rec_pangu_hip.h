@@ -889,6 +889,44 @@ int rp_embed_pool_bwd(const int32_t *sorted_keys, const int32_t *sorted_pos, int
 int rp_seq_pool_fwd(const float *e, int64_t B, int64_t L, int D, int mode, float *out, float *inv_out, rp_stream_t stream);
 int rp_seq_pool_bwd(const float *g, const float *inv, int64_t B, int64_t L, int D, float *de, rp_stream_t stream);
 
+/* ---- sequence recall: the full-softmax loss head and the masked history mean (csrc/softmax_ce.hip, csrc/pool.hip) --------
+ * rp_softmax_ce_fwd / _bwd replace SequenceBaseModel.calculate_loss (rec_pangu/models/base_model.py:124-138:
+ *   scores = user_emb @ item_emb.weight.T  [B, V];  loss = CrossEntropyLoss()(scores, target)) and its autograd, which keeps
+ * the logits, the softmax and their gradient — three [B, V] tensors.  Here none exists:
+ *   U [B, ldu >= D] fp32, E [V, D] fp32 contiguous, target int64 [B] in [0, V), s[b, v] = sum_d U[b, d] E[v, d]
+ *   fwd:  lse[b] = log sum_v exp(s[b, v]) (float[B]),  loss[0] = (1/B) sum_b (lse[b] - s[b, target[b]])
+ *   bwd:  with p'[b, v] = exp(s[b, v] - lse[b]) - [v == target[b]] and g = gloss[0] (device float):
+ *         dU[b, :] = (g/B) sum_v p'[b, v] E[v, :]   ([B, lddu >= D], or NULL)
+ *         dE[v, :] = (g/B) sum_b p'[b, v] U[b, :]   ([V, D] contiguous, or NULL)
+ * A target outside [0, V) sets *err_flag and counts as item 0 (the reference raises IndexError).  Score tiles are formed on
+ * the bf16 matrix core from split-bf16 operands (product count: rp_set_matmul_precision; the automatic mode runs the
+ * fp32-faithful six); no floating-point atomics, results are bit-identical from run to run.  1 <= D <= max_d of
+ * rp_softmax_ce_geometry (128), RP_ERR_ARG above.  workspace: rp_softmax_ce_workspace_bytes(B, V, D) bytes, 16-byte aligned,
+ * the same for both calls; it holds one (max, sum) pair per (row, split of V), the dU slab of each split and the loss
+ * partials — nothing of size B x V.
+ * rp_softmax_ce_geometry: tb = rows of U per workgroup, tv = rows of E per tile, max_d, slices = lanes per row of the
+ * finishing merge (slice q merges the splits q, q + slices, ... in ascending order).  rp_softmax_ce_splits: the number of
+ * splits of V and the tiles of E in each (the last may hold fewer) for a batch of B rows.
+ * rp_hist_mean_fwd / _bwd replace the lookup, mask product and mean of rec_pangu/models/sequence/yotubednn.py:34-36:
+ *   out[b, :] = (1/L) sum_l mask[b, l] E[hist[b, l], :]   (hist int64 [B, L], mask float [B, L]; the divisor is L)
+ * without the [B, L, D] tensor; an id outside [0, V) sets *err_flag and reads row 0.  The backward ADDS
+ * (mask[b, l] / L) g[b, :] into dE[hist[b, l], :] for every position whose id is not 0 (the table is
+ * nn.Embedding(padding_idx=0): row 0 takes no gradient from lookups whatever the mask says), from the (id, flat position)
+ * pairs sorted by id (rp_sort_pairs_i32 over the flat int32 ids); one writer per row, a fixed order. */
+int rp_softmax_ce_geometry(int *tb, int *tv, int *max_d, int *slices);
+int rp_softmax_ce_splits(int64_t B, int64_t V, int *nsplit, int64_t *tiles_per_split);
+int rp_softmax_ce_workspace_bytes(int64_t B, int64_t V, int D, size_t *bytes);
+int rp_softmax_ce_fwd(const float *U, int64_t ldu, const float *E, const int64_t *target, int64_t B, int64_t V, int D,
+                      float *lse, float *loss, int32_t *err_flag, void *workspace, size_t workspace_bytes,
+                      rp_stream_t stream);
+int rp_softmax_ce_bwd(const float *U, int64_t ldu, const float *E, const int64_t *target, const float *lse,
+                      const float *gloss, int64_t B, int64_t V, int D, float *dU, int64_t lddu, float *dE, void *workspace,
+                      size_t workspace_bytes, rp_stream_t stream);
+int rp_hist_mean_fwd(const float *E, int64_t V, int D, const int64_t *hist, const float *mask, int64_t B, int64_t L,
+                     float *out, int64_t ldo, int32_t *err_flag, rp_stream_t stream);
+int rp_hist_mean_bwd(const int32_t *sorted_keys, const int32_t *sorted_pos, int64_t n, int64_t L, int D, int64_t V,
+                     const float *mask, const float *g, int64_t ldg, float *dE, rp_stream_t stream);
+
 /* ---- K11: fused Adam (torch.optim.Adam single-tensor operation order) -----------------------
  * replaces trainer.py:75 + model_pipeline.py:57-58 (optimizer.step(); model.zero_grad()).
  * n_tensors <= RP_MAX_FIELDS per call; zero_grad=1 also clears g (the fused zero_grad).

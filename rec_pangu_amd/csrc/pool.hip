@@ -127,6 +127,77 @@ __global__ __launch_bounds__(256) void seq_pool_bwd_kernel(const float *__restri
     }
 }
 
+// Masked history mean of the sequence-recall models (rec_pangu/models/sequence/yotubednn.py:34-36):
+//   out[b, :] = (1 / L) sum_l mask[b, l] E[hist[b, l], :]       (the divisor is L, not the mask count)
+// — the lookup, the mask product and torch.mean(dim=1) in one launch; the [B, L, D] tensor never exists.  The bag's rows are
+// added in position order.
+template <int TPR, int VEC>
+__global__ __launch_bounds__(256) void hist_mean_fwd_kernel(const float *__restrict__ E, int64_t V,
+                                                            const int64_t *__restrict__ hist, const float *__restrict__ mask,
+                                                            int64_t L, int64_t B, int D, float *__restrict__ out, int64_t ldo,
+                                                            int32_t *__restrict__ err_flag) {
+    typedef PV<VEC> PVT;
+    constexpr int BPB = 256 / TPR;
+    const int t = threadIdx.x % TPR;
+    const int64_t b = (int64_t)blockIdx.x * BPB + threadIdx.x / TPR;
+    if (b >= B) return;
+    const float inv_l = 1.f / (float)L;
+    for (int c = t * VEC; c < D; c += TPR * VEC) {
+        typename PVT::T acc = PVT::zero();
+        for (int64_t j0 = 0; j0 < L; j0 += RP_POOL_INFLIGHT) {
+            typename PVT::T r[RP_POOL_INFLIGHT];
+            float mk[RP_POOL_INFLIGHT];
+#pragma unroll
+            for (int u = 0; u < RP_POOL_INFLIGHT; ++u) {
+                const int64_t j = j0 + u;
+                r[u] = PVT::zero();
+                mk[u] = 0.f;
+                if (j < L) {
+                    int64_t id = hist[b * L + j];
+                    if (id < 0 || id >= V) {  // reference: IndexError from nn.Embedding on CPU
+                        *err_flag = 1;
+                        id = 0;
+                    }
+                    r[u] = PVT::load(E + id * D + c);
+                    mk[u] = mask[b * L + j];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < RP_POOL_INFLIGHT; ++u) acc += r[u] * PVT::splat(mk[u]);
+        }
+        PVT::store(out + b * ldo + c, acc * PVT::splat(inv_l));
+    }
+}
+
+// Its backward into the item table's DENSE gradient: dE[v, :] += sum over the positions (b, l) with hist[b, l] == v of
+// (mask[b, l] / L) g[b, :] — except v == 0, whatever its mask: the table is nn.Embedding(padding_idx=0), whose row 0 takes no
+// gradient from lookups.  From the (id, flat position) pairs sorted by id (stable: ascending position inside a run): the lane
+// group at a run's first pair walks the run in order and adds the sum to the row once — one writer per row, a fixed order.
+template <int TPR, int VEC>
+__global__ __launch_bounds__(256) void hist_mean_bwd_kernel(const int32_t *__restrict__ sk, const int32_t *__restrict__ sp,
+                                                            int64_t n, int64_t L, int D, int64_t V,
+                                                            const float *__restrict__ mask, const float *__restrict__ g,
+                                                            int64_t ldg, float *__restrict__ dE) {
+    typedef PV<VEC> PVT;
+    constexpr int BPB = 256 / TPR;
+    const int t = threadIdx.x % TPR;
+    const int64_t p = (int64_t)blockIdx.x * BPB + threadIdx.x / TPR;
+    if (p >= n) return;
+    const int32_t key = sk[p];
+    if (key <= 0 || key >= V || (p > 0 && sk[p - 1] == key)) return;
+    const float inv_l = 1.f / (float)L;
+    for (int c = t * VEC; c < D; c += TPR * VEC) {
+        typename PVT::T acc = PVT::zero();
+        for (int64_t q = p; q < n && sk[q] == key; ++q) {
+            const int64_t pos = sp[q];
+            const float mk = mask[pos];
+            if (mk != 0.f) acc += PVT::load(g + (pos / L) * ldg + c) * PVT::splat(mk * inv_l);
+        }
+        float *o = dE + (int64_t)key * D + c;
+        PVT::store(o, PVT::load(o) + acc);
+    }
+}
+
 int pool_tpr(int D, int vec) {
     int need = (D + vec - 1) / vec, tpr = 1;
     while (tpr < need && tpr < 64) tpr <<= 1;
@@ -226,5 +297,40 @@ extern "C" int rp_seq_pool_bwd(const float *g, const float *inv, int64_t B, int6
     RP_POOL_DISPATCH(tpr, vec, CALL);
 #undef CALL
     RP_LAUNCH_CHECK("seq_pool_bwd");
+    return RP_OK;
+}
+
+extern "C" int rp_hist_mean_fwd(const float *E, int64_t V, int D, const int64_t *hist, const float *mask, int64_t B, int64_t L,
+                                float *out, int64_t ldo, int32_t *err_flag, rp_stream_t stream) {
+    RP_REQUIRE(E && hist && mask && out && err_flag, "hist_mean_fwd: null pointer");
+    RP_REQUIRE(V >= 1 && D >= 1 && B >= 0 && L >= 1 && ldo >= D, "hist_mean_fwd: bad V / D / B / L / ldo");
+    if (B == 0) return RP_OK;
+    const int vec = (D % 4 == 0 && ldo % 4 == 0 && rp_aligned16(E) && rp_aligned16(out)) ? 4 : 1;
+    const int tpr = pool_tpr(D, vec);
+    const unsigned grid = (unsigned)rp_cdiv(B, 256 / tpr);
+    hipStream_t s = (hipStream_t)stream;
+#define CALL(T, VV) \
+    hipLaunchKernelGGL((hist_mean_fwd_kernel<T, VV>), dim3(grid), dim3(256), 0, s, E, V, hist, mask, L, B, D, out, ldo, err_flag)
+    RP_POOL_DISPATCH(tpr, vec, CALL);
+#undef CALL
+    RP_LAUNCH_CHECK("hist_mean_fwd");
+    return RP_OK;
+}
+
+extern "C" int rp_hist_mean_bwd(const int32_t *sorted_keys, const int32_t *sorted_pos, int64_t n, int64_t L, int D, int64_t V,
+                                const float *mask, const float *g, int64_t ldg, float *dE, rp_stream_t stream) {
+    RP_REQUIRE(sorted_keys && sorted_pos && mask && g && dE, "hist_mean_bwd: null pointer");
+    RP_REQUIRE(n >= 0 && L >= 1 && D >= 1 && V >= 1 && ldg >= D, "hist_mean_bwd: bad n / L / D / V / ldg");
+    if (n == 0) return RP_OK;
+    const int vec = (D % 4 == 0 && ldg % 4 == 0 && rp_aligned16(g) && rp_aligned16(dE)) ? 4 : 1;
+    const int tpr = pool_tpr(D, vec);
+    const unsigned grid = (unsigned)rp_cdiv(n, 256 / tpr);
+    hipStream_t s = (hipStream_t)stream;
+#define CALL(T, VV) \
+    hipLaunchKernelGGL((hist_mean_bwd_kernel<T, VV>), dim3(grid), dim3(256), 0, s, sorted_keys, sorted_pos, n, L, D, V, mask, g, \
+                       ldg, dE)
+    RP_POOL_DISPATCH(tpr, vec, CALL);
+#undef CALL
+    RP_LAUNCH_CHECK("hist_mean_bwd");
     return RP_OK;
 }

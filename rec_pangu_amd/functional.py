@@ -1961,3 +1961,96 @@ class _SeqPool(torch.autograd.Function):
 def seq_pool(e, mode: str):
     """MaskedSumPooling ("sum") / MaskedAveragePooling ("average") of an explicit [B, L, D] HIP tensor"""
     return _SeqPool.apply(e.float().contiguous(), mode)
+
+
+# ----------------------------------------------------------------------------------------------
+# sequence recall: the full-softmax loss head (models/base_model.py:124-138 of the reference) and the masked history mean
+# (models/sequence/yotubednn.py:34-36).  No [B, V] and no [B, L, D] tensor exists on the HIP path.
+# ----------------------------------------------------------------------------------------------
+_SEQ_FLAGS: dict = {}
+
+
+def _seq_flag(device) -> torch.Tensor:
+    """the device word the sequence kernels raise on an id / target outside its table (one per device)"""
+    flag = _SEQ_FLAGS.get(device)
+    if flag is None:
+        flag = _SEQ_FLAGS[device] = torch.zeros(1, dtype=torch.int32, device=device)
+    return flag
+
+
+def _raise_if_flagged(device, what: str):
+    flag = _seq_flag(device)
+    if int(flag.item()) != 0:  # (one 4-byte copy: what the reference's CPU ops check on the host)
+        flag.zero_()
+        raise IndexError(what)
+
+
+class _SoftmaxCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, user_emb, item_weight, target):
+        u, e = _unit_inner(user_emb), item_weight.contiguous()
+        loss, lse = hip.softmax_ce_fwd(u, e, target, _seq_flag(u.device))
+        # the inputs themselves plus lse [B]: no logits, no softmax
+        ctx.save_for_backward(u, e, target, lse)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        u, e, target, lse = ctx.saved_tensors
+        du, de = hip.softmax_ce_bwd(u, e, target, lse, g.reshape(1).float().contiguous(), ctx.needs_input_grad[0],
+                                    ctx.needs_input_grad[1])
+        return du, de, None
+
+
+def full_softmax_ce(user_emb: torch.Tensor, item_weight: torch.Tensor, target: torch.Tensor, check_indices: str = "sync"):
+    """CrossEntropyLoss()(user_emb @ item_weight.T, target), the scalar mean over the batch (reference
+    models/base_model.py:135-137).  user_emb [B, D], item_weight [V, D], target int64 [B].  On the HIP device the fused
+    kernels (no [B, V] tensor; the backward recomputes from lse); check_indices "sync" raises IndexError for a target outside
+    [0, V) right after the forward, as the reference's CPU loss does, "deferred" leaves the flag set.  On CPU tensors the
+    reference's torch formula."""
+    if not user_emb.is_cuda:
+        return torch.nn.functional.cross_entropy(torch.matmul(user_emb, item_weight.transpose(1, 0)), target)
+    target = target.contiguous()
+    if user_emb.dtype != torch.float32 or item_weight.dtype != torch.float32 or not hip.softmax_ce_fits(user_emb.shape[1]):
+        hip.note_torch_path(f"full_softmax_ce at D={user_emb.shape[1]}, {user_emb.dtype} (the kernels take fp32 up to "
+                            f"D={hip.softmax_ce_geometry()['max_d']})")
+        return torch.nn.functional.cross_entropy(torch.matmul(user_emb, item_weight.transpose(1, 0)), target)
+    loss = _SoftmaxCE.apply(user_emb, item_weight, target)
+    if check_indices == "sync":
+        _raise_if_flagged(user_emb.device, f"Target out of bounds: every target must lie in [0, {item_weight.shape[0]})")
+    return loss
+
+
+class _HistMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, item_weight, hist, mask):
+        e = item_weight.contiguous()
+        out = hip.hist_mean_fwd(e, hist, mask, _seq_flag(e.device))
+        ctx.save_for_backward(hist, mask)
+        ctx.rows = e.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        hist, mask = ctx.saved_tensors
+        de = torch.zeros(ctx.rows, dtype=torch.float32, device=g.device)
+        hip.hist_mean_bwd(hist, mask, _unit_inner(g), de)
+        return de, None, None
+
+
+def hist_mean(item_weight: torch.Tensor, hist: torch.Tensor, mask: torch.Tensor, check_indices: str = "sync"):
+    """mean over dim 1 of item_emb(hist) * mask[..., None] with item_emb = nn.Embedding(V, D, padding_idx=0) (reference
+    models/sequence/yotubednn.py:34-36): out[b] = (1/L) sum_l mask[b, l] item_weight[hist[b, l]] — the divisor is L, not the
+    mask count — and no gradient reaches row 0 through it, whatever the mask.  hist int64 [B, L], mask [B, L] of any dtype.
+    On the HIP device one launch each way and no [B, L, D] tensor; on CPU tensors the reference's torch formula."""
+    if not item_weight.is_cuda:
+        e = torch.nn.functional.embedding(hist, item_weight, padding_idx=0)
+        return torch.mean(e * mask.unsqueeze(-1).float(), dim=1)
+    if item_weight.dtype != torch.float32:
+        hip.note_torch_path(f"hist_mean over a {item_weight.dtype} table (the kernels take fp32)")
+        e = torch.nn.functional.embedding(hist, item_weight, padding_idx=0)
+        return torch.mean(e * mask.unsqueeze(-1).float(), dim=1)
+    out = _HistMean.apply(item_weight, hist.contiguous(), mask.float().contiguous())
+    if check_indices == "sync":
+        _raise_if_flagged(item_weight.device, "index out of range in self")
+    return out

@@ -245,6 +245,13 @@ _SIGNATURES = {
     "rp_lazy_adam_cf_table": (C.c_int, [_vp, _i64, _i64, _f64, _f64, _vp, _i64, _i64, _vp, _vp]),
     "rp_metrics_workspace_bytes": (C.c_int, [_i64, C.POINTER(_sz)]),
     "rp_binary_metrics": (C.c_int, [_vp, _sz, _vp, _vp, _i64, _f64, _i32, _vp, _vp]),
+    "rp_softmax_ce_geometry": (C.c_int, [C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
+    "rp_softmax_ce_splits": (C.c_int, [_i64, _i64, C.POINTER(_i32), C.POINTER(_i64)]),
+    "rp_softmax_ce_workspace_bytes": (C.c_int, [_i64, _i64, _i32, C.POINTER(_sz)]),
+    "rp_softmax_ce_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "rp_softmax_ce_bwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "rp_hist_mean_fwd": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
+    "rp_hist_mean_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 
@@ -2984,4 +2991,105 @@ def seq_pool_bwd(g, inv, L: int):
     de = _new((B, L, D), torch.float32, g.device)
     with _Timed("seq_pool_bwd", f"{B}x{L}x{D}", (B * L * D + B * D) * 4):
         _check(lib().rp_seq_pool_bwd(g.data_ptr(), _ptr(inv), B, L, D, de.data_ptr(), _stream()), "rp_seq_pool_bwd")
+    return de
+
+
+# ---- sequence recall: the full-softmax loss head and the masked history mean (csrc/softmax_ce.hip, csrc/pool.hip) --------
+def softmax_ce_geometry() -> dict:
+    """{"TB": rows of U per workgroup, "TV": rows of E per tile, "max_d": largest D the kernels take, "slices": lanes per row
+    of the finishing merge (slice q merges the splits q, q + slices, ... in ascending order)}"""
+    v = [_i32(0) for _ in range(4)]
+    _check(lib().rp_softmax_ce_geometry(*[C.byref(x) for x in v]), "rp_softmax_ce_geometry")
+    return dict(zip(("TB", "TV", "max_d", "slices"), (x.value for x in v)))
+
+
+def softmax_ce_splits(B: int, V: int):
+    """(number of splits of V, tiles of E per split) of the forward and dU launches for a batch of B rows"""
+    n, per = _i32(0), _i64(0)
+    _check(lib().rp_softmax_ce_splits(B, V, C.byref(n), C.byref(per)), "rp_softmax_ce_splits")
+    return n.value, per.value
+
+
+def softmax_ce_workspace_bytes(B: int, V: int, D: int) -> int:
+    n = _sz(0)
+    _check(lib().rp_softmax_ce_workspace_bytes(B, V, D, C.byref(n)), "rp_softmax_ce_workspace_bytes")
+    return n.value
+
+
+def softmax_ce_fits(D: int) -> bool:
+    return 1 <= D <= softmax_ce_geometry()["max_d"]
+
+
+def _sce_args(u, e, target):
+    _req(u, torch.float32, "user_emb")
+    _req(e, torch.float32, "item_weight")
+    _req(target, torch.int64, "target")
+    B, D = u.shape
+    V = e.shape[0]
+    if e.dim() != 2 or e.shape[1] != D or not e.is_contiguous():
+        raise RuntimeError(f"softmax_ce: item_weight must be a contiguous [V, {D}] tensor, got {tuple(e.shape)}/{e.stride()}")
+    if target.shape != (B,) or not target.is_contiguous():
+        raise RuntimeError(f"softmax_ce: target must be a contiguous [{B}] tensor, got {tuple(target.shape)}")
+    return B, V, D, _rowmajor(u, "user_emb")
+
+
+def softmax_ce_fwd(u, e, target, err_flag):
+    """rp_softmax_ce_fwd -> (loss float32 [1], lse float32 [B]); u [B, D] (unit inner stride), e [V, D], target int64 [B]"""
+    B, V, D, ldu = _sce_args(u, e, target)
+    ws, nbytes = _workspace("softmax_ce", B, V, D, device=u.device)
+    lse, loss = _new((B,), torch.float32, u.device), _new((1,), torch.float32, u.device)
+    with _Timed("softmax_ce_fwd", f"{B}x{V}x{D}", 4 * (B * D + V * D), 2 * B * V * D):
+        _check(lib().rp_softmax_ce_fwd(u.data_ptr(), ldu, e.data_ptr(), target.data_ptr(), B, V, D, lse.data_ptr(),
+                                       loss.data_ptr(), err_flag.data_ptr(), ws.data_ptr(), nbytes, _stream()),
+               "rp_softmax_ce_fwd")
+    return loss, lse
+
+
+def softmax_ce_bwd(u, e, target, lse, gloss, want_du: bool = True, want_de: bool = True):
+    """rp_softmax_ce_bwd -> (dU [B, D] or None, dE [V, D] or None); gloss: device float32 [1].  The two gradients are two
+    launches, issued (and timed) as one call each."""
+    B, V, D, ldu = _sce_args(u, e, target)
+    _req(lse, torch.float32, "lse")
+    _req(gloss, torch.float32, "gloss")
+    ws, nbytes = _workspace("softmax_ce", B, V, D, device=u.device)
+    du = _new((B, D), torch.float32, u.device) if want_du else None
+    de = _new((V, D), torch.float32, u.device) if want_de else None
+    for tag, out, nbytes_moved in (("dU", du, 4 * (2 * B * D + V * D)), ("dE", de, 4 * (B * D + 2 * V * D))):
+        if out is None:
+            continue
+        with _Timed("softmax_ce_bwd", f"{tag} {B}x{V}x{D}", nbytes_moved, 4 * B * V * D):
+            _check(lib().rp_softmax_ce_bwd(u.data_ptr(), ldu, e.data_ptr(), target.data_ptr(), lse.data_ptr(), gloss.data_ptr(),
+                                           B, V, D, _ptr(du) if tag == "dU" else None, D, _ptr(de) if tag == "dE" else None,
+                                           ws.data_ptr(), nbytes, _stream()), "rp_softmax_ce_bwd")
+    return du, de
+
+
+def hist_mean_fwd(e, hist, mask, err_flag):
+    """rp_hist_mean_fwd: out[b] = (1/L) sum_l mask[b, l] e[hist[b, l]]; e [V, D], hist int64 [B, L], mask float32 [B, L]"""
+    _req(e, torch.float32, "item_weight")
+    _req(hist, torch.int64, "hist")
+    _req(mask, torch.float32, "mask")
+    B, L = hist.shape
+    V, D = e.shape
+    if not (e.is_contiguous() and hist.is_contiguous() and mask.is_contiguous()) or mask.shape != hist.shape:
+        raise RuntimeError("hist_mean: item_weight, hist and mask must be contiguous, hist and mask of one shape")
+    out = _new((B, D), torch.float32, e.device)
+    with _Timed("hist_mean_fwd", f"D={D}", B * L * (D * 4 + 12) + B * D * 4):
+        _check(lib().rp_hist_mean_fwd(e.data_ptr(), V, D, hist.data_ptr(), mask.data_ptr(), B, L, out.data_ptr(), D,
+                                      err_flag.data_ptr(), _stream()), "rp_hist_mean_fwd")
+    return out
+
+
+def hist_mean_bwd(hist, mask, g, de):
+    """rp_hist_mean_bwd: de[hist[b, l]] += (mask[b, l] / L) g[b] for every position whose id is not 0 (de [V, D], added into)"""
+    _req(g, torch.float32, "g")
+    _req(de, torch.float32, "dE")
+    B, L = hist.shape
+    V, D = de.shape
+    assert de.is_contiguous() and g.shape == (B, D)
+    # (all 32 bits: an id outside the table, skipped by the kernel, must not land inside another id's run)
+    sk, sp = sort_pairs(hist.reshape(-1).to(torch.int32))
+    with _Timed("hist_mean_bwd", f"D={D}", B * L * (D * 4 + 12)):
+        _check(lib().rp_hist_mean_bwd(sk.data_ptr(), sp.data_ptr(), B * L, L, D, V, mask.data_ptr(), g.data_ptr(),
+                                      _rowmajor(g, "g"), de.data_ptr(), _stream()), "rp_hist_mean_bwd")
     return de

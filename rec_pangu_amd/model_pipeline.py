@@ -1,4 +1,5 @@
-"""train_model / test_model — counterparts of rec_pangu/model_pipeline.py:17-219 (ranking + multi-task).
+"""train_model / test_model — counterparts of rec_pangu/model_pipeline.py:17-219 (ranking + multi-task) — and
+train_sequence_model / test_sequence_model, counterparts of :222-318 (sequence recall; at the end of this file).
 
 Same call order per batch (forward -> loss.backward() -> optimizer.step() -> model.zero_grad()),
 same returned keys (`train_roc_auc_score`, `train_log_loss`, `roc_auc_score`, `log_loss`,
@@ -18,6 +19,7 @@ from sklearn.metrics import roc_auc_score
 from sklearn.metrics import log_loss as _sk_log_loss
 
 from . import metrics as _device_metrics
+from .utils.evaluate import evaluate_recall, get_recall_predict
 
 logger = logging.getLogger("rec_pangu_amd")
 SUPPORTED_METRICS = ['roc_auc_score', 'log_loss']
@@ -175,3 +177,44 @@ def test_model(model, test_loader, device, metric_list: List[str] = ['roc_auc_sc
 
 
 test_model.__test__ = False  # not a pytest test
+
+
+# ---- sequence recall (rec_pangu/model_pipeline.py:222-318) -------------------------------------------------------------
+def train_sequence_model(model: torch.nn.Module, train_loader, optimizer, device, use_wandb: bool = False,
+                         log_rounds: int = 100):
+    """One epoch: per batch forward -> loss.backward() -> optimizer.step() -> model.zero_grad(), the reference's order.
+    The loss is read back only on the iterations that log it."""
+    model.train()
+    max_iter = len(train_loader)
+    start_time = time.time()
+    for idx, data in enumerate(train_loader):
+        _move(data, device)
+        loss = model(data, is_training=True)['loss']
+        loss.backward()
+        optimizer.step()
+        model.zero_grad()
+        if use_wandb:
+            import wandb
+            wandb.log({'train_loss': loss.item()})
+        if idx % log_rounds == 0 and idx != 0:
+            logger.info(f"Iter {idx}/{max_iter} Loss:{round(float(loss.item()), 4)} "
+                        f"Time:{round(time.time() - start_time, 1)}s")
+
+
+def test_sequence_model(model: torch.nn.Module, test_loader, device, topk_list: List[int] = [20, 50, 100],
+                        use_wandb: bool = False) -> dict:
+    """{recall@k, ndcg@k, hitrate@k for every k of topk_list} against test_loader.dataset.get_test_gd(), from ONE search of
+    the 200 best items per user (the reference's topN=200)."""
+    model.eval()
+    test_gd = test_loader.dataset.get_test_gd()
+    with torch.no_grad():
+        preds = get_recall_predict(model, test_loader, device, topN=200)
+    metric_dict = {}
+    for k in topk_list:
+        part = evaluate_recall(preds, test_gd, k)
+        logger.info(part)
+        metric_dict.update(part)
+    if use_wandb:
+        import wandb
+        wandb.log(metric_dict)
+    return metric_dict

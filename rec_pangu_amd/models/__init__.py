@@ -1,1 +1,1 @@
-from . import layers, ranking, multi_task  # noqa: F401
+from . import layers, ranking, multi_task, sequence  # noqa: F401

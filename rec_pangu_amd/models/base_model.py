@@ -1,4 +1,4 @@
-"""BaseModel — drop-in for rec_pangu/models/base_model.py:14-90 (ranking / multi-task base only).
+"""BaseModel and SequenceBaseModel — drop-ins for rec_pangu/models/base_model.py:14-90 and :93-224.
 
 Owns the arena-backed EmbeddingLayer; keeps the reference's two init schemes bit-for-bit (they
 consume the global torch RNG in parameter-registration order, which is identical here), and adds the
@@ -131,3 +131,68 @@ class BaseModel(nn.Module):
         if is_training:
             return {"pred": pred, "loss": loss_fun(pred.squeeze(-1), data["label"])}
         return {"pred": pred}
+
+
+class SequenceBaseModel(nn.Module):
+    """Base of the sequence-recall models — drop-in for rec_pangu/models/base_model.py:93-224: the same constructor, the same
+    parameters in the same registration order (`item_emb`, then one `<col>_emb` per config['cate_cols'], all
+    nn.Embedding(padding_idx=0)), the same init schemes on the same RNG stream.
+
+    calculate_loss is the family's hot path: the reference forms scores = user_emb @ item_emb.weight.T as a [B, V] tensor and
+    applies CrossEntropyLoss over the whole vocabulary; here Fh.full_softmax_ce runs the fused kernels on the HIP device
+    (no [B, V] tensor in either direction) and the reference's formula on the CPU.
+
+    check_indices: "sync" raises IndexError for an id / target outside its table right after the loss (one 4-byte copy per
+    step, what the reference's CPU ops do); "deferred" leaves the device flag set."""
+
+    def __init__(self, enc_dict: dict, config: dict):
+        super().__init__()
+        self.enc_dict = enc_dict
+        self.config = config
+        self.embedding_dim = self.config['embedding_dim']
+        self.max_length = self.config['max_length']
+        self.device = self.config['device']
+        self.check_indices = "sync"
+
+        self.item_emb = nn.Embedding(self.enc_dict[self.config['item_col']]['vocab_size'], self.embedding_dim,
+                                     padding_idx=0)
+        for col in self.config['cate_cols']:
+            setattr(self, f'{col}_emb',
+                    nn.Embedding(self.enc_dict[col]['vocab_size'], self.embedding_dim, padding_idx=0))
+
+        self.loss_fun = nn.CrossEntropyLoss()
+
+    def calculate_loss(self, user_emb: torch.Tensor, pos_item: torch.Tensor) -> torch.Tensor:
+        return Fh.full_softmax_ce(user_emb, self.output_items(), pos_item, check_indices=self.check_indices)
+
+    def gather_indexes(self, output: torch.Tensor, gather_index: torch.Tensor) -> torch.Tensor:
+        """output [B, L, D], gather_index [B] -> output[b, gather_index[b], :]  (base_model.py:140-153)"""
+        gather_index = gather_index.view(-1, 1, 1).expand(-1, -1, output.shape[-1])
+        output_tensor = output.gather(dim=1, index=gather_index)
+        return output_tensor.squeeze(1)
+
+    def output_items(self) -> torch.Tensor:
+        return self.item_emb.weight
+
+    def get_attention_mask(self, attention_mask: torch.Tensor) -> torch.Tensor:
+        """[B, L] of 0 / 1 -> [B, 1, L, L]: 0 where position j <= i is content, -1e6 elsewhere (base_model.py:164-193)"""
+        extended_attention_mask = attention_mask.unsqueeze(1).unsqueeze(2)
+        max_len = attention_mask.size(-1)
+        subsequent_mask = torch.triu(torch.ones((1, max_len, max_len), dtype=torch.uint8), diagonal=1)
+        subsequent_mask = (subsequent_mask == 0).unsqueeze(1).type_as(attention_mask)
+        extended_attention_mask = extended_attention_mask * subsequent_mask
+        return (1.0 - extended_attention_mask) * -1e6
+
+    def _init_weights(self, module: nn.Module):
+        if isinstance(module, nn.Embedding):
+            torch.nn.init.kaiming_normal_(module.weight.data)
+        elif isinstance(module, nn.Linear):
+            torch.nn.init.kaiming_normal_(module.weight.data)
+
+    def reset_parameters(self):
+        """kaiming_normal_ on every >=2-D parameter — the padding rows included: row 0 of item_emb is NOT zero afterwards
+        (base_model.py:207-224); 1-D parameters are left as built."""
+        for weight in self.parameters():
+            if len(weight.shape) == 1:
+                continue
+            torch.nn.init.kaiming_normal_(weight)
