@@ -22,6 +22,6 @@ void rp_count_launch() { g_launches.fetch_add(1, std::memory_order_relaxed); }
 // removed entry point fail when they look it up, nothing is called through a wrong prototype).  Entry points added since,
 // rp_binary_metrics the latest, changed no existing prototype and kept 108 (the *_host tests pin it): bindings that name an
 // entry point a stale library lacks fail when they load it.
-extern "C" int rp_version(void) { return 108; }
+extern "C" int rp_version(void) { return RP_ABI_VERSION; }
 extern "C" const char *rp_last_error(void) { return g_err; }
 extern "C" uint64_t rp_launch_count(void) { return g_launches.load(std::memory_order_relaxed); }

@@ -37,6 +37,18 @@ def _unit_inner(t: torch.Tensor) -> torch.Tensor:
     return t.contiguous()
 
 
+def padded(width: int, pad_to: int) -> int:
+    """width rounded up to a multiple of pad_to (pad_to <= 1: width itself): the leading dimension of a padded row buffer"""
+    return width if pad_to <= 1 else (width + pad_to - 1) // pad_to * pad_to
+
+
+def _wide_rows_grad(rows: torch.Tensor, used: int) -> Optional[torch.Tensor]:
+    """the gradient buffer of a row buffer of which a block reads the first `used` columns only: zero-filled at full width
+    when there are columns beyond them (they carry no gradient; the library's own fill), None when there are none (the
+    wrapper then makes a [B, used] one)"""
+    return hip.zeros(tuple(rows.shape), torch.float32, rows.device) if rows.shape[1] > used else None
+
+
 # ----------------------------------------------------------------------------------------------
 # K4  Linear (+bias, +ReLU)   — layers/deep.py:62-72
 # ----------------------------------------------------------------------------------------------
@@ -1235,9 +1247,8 @@ class _GINStack(torch.autograd.Function):
         F, D, nl = ctx.F, ctx.D, ctx.nl
         saved = ctx.saved_tensors
         x0, params, outs = saved[0], saved[1:1 + 3 * nl], saved[1 + 3 * nl:]
-        if x0.shape[1] > F * D:  # columns the layers never read: their gradient is zero (the library's own fill)
-            dx0 = hip.zeros(tuple(x0.shape), torch.float32, x0.device)
-        else:
+        dx0 = _wide_rows_grad(x0, F * D)
+        if dx0 is None:  # (rp_gin_bwd takes its dx0 from the caller either way)
             dx0 = torch.empty(tuple(x0.shape), dtype=torch.float32, device=x0.device)
         grads = [None] * (3 * nl)
         g = _unit_inner(dout)
@@ -1282,11 +1293,7 @@ class _CCPMStack(torch.autograd.Function):
         F, D, nl = ctx.F, ctx.D, ctx.nl
         saved = ctx.saved_tensors
         x, weights, biases = saved[0], list(saved[1:1 + nl]), list(saved[1 + nl:])
-        if x.shape[1] > F * D:  # columns the stack never reads: their gradient is zero (the library's own fill)
-            dx = hip.zeros(tuple(x.shape), torch.float32, x.device)
-        else:
-            dx = None
-        dx, dWs, dbs = hip.ccpm_bwd(_unit_inner(dout), x, weights, biases, F, D, ctx.ks, dx=dx)
+        dx, dWs, dbs = hip.ccpm_bwd(_unit_inner(dout), x, weights, biases, F, D, ctx.ks, dx=_wide_rows_grad(x, F * D))
         return (dx if ctx.needs_input_grad[0] else None, None, None, None, *dWs, *dbs)
 
 
@@ -1322,11 +1329,8 @@ class _SenetBilinear(torch.autograd.Function):
         F, D, R, btype, n_dense = ctx.geom
         rows, params = ctx.saved_tensors[0], list(ctx.saved_tensors[1:])
         senet, weights = (tuple(params[:2]), params[2:]) if R > 0 else (None, params)
-        if rows.shape[1] > F * D:  # columns that carry no gradient (dense, padding): the library's own fill
-            dx = hip.zeros(tuple(rows.shape), torch.float32, rows.device)
-        else:
-            dx = None
-        dx, dW, dW1, dW2 = hip.bilinear_bwd(_unit_inner(dout), rows, F, D, weights, btype, senet, n_dense, dx=dx)
+        dx, dW, dW1, dW2 = hip.bilinear_bwd(_unit_inner(dout), rows, F, D, weights, btype, senet, n_dense,
+                                            dx=_wide_rows_grad(rows, F * D))
         # field_each: the last field opens no pair, its matrix takes no part (the reference leaves its .grad None)
         used = len(weights) - 1 if btype == hip.BILINEAR_TYPES["field_each"] else len(weights)
         grads = [dW[k] if k < used else None for k in range(len(weights))]
@@ -1345,7 +1349,7 @@ def senet_bilinear(rows, F: int, D: int, senet, bilinear, dense: int = 0, pad_to
         raise RuntimeError(f"senet_bilinear: {F} fields of width {D}, {R} SENET units, {bilinear.bilinear_type!r}: no kernel "
                            "form (hip.bilinear_fits)")
     width = (2 if R else 1) * (F * (F - 1) // 2) * D + dense
-    ld = (width + pad_to - 1) // pad_to * pad_to if pad_to > 1 else width
+    ld = padded(width, pad_to)
     params = [] if senet is None else [senet.excitation[0].weight, senet.excitation[2].weight]
     return _SenetBilinear.apply(rows, F, D, R, btype, dense, ld, *params, *bilinear.weights())
 
@@ -1383,12 +1387,8 @@ class _LogarithmicNet(torch.autograd.Function):
         rows, z, W, g1, b1, g2, m1, v1, m2, v2 = ctx.saved_tensors
         if dout is None:
             return (None,) * (11 + (0 if train else 4))
-        if rows.shape[1] > F * D:  # columns that carry no gradient (dense, padding): the library's own fill
-            dx = hip.zeros(tuple(rows.shape), torch.float32, rows.device)
-        else:
-            dx = None
         dx, dW, dg1, db1, dg2, db2 = hip.lognet_bwd(_unit_inner(dout), rows, z, F, D, W, g1, b1, m1, v1, eps1, g2, m2, v2, eps2,
-                                                    train, dx=dx)
+                                                    train, dx=_wide_rows_grad(rows, F * D))
         return (dx if ctx.needs_input_grad[0] else None, None, None, None, None, None, dW, dg1, db1, dg2, db2,
                 *(() if train else (None,) * 4))
 
@@ -1410,7 +1410,7 @@ def logarithmic_net(rows, F: int, D: int, coefficient_W, log_bn, exp_bn, pad_to:
     batch = [bn.training or not bn.track_running_stats or bn.running_mean is None for bn in (log_bn, exp_bn)]
     if batch[0] != batch[1]:
         raise RuntimeError("logarithmic_net: one BatchNorm on batch statistics and one on running statistics")
-    ld = (L * D + pad_to - 1) // pad_to * pad_to if pad_to > 1 else L * D
+    ld = padded(L * D, pad_to)
     head = (rows, F, D, ld, float(log_bn.eps), float(exp_bn.eps), W, log_bn.weight, log_bn.bias, exp_bn.weight, exp_bn.bias)
     if not batch[0]:
         return _LogarithmicNet.apply(*head, log_bn.running_mean, log_bn.running_var, exp_bn.running_mean, exp_bn.running_var)

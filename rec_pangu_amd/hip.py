@@ -8,251 +8,68 @@ fails, a RuntimeError is raised — a CUDA(HIP)-resident tensor never silently t
 import contextlib
 import ctypes as C
 import os
+import re
 from typing import List, Optional, Sequence
 
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-ABI_VERSION = 108  # csrc/common.hip: rp_version() — bumped with every change of the entry points' prototypes
+HEADER_PATH = os.path.join(_HERE, os.pardir, "include", "rec_pangu_hip.h")  # (csrc/Makefile: ../../include from csrc)
 LIB_PATH = os.environ.get("RP_LIB_PATH") or os.path.join(_HERE, "lib", "librecpangu_hip.so")  # (override: A/B builds)
-MAX_FIELDS = 64
-
-ACT_NONE, ACT_RELU, ACT_MASK, ACT_TANH, ACT_SIGMOID, ACT_LEAKY = 0, 1, 2, 3, 4, 5
 
 _lib = None
 
 _i64, _i32, _f32, _vp, _sz = C.c_int64, C.c_int, C.c_float, C.c_void_p, C.c_size_t
-_ip = C.POINTER(C.c_int)  # a host array of ints the library copies into its launch
 _f64 = C.c_double
-_SIGNATURES = {
-    "rp_version": (C.c_int, []),
-    "rp_last_error": (C.c_char_p, []),
-    "rp_launch_count": (C.c_uint64, []),
-    "rp_embed_gather_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
-    "rp_embed_gather_linear_fits": (C.c_int, [_i32, _i32, _i32, _i64, _i64]),
-    "rp_embed_gather_linear_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp,
-                                             _vp, _vp, _vp, _vp, _vp]),
-    "rp_embed_gather_linear_fwd_bf16": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp,
-                                                  _i64, _vp, _vp, _vp, _vp, _vp]),
-    "rp_sort_workspace_bytes": (C.c_int, [_i64, C.POINTER(_sz)]),
-    "rp_sort_pairs_i32": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _i64, _i32, _vp]),
-    "rp_sort_pairs_fields_workspace_bytes": (C.c_int, [_i64, _i32, C.POINTER(_sz)]),
-    "rp_sort_pairs_fields_i32": (C.c_int, [_vp, _sz, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp]),
-    "rp_embed_grad_reduce_workspace_bytes": (C.c_int, [_i64, _i32, C.POINTER(_sz)]),
-    "rp_embed_grad_reduce": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
-    "rp_embed_grad_gemm_fits": (C.c_int, [_i32, _i32, _i64, _i64]),
-    "rp_embed_grad_gemm": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32,
-                                     C.c_uint64, _vp, _sz, _vp]),
-    "rp_embed_grad_tiny_workspace_bytes": (C.c_int, [_i64, C.POINTER(_sz)]),
-    "rp_embed_grad_tiny": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i64,
-                                     _vp, _sz, _vp]),
-    "rp_embed_grad_ss_workspace_bytes": (C.c_int, [_i64, _i64, _i32, C.c_uint64, C.POINTER(_sz)]),
-    "rp_embed_grad_ss_mark_sizes": (C.c_int, [_i64, _i32, C.POINTER(_sz), C.POINTER(_sz)]),
-    "rp_embed_grad_ss_mark": (C.c_int, [_vp, _i64, _i64, C.c_uint64, _vp, _vp, _vp, _vp]),
-    "rp_embed_grad_ss": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, C.c_uint64, _vp,
-                                   _vp, _i64, _vp, _vp, _vp, _i32, _vp, _sz, _vp]),
-    "rp_embed_grad_smp_fits": (C.c_int, [_i32, _i32, _i64]),
-    "rp_embed_grad_smp_workspace_bytes": (C.c_int, [_i64, _i32, C.POINTER(_sz)]),
-    "rp_embed_grad_smp_mark_scratch": (C.c_int, [_i64, _i32, C.POINTER(_sz)]),
-    "rp_embed_grad_smp_mark": (C.c_int, [_vp, _vp, _i64, _i64, _vp, _i32, _vp, _vp, _vp, _vp]),
-    "rp_embed_grad_smp": (C.c_int, [_vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32,
-                                    _vp, _i64, _i32, _vp, _sz, _vp]),
-    "rp_embed_grad_reduce_rows": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i32, _vp, _sz, _vp]),
-    "rp_embed_grad_seg_fits": (C.c_int, [_i32, _i32, _i64]),
-    "rp_embed_grad_seg_workspace_bytes": (C.c_int, [_i64, _i64, _i32, C.POINTER(_sz)]),
-    "rp_embed_grad_seg": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, C.c_uint64, _vp,
-                                    _vp, _i64, _vp, _sz, _vp]),
-    "rp_zero_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp]),
-    "rp_linear_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
-    "rp_linear_fwd_rowadd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _vp]),
-    "rp_linear_wgrad_workspace_bytes": (C.c_int, [_i64, _i32, _i32, C.POINTER(_sz)]),
-    "rp_linear_wgrad": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _sz, _vp]),
-    "rp_transpose": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp]),
-    "rp_copy_rows": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp]),
-    "rp_add_rows": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _vp]),
-    "rp_transpose_copy": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp]),
-    "rp_pieces_ld": (C.c_int64, [_i32, _i32]),
-    "rp_pieces_pack": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp]),
-    "rp_linear_fwd_pieces": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _vp, _i64, _vp]),
-    "rp_plan_begin": (C.c_int, [C.POINTER(_vp)]),
-    "rp_plan_section": (C.c_int, [_i32]),
-    "rp_plan_fork_here": (C.c_int, []),
-    "rp_plan_join": (C.c_int, []),
-    "rp_plan_fork2_mark": (C.c_int, []),
-    "rp_stream_create_low": (C.c_int, [C.POINTER(_vp)]),
-    "rp_plan_is_recording": (C.c_int, []),
-    "rp_plan_end": (C.c_int, [_vp]),
-    "rp_plan_info": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
-    "rp_plan_replay": (C.c_int, [_vp, _vp]),
-    "rp_plan_set_streams": (C.c_int, [_vp, _vp, _vp]),
-    "rp_plan_set_probe": (C.c_int, [_vp, _i32]),
-    "rp_plan_probe_ms": (C.c_int, [_vp, C.POINTER(C.c_float)]),
-    "rp_marker_create": (C.c_int, [C.POINTER(_vp)]),
-    "rp_marker_record": (C.c_int, [_vp, _vp]),
-    "rp_marker_wait": (C.c_int, [_vp]),
-    "rp_marker_destroy": (C.c_int, [_vp]),
-    "rp_plan_slowest_call": (C.c_int, [_vp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_double), C.c_int]),
-    "rp_plan_launch_name": (C.c_int, [_vp, _i32, C.c_char_p, _i32, C.POINTER(_i32)]),
-    "rp_plan_host_mark": (C.c_int, [C.POINTER(_i32)]),
-    "rp_plan_replay_segment": (C.c_int, [_vp, _i32, _vp]),
-    "rp_fill_words": (C.c_int, [_vp, _i64, C.c_uint32, _vp]),
-    "rp_plan_side2_sync": (C.c_int, []),
-    "rp_plan_bind_inputs": (C.c_int, [_vp, _vp, _i32, C.POINTER(_i32)]),
-    "rp_plan_bind_report": (C.c_int, [_vp, _vp, _vp, _i32, _vp, C.POINTER(_i32)]),
-    "rp_plan_set_inputs": (C.c_int, [_vp, _vp, _i32]),
-    "rp_plan_inline_count": (C.c_int, [_vp, C.POINTER(_i32)]),
-    "rp_plan_destroy": (C.c_int, [_vp]),
-    "rp_graph_node_counts": (C.c_int, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
-    "rp_multi_copy": (C.c_int, [_vp, _vp, _vp, _i32, _vp]),
-    "rp_relu_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _vp]),
-    "rp_act_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp]),
-    "rp_act_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp]),
-    "rp_crossnet_fwd": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp]),
-    "rp_crossnet_bwd_rows": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp]),
-    "rp_crossnet_param_grads": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _vp, _vp, _vp, _vp]),
-    "rp_cin_layer_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _vp]),
-    "rp_cin_layer_bwd_x": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64, _i32, _i32,
-                                     _i32, _i32, _i64, _vp]),
-    "rp_cin_layer_bwd_w_workspace_bytes": (C.c_int, [_i64, _i32, _i32, _i32, C.POINTER(_sz)]),
-    "rp_cin_layer_bwd_w": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _i64, _vp,
-                                     _sz, _vp]),
-    "rp_field_attention_fits": (C.c_int, [_i32, _i32, _i32, _i32, _i32]),
-    "rp_field_attention_fwd": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _i64, _vp]),
-    "rp_field_attention_bwd_workspace_bytes": (C.c_int, [_i64, _i32, _i32, _i32, _i32, _i32, C.POINTER(_sz)]),
-    "rp_field_attention_bwd": (C.c_int, [_vp, _i64, _vp, _i32, _i32, _i32, _i32, _i32, _f32, _vp, _vp, _i64, _vp, _i64,
-                                         _vp, _sz, _vp]),
-    "rp_mmoe_combine_fwd": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
-    "rp_mmoe_combine_bwd": (C.c_int, [_vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp]),
-    "rp_cin_bs_fits": (C.c_int, [_i32, _i32, _i32]),
-    "rp_cin_bs_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
-    "rp_cin_bs_bwd_x": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _i64, _i64, _vp]),
-    "rp_cin_bs_bwd_w_workspace_bytes": (C.c_int, [_i64, _i32, C.POINTER(_sz)]),
-    "rp_cin_bs_bwd_w": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _sz, _vp]),
-    "rp_cin_pair_fits": (C.c_int, [_i32, _i32, _i32]),
-    "rp_cin_pair_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp]),
-    "rp_cin_pair_bwd_x": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _i64, _i32, _vp]),
-    "rp_cin_pair_bwd_w_workspace_bytes": (C.c_int, [_i64, _i32, _i32, C.POINTER(_sz)]),
-    "rp_cin_pair_bwd_w": (C.c_int, [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _i64, _vp, _sz, _vp]),
-    "rp_cin_last_fits": (C.c_int, [_i32, _i32, _i32]),
-    "rp_cin_last_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _i64, _vp]),
-    "rp_cin_last_bwd_x": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _i64, _i64, _vp]),
-    "rp_cin_last_bwd_v_workspace_bytes": (C.c_int, [_i64, _i32, _i32, C.POINTER(_sz)]),
-    "rp_cin_last_bwd_v": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _vp, _i64, _vp, _sz, _vp]),
-    "rp_cin_pair_pieces": (C.c_int, [_vp, _i32, _i32, _vp, _vp, _vp]),
-    "rp_cin_head_params_fwd": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp]),
-    "rp_cin_head_params_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_float, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
-    "rp_add_scalars": (C.c_int, [_vp, _i64, _vp, C.c_float, _vp, _vp]),
-    "rp_sum_all": (C.c_int, [_vp, _i64, _vp, _vp]),
-    "rp_attention_core_fits": (C.c_int, [_i32, _i32, _i32]),
-    "rp_attention_core_fwd": (C.c_int, [_vp, _i64, _i32, _vp, _i64, _i32, _i32, _i32, _f32, _vp, _vp, _i64, _vp]),
-    "rp_attention_core_bwd": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _i64, _vp, _i64, _i64,
-                                        _vp]),
-    "rp_attention_wide_fits": (C.c_int, [_i32, _i32, _i32]),
-    "rp_attention_wide_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp]),
-    "rp_attention_wide_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i32, _i32, _i32, _f32, _i32, _vp, _i64, _vp, _i64, _i64,
-                                        _vp]),
-    "rp_set_matmul_precision": (C.c_int, [_i32]),
-    "rp_get_matmul_precision": (C.c_int, []),
-    "rp_fm_pool_fwd": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _i64, _vp]),
-    "rp_fm_pool_bwd": (C.c_int, [_vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _i64, _vp]),
-    "rp_batchnorm_workspace_bytes": (C.c_int, [_i64, _i32, C.POINTER(_sz)]),
-    "rp_batchnorm_train_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
-    "rp_batchnorm_train_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _sz,
-                                         _vp]),
-    "rp_batchnorm_apply": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
-    "rp_batchnorm_apply_bwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
-    "rp_batchnorm_update_running": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _f32, _i64, _i32, _vp]),
-    "rp_batchnorm_colsum": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
-    "rp_batchnorm_bwd_sums": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _sz, _vp]),
-    "rp_batchnorm_bwd_apply": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp]),
-    "rp_layernorm_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp, _i64, _i32, _f32, _i32, _vp, _i32, _i64, _i32, _vp]),
-    "rp_layernorm_bwd_workspace_bytes": (C.c_int, [_i32, C.POINTER(_sz)]),
-    "rp_layernorm_bwd": (C.c_int, [_vp, _i64, _f32, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp,
-                                   _vp, _i64, _i32, _vp, _sz, _vp]),
-    "rp_gin_fits": (C.c_int, [_i32, _i32, _i32, _i32]),
-    "rp_gin_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i64, _vp]),
-    "rp_gin_bwd_workspace_bytes": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_sz)]),
-    "rp_gin_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _vp,
-                             _i32, _i32, _i32, _i32, _i64, _vp, _sz, _vp]),
-    "rp_ccpm_fits": (C.c_int, [_i32, _i32, _i32, _ip, _ip, _ip]),
-    "rp_ccpm_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _ip, _ip, _ip, _i64, _vp]),
-    "rp_ccpm_bwd_workspace_bytes": (C.c_int, [_i32, _ip, _ip, C.POINTER(_sz)]),
-    "rp_ccpm_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _i32, _i32, _i32, _ip, _ip, _ip, _i64, _vp,
-                              _sz, _vp]),
-    "rp_bilinear_fits": (C.c_int, [_i32, _i32, _i32, _i32]),
-    "rp_bilinear_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i64, _vp]),
-    "rp_bilinear_bwd_workspace_bytes": (C.c_int, [_i32, _i32, _i32, _i32, C.POINTER(_sz)]),
-    "rp_bilinear_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _i32, _i32, _i32,
-                                  _i32, _i32, _i64, _vp, _sz, _vp]),
-    "rp_lognet_fits": (C.c_int, [_i32, _i32, _i32]),
-    "rp_lognet_plan": (C.c_int, [_i64, _i32, _ip, C.POINTER(_i64)]),
-    "rp_lognet_workspace_bytes": (C.c_int, [_i32, _i32, C.POINTER(_sz)]),
-    "rp_lognet_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i64, _i64, _i32, _i32,
-                                _i32, _i32, _vp, _sz, _vp]),
-    "rp_lognet_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _vp, _f32, _vp, _i64, _vp, _vp,
-                                _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
-    "rp_pair_fc_partials": (C.c_int, [_i64]),
-    "rp_pair_fc_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "rp_pair_fc_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "rp_dice_gate_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp]),
-    "rp_dice_gate_bwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _i64, _i32, _vp]),
-    "rp_mlp_tail_fits": (C.c_int, [_i32, _i32, _i64]),
-    "rp_mlp_tail_fwd": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp]),
-    "rp_mlp_tail_bwd_workspace_bytes": (C.c_int, [_i64, _i32, C.POINTER(_sz)]),
-    "rp_mlp_tail_bwd": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _sz, _vp]),
-    "rp_mlp_tail_bwd_parts": (C.c_int, [_vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, _sz, _i32, _vp]),
-    "rp_mlp_tail_loss_partials": (C.c_int, [_i64]),
-    "rp_mlp_tail_fwd_bce": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _f32, _vp, _vp, _i64, _vp]),
-    "rp_mlp_tail_bwd_bce": (C.c_int, [_vp, _vp, _vp, _f32, _f32, _vp, _i32, _vp, _vp, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp,
-                                      _sz, _i32, _vp]),
-    "rp_loss_finish": (C.c_int, [_vp, _i32, _f32, _vp, _vp]),
-    "rp_dropout_fwd": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _f32, C.c_uint64, C.c_uint64, _vp]),
-    "rp_dropout_fwd_dev": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _i32, _f32, C.c_uint64, C.c_uint64, _vp, _vp]),
-    "rp_counter_add_u64": (C.c_int, [_vp, C.c_uint64, _vp]),
-    "rp_dropout_bwd": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _f32, _vp]),
-    "rp_loss_partials": (C.c_int, [_i64]),
-    "rp_sigmoid_bce_fwd": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp]),
-    "rp_sigmoid_bce_fwd_accum": (C.c_int, [_vp, _i32, _i32, _vp, _i64, _f32, _f32, _vp, _vp, _vp, _vp]),
-    "rp_sigmoid_bce_bwd": (C.c_int, [_vp, _vp, _vp, _i64, _f32, _f32, _i32, _vp, _vp]),
-    "rp_pair_loss_fwd": (C.c_int, [_vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "rp_pair_loss_bwd": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _i32, _vp, _vp, _vp]),
-    "rp_adam_step": (C.c_int, [_vp, _vp, _vp, _vp, _vp, _i32, _f64, _f64, _f64, _f64, _i64, _i32, _vp, _vp, _vp]),
-    "rp_counter_add": (C.c_int, [_vp, _i32, _vp]),
-    "rp_counters_add": (C.c_int, [_vp, _i32, _i32, _vp]),
-    "rp_accumulate": (C.c_int, [_vp, _vp, _i64, _vp]),
-    "rp_embed_keys": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _vp, _vp, _vp]),
-    "rp_shard_keys": (C.c_int, [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp, _vp, _vp]),
-    "rp_route_workspace_bytes": (C.c_int, [_i64, _i32, C.POINTER(_sz)]),
-    "rp_route_build": (C.c_int, [_vp, _sz, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
-    "rp_route_pad": (C.c_int, [_vp, _vp, _i64, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-    "rp_route_field_major": (C.c_int, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp]),
-    "rp_adam_step_scalars": (C.c_int, [_f64, _f64, _f64, _f64, _i64, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
-    "rp_adam_step_scalars_range": (C.c_int, [_f64, _f64, _f64, _f64, _i64, _i64, _vp]),
-    "rp_lazy_adam_rows": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f64, _f64, _f64,
-                                    _vp, _i64, _vp, _vp]),
-    "rp_lazy_adam_flush": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _vp, _i64, _vp]),
-    "rp_lazy_adam_catchup": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _f64, _f64, _f64,
-                                       _vp, _i64, _vp, _vp, _vp]),
-    "rp_lazy_adam_flush_deferred": (C.c_int, [_i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _f64, _f64, _f64, _vp, _i64,
-                                              _vp, _vp]),
-    "rp_rows_to_bf16": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _vp]),
-    "rp_linear_wgrad_xbf16": (C.c_int, [_vp, _i64, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _sz, _vp]),
-    "rp_embed_gather_pool_fwd": (C.c_int, [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp, _vp, _vp]),
-    "rp_embed_pool_bwd": (C.c_int, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _i32, _vp, _sz, _vp]),
-    "rp_seq_pool_fwd": (C.c_int, [_vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp]),
-    "rp_seq_pool_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
-    "rp_lazy_adam_cf_terms": (C.c_int, [_f64, C.POINTER(C.c_int)]),
-    "rp_lazy_adam_cf_table": (C.c_int, [_vp, _i64, _i64, _f64, _f64, _vp, _i64, _i64, _vp, _vp]),
-    "rp_metrics_workspace_bytes": (C.c_int, [_i64, C.POINTER(_sz)]),
-    "rp_binary_metrics": (C.c_int, [_vp, _sz, _vp, _vp, _i64, _f64, _i32, _vp, _vp]),
-    "rp_softmax_ce_geometry": (C.c_int, [C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32), C.POINTER(_i32)]),
-    "rp_softmax_ce_splits": (C.c_int, [_i64, _i64, C.POINTER(_i32), C.POINTER(_i64)]),
-    "rp_softmax_ce_workspace_bytes": (C.c_int, [_i64, _i64, _i32, C.POINTER(_sz)]),
-    "rp_softmax_ce_fwd": (C.c_int, [_vp, _i64, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "rp_softmax_ce_bwd": (C.c_int, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _i64, _vp, _vp, _sz, _vp]),
-    "rp_hist_mean_fwd": (C.c_int, [_vp, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp]),
-    "rp_hist_mean_bwd": (C.c_int, [_vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _i64, _vp, _vp]),
-}
+_C_TYPES = {"int": C.c_int, "int32_t": C.c_int, "int64_t": C.c_int64, "uint32_t": C.c_uint32, "uint64_t": C.c_uint64,
+            "size_t": C.c_size_t, "float": C.c_float, "double": C.c_double, "rp_stream_t": C.c_void_p}
+_PROTOTYPE = re.compile(r"([A-Za-z_][\w\s]*?[\s*]+)(rp_[a-z0-9_]+)\s*\(([^()]*)\)\s*;")
+
+
+def parse_header(text: str):
+    """-> ({entry point: (restype, [argtypes])} in header order, {RP_* constant: int}) from the text of the C header: every
+    `ret rp_name(params);` outside comments and preprocessor lines, every `#define RP_NAME <integer>`.  A scalar maps to
+    its ctypes type, rp_stream_t and every pointer (host out-parameters included: byref(...), ctypes arrays and string
+    buffers all pass) to c_void_p, a `const char *` result to c_char_p.  Anything else raises, naming the prototype."""
+    text = re.sub(r"/\*.*?\*/", " ", text, flags=re.S)
+    text = re.sub(r"//[^\n]*", " ", text)
+    consts = {m.group(1): int(m.group(2), 0) for m in re.finditer(
+        r"^[ \t]*#[ \t]*define[ \t]+(RP_\w+)[ \t]+\(?(-?(?:0[xX][0-9a-fA-F]+|\d+))\)?[ \t]*$", text, re.M)}
+    text = re.sub(r"^[ \t]*#.*$", " ", text, flags=re.M)
+
+    def ctype(decl: str, proto: str, result: bool = False):
+        words = decl.replace("*", " * ").split()
+        if "[" in decl:
+            raise RuntimeError(f"C header: array parameter {decl.strip()!r} in `{proto}` has no ctypes mapping")
+        if "*" in words:
+            if result and words != ["const", "char", "*"]:
+                raise RuntimeError(f"C header: result type {decl.strip()!r} of `{proto}` has no ctypes mapping")
+            return C.c_char_p if result else C.c_void_p
+        words = [w for w in words if w != "const"]
+        if not result and len(words) == 2:  # `type name`
+            words = words[:1]
+        if len(words) != 1 or words[0] not in _C_TYPES:
+            raise RuntimeError(f"C header: type {decl.strip()!r} in `{proto}` has no ctypes mapping")
+        return _C_TYPES[words[0]]
+
+    sigs = {}
+    for m in _PROTOTYPE.finditer(text):
+        ret, name, params = m.groups()
+        proto = " ".join(m.group(0).split())
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        sigs[name] = (ctype(ret, proto, result=True), [ctype(p, proto) for p in params])
+    calls = set(re.findall(r"\b(rp_[a-z0-9_]+)\s*\(", text))
+    if calls != set(sigs):
+        raise RuntimeError(f"C header: not parsed as prototypes: {sorted(calls - set(sigs))}")
+    return sigs, consts
+
+
+with open(HEADER_PATH) as _f:
+    _SIGNATURES, _RP = parse_header(_f.read())
+ABI_VERSION = _RP["RP_ABI_VERSION"]  # rp_version(): bumped with every change of the entry points' prototypes
+MAX_FIELDS = _RP["RP_MAX_FIELDS"]
+ACT_NONE, ACT_RELU, ACT_MASK, ACT_TANH, ACT_SIGMOID, ACT_LEAKY = (
+    _RP["RP_ACT_" + n] for n in ("NONE", "RELU", "MASK", "TANH", "SIGMOID", "LEAKY"))
 EXPORTED_SYMBOLS = tuple(_SIGNATURES.keys())
 
 
@@ -347,6 +164,34 @@ def _rowmajor(t: torch.Tensor, name: str) -> int:
     if t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
         raise RuntimeError(f"{name}: need a 2-D tensor with unit inner stride, got {tuple(t.shape)}/{t.stride()}")
     return t.stride(0) if t.shape[0] > 1 else max(t.stride(0), t.shape[1])
+
+
+def _rows(t: torch.Tensor, name: str, cols: int, B: Optional[int] = None) -> int:
+    """The contract of a row buffer a kernel reads or writes in place — float32 [B, >= cols], unit inner stride, rows that
+    do not overlap — checked in that order -> leading dimension.  Host-side only: a validator runs every such check first
+    and the device checks (_req) last, so a refusal never depends on where the tensor lives."""
+    if t.dtype != torch.float32:
+        raise RuntimeError(f"{name}: expected torch.float32, got {t.dtype}")
+    if t.dim() != 2:
+        raise RuntimeError(f"{name}: need a 2-D tensor, got {tuple(t.shape)}")
+    if t.shape[1] > 1 and t.stride(1) != 1:
+        raise RuntimeError(f"{name}: need unit inner stride, got {tuple(t.shape)}/{t.stride()}")
+    if t.shape[1] < cols:
+        raise RuntimeError(f"{name} {tuple(t.shape)}: rows narrower than {cols}")
+    if t.shape[0] > 1 and t.stride(0) < cols:
+        raise RuntimeError(f"{name} {tuple(t.shape)} / strides {t.stride()}: rows overlap, row stride narrower than {cols}")
+    if B is not None and t.shape[0] != B:
+        raise RuntimeError(f"{name} {tuple(t.shape)}: expected {B} rows")
+    return _rowmajor(t, name)
+
+
+def _params(named) -> None:
+    """(name, tensor) pairs of a parameter list: float32 and contiguous (host-side, like _rows)"""
+    for name, t in named:
+        if t.dtype != torch.float32:
+            raise RuntimeError(f"{name}: expected torch.float32, got {t.dtype}")
+        if not t.is_contiguous():
+            raise RuntimeError(f"{name} must be contiguous")
 
 
 # ---- device memory: ONE allocator, and one rule for recorded steps ----------------------------------------------------
@@ -610,10 +455,10 @@ def sort_pairs(keys: torch.Tensor, end_bit: int = 32, out=None, workspace=None):
     return ko, po
 
 
-METRIC_AUC, METRIC_LOGLOSS = 1, 2
+METRIC_AUC, METRIC_LOGLOSS = _RP["RP_METRIC_AUC"], _RP["RP_METRIC_LOGLOSS"]
 # the launches of rp_binary_metrics in issue order: name -> RP_METRICS_STAGE_* bit (a measurement issues them one by one)
-METRICS_STAGES = {"key": 0x100, "sort": 0x200, "tile_sums": 0x400, "tile_scan": 0x800, "group_neg": 0x1000, "rank": 0x2000,
-                  "finish": 0x4000}
+METRICS_STAGES = {s: _RP["RP_METRICS_STAGE_" + s.upper()]
+                  for s in ("key", "sort", "tile_sums", "tile_scan", "group_neg", "rank", "finish")}
 
 
 def metrics_workspace(n: int, device) -> torch.Tensor:
@@ -1839,13 +1684,13 @@ def attention_wide_fits(T: int, H: int, a: int) -> bool:
 
 
 def _attention_wide_dims(qkv, xres, T: int, a: int):
+    ldq = _rows(qkv, "attention_wide: qkv", 3 * a)
+    BT = qkv.shape[0]
+    ldr = _rows(xres, "attention_wide: xres", a, BT)
+    if BT % T != 0 or BT == 0:
+        raise RuntimeError(f"attention_wide: qkv {tuple(qkv.shape)} does not hold B*{T} token rows")
     _req(qkv, torch.float32, "qkv")
     _req(xres, torch.float32, "xres")
-    ldq, ldr = _rowmajor(qkv, "qkv"), _rowmajor(xres, "xres")
-    BT = qkv.shape[0]
-    if BT % T != 0 or BT == 0 or xres.shape[0] != BT or qkv.shape[1] < 3 * a or xres.shape[1] < a:
-        raise RuntimeError(f"attention_wide: qkv {tuple(qkv.shape)} / xres {tuple(xres.shape)} do not hold B*{T} token rows of "
-                           f"3*{a} / {a} columns")
     return BT // T, ldq, ldr
 
 
@@ -1897,7 +1742,7 @@ def mmoe_combine_bwd(z, K: int, E: int, T: int, gate, dout):
     return dz
 
 
-MATMUL_MODES = {"fp32": 0, "bf16": 1, "auto": 2, "bf16x3": 3, "bf16x6": 6}
+MATMUL_MODES = {m: _RP["RP_MATMUL_" + m.upper()] for m in ("fp32", "bf16", "auto", "bf16x3", "bf16x6")}
 
 
 def set_matmul_precision(mode: str):
@@ -1976,24 +1821,26 @@ def layernorm_fwd(x, gamma, beta, eps: float, mul=None, out=None, out_scale: flo
     """-> (y, stats).  y = out_scale * (LayerNorm(x[:, :N]) [* mul[:, :N]]) over the N = gamma.numel() leading columns of the
     2-D x, written (accumulate: added) into `out` [M, >= N] (default: a fresh [M, N]); out's columns from N on are written
     as zeros.  stats [M, 2] = (mean, 1 / sqrt(var + eps)) per row: made here or, with stats_given, read."""
+    N = gamma.numel()
+    ldx = _rows(x, "layernorm_fwd: x", N)
+    M = x.shape[0]
+    ldmul = _rows(mul, "layernorm_fwd: mul", N, M) if mul is not None else 0
+    if beta.numel() != N:
+        raise RuntimeError(f"layernorm_fwd: beta of {beta.numel()} elements against {N} normalised columns")
+    if out is not None:
+        _rows(out, "layernorm_fwd: out", N, M)
+    if stats is None and stats_given:
+        raise RuntimeError("layernorm_fwd: stats_given without stats")
     _req(x, torch.float32, "x")
     _req(gamma, torch.float32, "gamma")
     _req(beta, torch.float32, "beta")
-    M, N = x.shape[0], gamma.numel()
-    if x.dim() != 2 or x.shape[1] < N or beta.numel() != N or (mul is not None and (mul.shape[0] != M or mul.shape[1] < N)):
-        raise RuntimeError(f"layernorm_fwd: x {tuple(x.shape)} / mul against {N} normalised columns")
     if out is None:
         out = _new((M, N), torch.float32, x.device)
-    if out.shape[0] != M or out.shape[1] < N:
-        raise RuntimeError(f"layernorm_fwd: out {tuple(out.shape)} for [{M}, >= {N}]")
     if stats is None:
-        if stats_given:
-            raise RuntimeError("layernorm_fwd: stats_given without stats")
         stats = _new((M, 2), torch.float32, x.device)
-    ldmul = _rowmajor(mul, "mul") if mul is not None else 0
     with _Timed("layernorm_fwd", f"{M}x{N}" + ("*mul" if mul is not None else "") + ("+=" if accumulate else ""),
                 4 * M * N * (2 + (mul is not None) + bool(accumulate))):
-        _check(lib().rp_layernorm_fwd(x.data_ptr(), _rowmajor(x, "x"), gamma.data_ptr(), beta.data_ptr(), eps, _ptr(mul), ldmul,
+        _check(lib().rp_layernorm_fwd(x.data_ptr(), ldx, gamma.data_ptr(), beta.data_ptr(), eps, _ptr(mul), ldmul,
                                       out.data_ptr(), _rowmajor(out, "out"), out.shape[1], out_scale, int(accumulate),
                                       _ptr(stats), int(stats_given), M, N, _stream()), "rp_layernorm_fwd")
     return out, stats
@@ -2003,10 +1850,14 @@ def layernorm_bwd(dy, x, stats, gamma, beta, mul=None, dy_scale: float = 1.0, dx
     """-> (dx, dmul, dgamma, dbeta) of layernorm_fwd for the incoming dy [M, >= N] (times dy_scale).  dx [M, x.shape[1]]
     (fresh, or the given one; accumulate: added to it), zeros in its columns from N on; dmul [M, mul.shape[1]] (columns
     from N on are not written) or None."""
+    N = gamma.numel()
+    _rows(x, "layernorm_bwd: x", N)
+    M, dev = x.shape[0], x.device
+    for name, buf in (("dy", dy), ("mul", mul), ("dx", dx)):
+        if buf is not None:
+            _rows(buf, "layernorm_bwd: " + name, N, M)
     _req(dy, torch.float32, "dy")
     _req(x, torch.float32, "x")
-    M, N = x.shape[0], gamma.numel()
-    dev = x.device
     if dx is None:
         if accumulate:
             raise RuntimeError("layernorm_bwd: accumulate without dx")
@@ -2033,18 +1884,20 @@ def gin_fits(F: int, P: int, O: int, D: int) -> bool:
     return bool(lib().rp_gin_fits(F, P, O, D))
 
 
-def _gin_dims(x0, bi, W, alpha, h, F: int):
+def _gin_dims(x0, bi, W, alpha, h, F: int, wide=()):
+    """the checks that need no GPU (shapes, dtypes, contiguity, row widths), then the device check; -> P, O, D.
+    wide: (name, tensor, columns) of the row buffers besides x0 and bi"""
     O, D = W.shape[0], W.shape[1]
     P = alpha.shape[0] // F
-    if W.shape != (O, D, D) or alpha.shape != (P * F, O) or h.numel() != O * D or x0.shape[1] < F * D or bi.shape[1] < P * D \
-            or bi.shape[0] != x0.shape[0]:
-        raise RuntimeError(f"gin: x0 {tuple(x0.shape)} / bi {tuple(bi.shape)} / W {tuple(W.shape)} / alpha {tuple(alpha.shape)} "
-                           f"/ h {tuple(h.shape)} over {F} fields")
-    for t, name in ((x0, "x0"), (bi, "bi"), (W, "W"), (alpha, "alpha"), (h, "h")):
+    if W.shape != (O, D, D) or alpha.shape != (P * F, O) or h.numel() != O * D:
+        raise RuntimeError(f"gin: W {tuple(W.shape)} / alpha {tuple(alpha.shape)} / h {tuple(h.shape)} over {F} fields")
+    _params((("gin: W", W), ("gin: alpha", alpha), ("gin: h", h)))
+    _rows(x0, "gin: x0", F * D)
+    bufs = (("bi", bi, P * D), *wide)
+    for name, buf, cols in bufs:
+        _rows(buf, "gin: " + name, cols, x0.shape[0])
+    for name, t in (("x0", x0), ("W", W), ("alpha", alpha), ("h", h), *[(name, buf) for name, buf, _ in bufs]):
         _req(t, torch.float32, name)
-    for t, name in ((W, "W"), (alpha, "alpha"), (h, "h")):
-        if not t.is_contiguous():
-            raise RuntimeError(f"gin: {name} must be contiguous")
     return P, O, D
 
 
@@ -2063,12 +1916,8 @@ def gin_fwd(x0, bi, W, alpha, h, F: int):
 def gin_bwd(dout, x0, bi, W, alpha, h, F: int, dx0, accumulate: bool, bi_is_x0: bool = False):
     """-> (dbi, dW, dalpha, dh) of gin_fwd for the incoming dout [B, >= O D]; the gradient of x0 is written (accumulate: added)
     into the given dx0 [B, >= F D].  bi_is_x0 (layer 0: bi is the very tensor x0): bi's gradient joins dx0 and dbi is None."""
-    P, O, D = _gin_dims(x0, bi, W, alpha, h, F)
-    _req(dout, torch.float32, "dout")
-    _req(dx0, torch.float32, "dx0")
+    P, O, D = _gin_dims(x0, bi, W, alpha, h, F, wide=[("dout", dout, W.shape[0] * W.shape[1]), ("dx0", dx0, F * W.shape[1])])
     B, dev = x0.shape[0], x0.device
-    if dout.shape[0] != B or dout.shape[1] < O * D or dx0.shape[0] != B or dx0.shape[1] < F * D:
-        raise RuntimeError(f"gin_bwd: dout {tuple(dout.shape)} / dx0 {tuple(dx0.shape)} for B = {B}, O D = {O * D}, F D = {F * D}")
     dbi = None if bi_is_x0 else _new((B, P * D), torch.float32, dev)
     dW, dalpha, dh = _new_like(W), _new_like(alpha), _new_like(h)
     ws, nbytes = _workspace("gin_bwd", F, P, O, D, device=dev)
@@ -2097,9 +1946,9 @@ def ccpm_fits(F: int, D: int, channels, heights, ks) -> bool:
     return bool(lib().rp_ccpm_fits(int(F), int(D), n, _ccpm_ints(channels), _ccpm_ints(heights), _ccpm_ints(ks)))
 
 
-def _ccpm_dims(x, weights, biases, F: int, D: int, ks):
+def _ccpm_dims(x, weights, biases, F: int, D: int, ks, dout=None, dx=None):
     """the checks that need no GPU (shapes, dtypes, contiguity, widths, the range), then the device check; -> channels,
-    heights"""
+    heights.  dout: [B, >= C_last k_last D], dx: [B, >= F D] (the backward's row buffers)"""
     n = len(weights)
     if n == 0 or len(biases) != n or len(ks) != n:
         raise RuntimeError(f"ccpm: {n} weights / {len(biases)} biases / {len(ks)} pooling sizes")
@@ -2108,18 +1957,15 @@ def _ccpm_dims(x, weights, biases, F: int, D: int, ks):
         if w.dim() not in (3, 4) or w.shape[1] != cin or (w.dim() == 4 and w.shape[3] != 1) or b.shape != (w.shape[0],):
             raise RuntimeError(f"ccpm: layer {l}: weight {tuple(w.shape)} / bias {tuple(b.shape)} over {cin} input channels "
                                "(need [C_out, C_in, kh, 1] and [C_out])")
-        for t, name in ((w, "weight"), (b, "bias")):
-            if t.dtype != torch.float32:
-                raise RuntimeError(f"ccpm: layer {l} {name}: expected torch.float32, got {t.dtype}")
-            if not t.is_contiguous():
-                raise RuntimeError(f"ccpm: layer {l} {name} must be contiguous")
+        _params(((f"ccpm: layer {l} weight", w), (f"ccpm: layer {l} bias", b)))
         channels.append(w.shape[0])
         heights.append(w.shape[2])
         cin = w.shape[0]
-    if x.dtype != torch.float32:
-        raise RuntimeError(f"ccpm: x: expected torch.float32, got {x.dtype}")
-    if x.dim() != 2 or x.shape[1] < F * D or (x.shape[0] > 1 and x.stride(0) < F * D):
-        raise RuntimeError(f"ccpm: x {tuple(x.shape)} / strides {x.stride()}: rows narrower than F D = {F * D}")
+    _rows(x, "ccpm: x", F * D)
+    bufs = [(name, buf, cols) for name, buf, cols in (("dout", dout, channels[-1] * int(ks[-1]) * D), ("dx", dx, F * D))
+            if buf is not None]
+    for name, buf, cols in bufs:
+        _rows(buf, "ccpm: " + name, cols, x.shape[0])
     lin = F
     for l, (kh, k) in enumerate(zip(heights, ks)):
         if lin + kh - 1 < k:
@@ -2130,6 +1976,8 @@ def _ccpm_dims(x, weights, biases, F: int, D: int, ks):
     _req(x, torch.float32, "x")
     for t in list(weights) + list(biases):
         _req(t, torch.float32, "ccpm parameter")
+    for name, buf, _ in bufs:
+        _req(buf, torch.float32, name)
     return channels, heights
 
 
@@ -2160,17 +2008,10 @@ def ccpm_fwd(x, weights, biases, F: int, D: int, ks):
 def ccpm_bwd(dout, x, weights, biases, F: int, D: int, ks, dx=None):
     """-> (dx, dWs, dbs) of ccpm_fwd for the incoming dout [B, >= C_last k_last D], rebuilt from x alone (rp_ccpm_bwd).  dx: a
     [B, >= F D] buffer to write the first F D columns of (the others are left alone); a fresh [B, F D] one otherwise."""
-    channels, heights = _ccpm_dims(x, weights, biases, F, D, ks)
+    channels, heights = _ccpm_dims(x, weights, biases, F, D, ks, dout=dout, dx=dx)
     B, n, dev = x.shape[0], len(weights), x.device
-    width = channels[-1] * int(ks[-1]) * D
-    if dout.dtype != torch.float32 or dout.dim() != 2 or dout.shape[0] != B or dout.shape[1] < width:
-        raise RuntimeError(f"ccpm_bwd: dout {tuple(dout.shape)} {dout.dtype} for B = {B}, width {width}")
-    _req(dout, torch.float32, "dout")
     if dx is None:
         dx = _new((B, F * D), torch.float32, dev)
-    _req(dx, torch.float32, "dx")
-    if dx.dim() != 2 or dx.shape[0] != B or dx.shape[1] < F * D:
-        raise RuntimeError(f"ccpm_bwd: dx {tuple(dx.shape)} for B = {B}, F D = {F * D}")
     dWs, dbs = [_new_like(w) for w in weights], [_new_like(b) for b in biases]
     ws, wbytes = _workspace("ccpm_bwd", n, _ccpm_ints(channels), _ccpm_ints(heights), device=dev)
     nbytes, flops = _ccpm_cost(B, F, D, channels, heights, ks)
@@ -2182,7 +2023,7 @@ def ccpm_bwd(dout, x, weights, biases, F: int, D: int, ks, dx=None):
     return dx, dWs, dbs
 
 
-BILINEAR_TYPES = {"field_all": 0, "field_each": 1, "field_interaction": 2}  # RP_BILINEAR_*
+BILINEAR_TYPES = {"field_" + t: _RP["RP_BILINEAR_" + t.upper()] for t in ("all", "each", "interaction")}
 _BIL_TABLES: dict = {}
 _BIL_WMAPS: dict = {}
 
@@ -2232,16 +2073,8 @@ def _bilinear_dims(x, F: int, D: int, weights, bilinear_type, senet, n_dense: in
         raise RuntimeError(f"bilinear: unknown bilinear_type {bilinear_type!r}")
     R = 0 if senet is None else int(senet[0].shape[0])
     params = list(weights) + ([] if senet is None else list(senet))
-    for k, w in enumerate(params):
-        if w.dtype != torch.float32:
-            raise RuntimeError(f"bilinear: parameter {k}: expected torch.float32, got {w.dtype}")
-        if not w.is_contiguous():
-            raise RuntimeError(f"bilinear: parameter {k} must be contiguous")
-    if x.dtype != torch.float32:
-        raise RuntimeError(f"bilinear: x: expected torch.float32, got {x.dtype}")
-    need = F * D + n_dense
-    if x.dim() != 2 or x.shape[1] < need or (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < need):
-        raise RuntimeError(f"bilinear: x {tuple(x.shape)} / strides {x.stride()}: rows narrower than F D + dense = {need}")
+    _params((f"bilinear: parameter {k}", w) for k, w in enumerate(params))
+    _rows(x, "bilinear: x", F * D + n_dense)
     if F < 2 or len(weights) != bilinear_weight_count(F, t) or any(tuple(w.shape) != (D, D) for w in weights):
         raise RuntimeError(f"bilinear: {len(weights)} matrices for F = {F}, D = {D}, type {bilinear_type!r} "
                            "(need 1 / F / F (F - 1) / 2 of shape [D, D])")
@@ -2253,8 +2086,7 @@ def _bilinear_dims(x, F: int, D: int, weights, bilinear_type, senet, n_dense: in
     P = F * (F - 1) // 2
     width = (2 if R else 1) * P * D + n_dense
     for name, buf, cols in [(n, b, width) for n, b in wide] + ([("dx", dx, F * D)] if dx is not None else []):
-        if buf.dtype != torch.float32 or buf.dim() != 2 or buf.shape[0] != x.shape[0] or buf.shape[1] < cols:
-            raise RuntimeError(f"bilinear: {name} {tuple(buf.shape)} {buf.dtype} for B = {x.shape[0]}: rows narrower than {cols}")
+        _rows(buf, "bilinear: " + name, cols, x.shape[0])
     _req(x, torch.float32, "x")
     for w in params:
         _req(w, torch.float32, "bilinear parameter")
@@ -2323,23 +2155,17 @@ def lognet_plan(B: int, D: int):
 
 def _lognet_dims(x, F: int, D: int, W, vecs1, vecs2, wide=()):
     """the checks rp_lognet_fwd / rp_lognet_bwd share (shapes and types first, the device last) -> L"""
-    for name, t in (("x", x), ("W", W)):
-        if t.dtype is not torch.float32:
-            raise RuntimeError(f"lognet: {name}: expected torch.float32, got {t.dtype}")
     if W.dim() != 2 or W.shape[1] != F or not W.is_contiguous():
         raise RuntimeError(f"lognet: W {tuple(W.shape)} for F = {F}: expected a contiguous [L, F]")
     L = W.shape[0]
-    if x.dim() != 2 or x.shape[1] < F * D or (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < F * D):
-        raise RuntimeError(f"lognet: x {tuple(x.shape)} / strides {x.stride()}: rows narrower than F D = {F * D}")
+    _params([("lognet: W", W)] + [("lognet: a BatchNorm vector", v) for v in (*vecs1, *vecs2)])
+    _rows(x, "lognet: x", F * D)
     for n, vecs in ((F, vecs1), (L, vecs2)):
         for v in vecs:
-            if v.dtype is not torch.float32 or v.numel() != n or not v.is_contiguous():
-                raise RuntimeError(f"lognet: a BatchNorm vector of {v.numel()} {v.dtype} elements, expected {n} contiguous "
-                                   "torch.float32")
+            if v.numel() != n:
+                raise RuntimeError(f"lognet: a BatchNorm vector of {v.numel()} elements, expected {n}")
     for name, buf, cols in wide:
-        if buf.dtype is not torch.float32 or buf.dim() != 2 or buf.shape[0] != x.shape[0] or buf.shape[1] < cols \
-                or (buf.shape[1] > 1 and buf.stride(1) != 1):
-            raise RuntimeError(f"lognet: {name} {tuple(buf.shape)} {buf.dtype} for B = {x.shape[0]}: rows narrower than {cols}")
+        _rows(buf, "lognet: " + name, cols, x.shape[0])
     if not lognet_fits(F, D, L):
         raise RuntimeError(f"lognet: F={F} D={D} L={L}: outside rp_lognet_fits")
     for t in (x, W, *vecs1, *vecs2, *[buf for _, buf, _ in wide]):
@@ -2484,7 +2310,7 @@ def sigmoid_bce_bwd(pred, label, gloss, apply_sigmoid: bool = True, p_eps: float
     return dz
 
 
-PAIR_ESSM, PAIR_AITM = 0, 1  # RP_PAIR_*
+PAIR_ESSM, PAIR_AITM = _RP["RP_PAIR_ESSM"], _RP["RP_PAIR_AITM"]
 
 
 def _pair_vectors(tensors, names):

@@ -542,7 +542,7 @@ class EmbeddingLayer(nn.Module):
         from ... import hip
         F, D = len(self.emb_feature), self.embedding_dim
         d = F * D + n_dense
-        ldx = (d + pad_to - 1) // pad_to * pad_to
+        ldx = Fh.padded(d, pad_to)
         w = linear.weight
         # (the answer only depends on shapes, alignment and the matrix-core mode: remembered per weight tensor — the check
         #  runs in every forward and used to stage the weight and cross the C ABI each time)
@@ -640,7 +640,7 @@ class EmbeddingLayer(nn.Module):
             return out
         F, D = len(idx), self.embedding_dim
         d = F * D + len(dense)
-        ldx = (d + pad_to - 1) // pad_to * pad_to
+        ldx = Fh.padded(d, pad_to)
         dense = [t if (t.dtype is torch.float32 and t.dim() == 1 and t.is_contiguous()) else t.float().reshape(-1).contiguous()
                  for t in dense]
         src = tuple(X[c] for c in self.emb_feature)
@@ -794,7 +794,7 @@ class EmbeddingLayer(nn.Module):
         for all fields in order; src: the batch's id tensors (identity = sort cache key) or None."""
         F, D = len(idx), self.embedding_dim
         d = F * D + len(dense)
-        ldx = (d + pad_to - 1) // pad_to * pad_to
+        ldx = Fh.padded(d, pad_to)
         dense = [t.float().reshape(-1).contiguous() for t in dense]
         row_base, row_count = meta if meta is not None else (self.row_base, self.row_count)
         self._presorted = None

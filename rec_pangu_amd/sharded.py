@@ -785,7 +785,7 @@ class ShardedEmbeddingLayer(nn.Module):
         self._take_prepared(X)
         rows, slot_of_pair, slot_sorted, pos_sorted = _ShardedRows.apply(self, keys, self.local_arena)
         d = F * D + len(dense)
-        ldx = (d + pad_to - 1) // pad_to * pad_to
+        ldx = Fh.padded(d, pad_to)
         dense = [t.float().reshape(-1).contiguous() for t in dense]
         out = _RowsToX.apply(rows, slot_of_pair, dense, slot_sorted, pos_sorted, b, F, ldx, want_fm, self._err)
         self._route_ahead()
@@ -798,7 +798,7 @@ class ShardedEmbeddingLayer(nn.Module):
         from . import hip
         F, D = len(self.emb_feature), self.embedding_dim
         d = F * D + n_dense
-        ldx = (d + pad_to - 1) // pad_to * pad_to
+        ldx = Fh.padded(d, pad_to)
         return (self.local_arena.is_cuda and D == 64 and linear.out_features == 64 and linear.in_features == d
                 and self.lbits + max(1, (self.world - 1).bit_length()) <= 31
                 and hip.get_matmul_precision() != "fp32"
@@ -813,7 +813,7 @@ class ShardedEmbeddingLayer(nn.Module):
         scaled = self._scaled = [False]  # set by _RowsToLinear.backward once it has applied the 1/G itself
         rows, slot_of_pair, slot_sorted, pos_sorted = _ShardedRows.apply(self, keys, self.local_arena)
         d = F * D + len(dense)
-        ldx = (d + pad_to - 1) // pad_to * pad_to
+        ldx = Fh.padded(d, pad_to)
         dense = [t.float().reshape(-1).contiguous() for t in dense]
         fm_lists, self._route_fm = getattr(self, "_route_fm", None), None
         out = _RowsToLinear.apply(rows, slot_of_pair, dense, slot_sorted, pos_sorted, b, F, ldx, linear.weight, linear.bias,
