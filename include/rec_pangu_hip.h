@@ -1143,6 +1143,53 @@ int rp_graph_node_counts(void *graph, int *n_kernel, int *n_other);
  * input buffers of a captured step.  Host arrays of device addresses; buffers must not overlap. */
 int rp_multi_copy(void *const *dst_ptrs, const void *const *src_ptrs, const uint64_t *bytes, int n, rp_stream_t stream);
 
+/* ---- sequence recall: the GRU recurrence of GRU4Rec and NARM (csrc/gru.hip) and NARM's attention readout (csrc/narm.hip) ----
+ * replaces nn.GRU(batch_first=True) of rec_pangu/models/layers/sequence.py:231-251 (packed by length) and
+ * rec_pangu/models/sequence/narm.py:21,49 (all L positions) with its autograd.  torch's gates in the order r, z, n, h_0 = 0;
+ * ONE layer and direction per call, all L steps in one launch (plus one small launch that pads the weights).
+ *   input: either ids int64 [B, L] + E [V, in] (rows gathered inside the kernel; an id outside [0, V) sets *err_flag and
+ *          reads row 0) or a dense X [B, L, in]; exactly one of ids / X is non-NULL.
+ *   W_ih [3H, in], W_hh [3H, H], b_ih / b_hh [3H] or both NULL.  steps int32 [B]: row b takes min(steps[b], L) steps
+ *   (packed: its length; full: L).  last int32 [B]: h_last[b] = H_all[b, last[b]], zero when last[b] < 0 or >= steps[b].
+ *   H_all [B, L, H]: zero at t >= steps[b]; it is all the backward keeps besides the inputs.
+ * rp_gru_bwd: dH_all [B, L, H] and dh_last [B, H] are the arriving gradients (either may be NULL); dX [B, L, in] (NULL: not
+ * wanted; in id mode it is the per-position gradient row rp_hist_rows_bwd reduces into dE); dW_ih, dW_hh (both or neither),
+ * db_ih, db_hh (both or neither) are WRITTEN.  Deterministic: gate-gradient buffers [B, L, 3H] contracted by rp_linear_wgrad,
+ * db_hh's n part through per-workgroup slabs added in workgroup order.
+ * 1 <= in, H <= max_h of rp_gru_geometry (128) and L >= 1, RP_ERR_ARG otherwise (nothing is launched).  tb = batch rows per
+ * workgroup.  Workspace (the same query for both calls, 16-byte aligned), A(x) = x rounded up to 256, Hp / Kp = H / in
+ * rounded up to 32:
+ *   A(12 Hp Kp) + A(12 Hp Hp) + 2 A(12 B L H) + A(4 H ceil(B / tb)) + (ids_mode ? A(4 B L in) : 0)
+ *   + A(max(rp_linear_wgrad_workspace_bytes(B L, 3H, in), rp_linear_wgrad_workspace_bytes(B L, 3H, H))) */
+int rp_gru_geometry(int *tb, int *max_h);
+int rp_gru_workspace_bytes(int64_t B, int64_t L, int in, int H, int ids_mode, size_t *bytes);
+int rp_gru_fwd(const int64_t *ids, const float *E, int64_t V, const float *X, int64_t B, int64_t L, int in, int H,
+               const float *W_ih, const float *W_hh, const float *b_ih, const float *b_hh, const int32_t *steps,
+               const int32_t *last, float *H_all, float *h_last, int32_t *err_flag, void *workspace, size_t workspace_bytes,
+               rp_stream_t stream);
+int rp_gru_bwd(const int64_t *ids, const float *E, int64_t V, const float *X, int64_t B, int64_t L, int in, int H,
+               const float *W_ih, const float *W_hh, const float *b_ih, const float *b_hh, const int32_t *steps,
+               const int32_t *last, const float *H_all, const float *dH_all, const float *dh_last, float *dX, float *dW_ih,
+               float *dW_hh, float *db_ih, float *db_hh, void *workspace, size_t workspace_bytes, rp_stream_t stream);
+/* dE[keys, :] += the sum of the per-position gradient rows g[pos, :] of every sorted (id, flat position) pair with that id,
+ * id 0 skipped (padding_idx = 0): rp_hist_mean_bwd's walk over a [B L, D] gradient, one writer per row, a fixed order */
+/* out[p, :] = E[ids[p], :] for p < n (the lookup alone, for a dropout between it and the GRU); an id outside [0, V) sets
+ * *err_flag and reads row 0 */
+int rp_hist_rows_fwd(const float *E, int64_t V, int D, const int64_t *ids, int64_t n, float *out, int32_t *err_flag,
+                     rp_stream_t stream);
+int rp_hist_rows_bwd(const int32_t *sorted_keys, const int32_t *sorted_pos, int64_t n, int D, int64_t V, const float *g,
+                     int64_t ldg, float *dE, rp_stream_t stream);
+/* NARM's readout: alpha[b, l] = sum_h v[h] (ids[b, l] > 0) sigmoid(q1[b, l, h] + q2[b, h]);
+ *   out[b] = [sum_l alpha[b, l] G[b, l, :], ht[b, :]]  (out [B, 2H], alpha [B, L] kept for the backward).  1 <= H <= 128.
+ * The backward WRITES dq1 [B, L, H], dq2 [B, H], dG [B, L, H], dht [B, H] and dv [H] (slabs of at most 1024 workgroups added in
+ * workgroup order; workspace: rp_narm_attn_workspace_bytes = 4 H min(ceil(B / 4), 1024), at least 4 H). */
+int rp_narm_attn_workspace_bytes(int64_t B, int H, size_t *bytes);
+int rp_narm_attn_fwd(const float *q1, const float *q2, const float *v, const int64_t *ids, const float *G, const float *ht,
+                     int64_t B, int64_t L, int H, float *alpha, float *out, rp_stream_t stream);
+int rp_narm_attn_bwd(const float *q1, const float *q2, const float *v, const int64_t *ids, const float *G, const float *alpha,
+                     const float *dout, int64_t B, int64_t L, int H, float *dq1, float *dq2, float *dG, float *dht, float *dv,
+                     void *workspace, size_t workspace_bytes, rp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -170,10 +170,11 @@ __global__ __launch_bounds__(256) void hist_mean_fwd_kernel(const float *__restr
 }
 
 // Its backward into the item table's DENSE gradient: dE[v, :] += sum over the positions (b, l) with hist[b, l] == v of
-// (mask[b, l] / L) g[b, :] — except v == 0, whatever its mask: the table is nn.Embedding(padding_idx=0), whose row 0 takes no
+// (mask[b, l] / L) g[b, :] (ROWS: of the position's own gradient row g[b * L + l, :], unscaled and unmasked — the id-mode
+// input gradient of the GRU recurrence, csrc/gru.hip) — except v == 0, whatever its mask: the table is nn.Embedding(padding_idx=0), whose row 0 takes no
 // gradient from lookups.  From the (id, flat position) pairs sorted by id (stable: ascending position inside a run): the lane
 // group at a run's first pair walks the run in order and adds the sum to the row once — one writer per row, a fixed order.
-template <int TPR, int VEC>
+template <int TPR, int VEC, bool ROWS = false>
 __global__ __launch_bounds__(256) void hist_mean_bwd_kernel(const int32_t *__restrict__ sk, const int32_t *__restrict__ sp,
                                                             int64_t n, int64_t L, int D, int64_t V,
                                                             const float *__restrict__ mask, const float *__restrict__ g,
@@ -190,6 +191,10 @@ __global__ __launch_bounds__(256) void hist_mean_bwd_kernel(const int32_t *__res
         typename PVT::T acc = PVT::zero();
         for (int64_t q = p; q < n && sk[q] == key; ++q) {
             const int64_t pos = sp[q];
+            if (ROWS) {
+                acc += PVT::load(g + pos * ldg + c);
+                continue;
+            }
             const float mk = mask[pos];
             if (mk != 0.f) acc += PVT::load(g + (pos / L) * ldg + c) * PVT::splat(mk * inv_l);
         }
@@ -332,5 +337,51 @@ extern "C" int rp_hist_mean_bwd(const int32_t *sorted_keys, const int32_t *sorte
     RP_POOL_DISPATCH(tpr, vec, CALL);
 #undef CALL
     RP_LAUNCH_CHECK("hist_mean_bwd");
+    return RP_OK;
+}
+
+extern "C" int rp_hist_rows_bwd(const int32_t *sorted_keys, const int32_t *sorted_pos, int64_t n, int D, int64_t V,
+                                const float *g, int64_t ldg, float *dE, rp_stream_t stream) {
+    RP_REQUIRE(sorted_keys && sorted_pos && g && dE, "hist_rows_bwd: null pointer");
+    RP_REQUIRE(n >= 0 && D >= 1 && V >= 1 && ldg >= D, "hist_rows_bwd: bad n / D / V / ldg");
+    if (n == 0) return RP_OK;
+    const int vec = (D % 4 == 0 && ldg % 4 == 0 && rp_aligned16(g) && rp_aligned16(dE)) ? 4 : 1;
+    const int tpr = pool_tpr(D, vec);
+    const unsigned grid = (unsigned)rp_cdiv(n, 256 / tpr);
+    hipStream_t s = (hipStream_t)stream;
+#define CALL(T, VV)                                                                                                        \
+    hipLaunchKernelGGL((hist_mean_bwd_kernel<T, VV, true>), dim3(grid), dim3(256), 0, s, sorted_keys, sorted_pos, n, (int64_t)1, \
+                       D, V, (const float *)nullptr, g, ldg, dE)
+    RP_POOL_DISPATCH(tpr, vec, CALL);
+#undef CALL
+    RP_LAUNCH_CHECK("hist_rows_bwd");
+    return RP_OK;
+}
+
+// out[p, :] = E[ids[p], :] for the n positions of a history — the lookup on its own, for the one case that needs the rows as
+// a tensor (a dropout between the lookup and the GRU: NARM's emb_dropout while training)
+__global__ __launch_bounds__(256) void hist_rows_fwd_kernel(const float *__restrict__ E, int64_t V, int D,
+                                                            const int64_t *__restrict__ ids, int64_t n, float *__restrict__ out,
+                                                            int32_t *__restrict__ err_flag) {
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= n * D) return;
+    const int64_t p = e / D;
+    const int c = (int)(e - p * D);
+    int64_t id = ids[p];
+    if (id < 0 || id >= V) {  // reference: IndexError from nn.Embedding on CPU
+        *err_flag = 1;
+        id = 0;
+    }
+    out[e] = E[id * D + c];
+}
+
+extern "C" int rp_hist_rows_fwd(const float *E, int64_t V, int D, const int64_t *ids, int64_t n, float *out, int32_t *err_flag,
+                                rp_stream_t stream) {
+    RP_REQUIRE(E && ids && out && err_flag, "hist_rows_fwd: null pointer");
+    RP_REQUIRE(V >= 1 && D >= 1 && n >= 0, "hist_rows_fwd: bad V / D / n");
+    if (n == 0) return RP_OK;
+    hipLaunchKernelGGL(hist_rows_fwd_kernel, dim3((unsigned)rp_cdiv(n * D, 256)), dim3(256), 0, (hipStream_t)stream, E, V, D, ids,
+                       n, out, err_flag);
+    RP_LAUNCH_CHECK("hist_rows_fwd");
     return RP_OK;
 }

@@ -2054,3 +2054,182 @@ def hist_mean(item_weight: torch.Tensor, hist: torch.Tensor, mask: torch.Tensor,
     if check_indices == "sync":
         _raise_if_flagged(item_weight.device, "index out of range in self")
     return out
+
+
+# ----------------------------------------------------------------------------------------------
+# sequence recall: the GRU encoder of GRU4Rec / NARM (models/layers/sequence.py:231-251, models/sequence/narm.py:49) and
+# NARM's attention readout (narm.py:52-61).  One launch per layer and direction; only the hidden states are saved.
+# ----------------------------------------------------------------------------------------------
+def _gru_layers(rnn):
+    """[(W_ih, W_hh, b_ih, b_hh)] per layer of an nn.GRU (biases None without them)"""
+    out = []
+    for k in range(rnn.num_layers):
+        b = (getattr(rnn, f"bias_ih_l{k}"), getattr(rnn, f"bias_hh_l{k}")) if rnn.bias else (None, None)
+        out.append((getattr(rnn, f"weight_ih_l{k}"), getattr(rnn, f"weight_hh_l{k}")) + b)
+    return out
+
+
+class _HistRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, item_weight, hist):
+        e = item_weight.contiguous()
+        ctx.save_for_backward(hist)
+        ctx.rows = e.shape
+        return hip.hist_rows_fwd(e, hist, _seq_flag(e.device))
+
+    @staticmethod
+    def backward(ctx, g):
+        (hist,) = ctx.saved_tensors
+        de = hip.zeros(ctx.rows, torch.float32, g.device)
+        hip.hist_rows_bwd(hist, g.contiguous(), de)
+        return de, None
+
+
+class _GRUEncode(torch.autograd.Function):
+    """inputs: item_weight | None, x | None, ids | None, steps, last, layers, has_bias, then each layer's parameters"""
+
+    @staticmethod
+    def forward(ctx, item_weight, x, ids, steps, last, n_layers: int, has_bias: bool, *params):
+        ctx.set_materialize_grads(False)  # (GRU4Rec reads h_last only, NARM both: no zero-filled [B, L, H] gradient)
+        per = 4 if has_bias else 2
+        layers = [tuple(p.contiguous() for p in params[k * per:(k + 1) * per]) + ((None, None) if not has_bias else ())
+                  for k in range(n_layers)]
+        e = item_weight.contiguous() if ids is not None else None
+        inp, hs, h_last = x, [], None
+        for k, (w_ih, w_hh, b_ih, b_hh) in enumerate(layers):
+            first_ids = k == 0 and ids is not None
+            h_all, h_last = hip.gru_fwd(ids if first_ids else None, e if first_ids else None, None if first_ids else inp,
+                                        w_ih, w_hh, b_ih, b_hh, steps, last, _seq_flag(w_ih.device) if first_ids else None)
+            hs.append(h_all)
+            inp = h_all
+        ctx.n_layers, ctx.has_bias, ctx.per = n_layers, has_bias, per
+        ctx.e_shape = None if e is None else e.shape
+        # saved between forward and backward: the inputs themselves and layers * B * L * H floats of hidden states
+        ctx.save_for_backward(e, x, ids, steps, last, *hs, *[p for lay in layers for p in lay[:per]])
+        return hs[-1], h_last
+
+    @staticmethod
+    def backward(ctx, dh_all, dh_last):
+        n, per = ctx.n_layers, ctx.per
+        saved = ctx.saved_tensors
+        e, x, ids, steps, last = saved[:5]
+        hs, flat = saved[5:5 + n], saved[5 + n:]
+        need = ctx.needs_input_grad
+        grads = [None] * (n * per)
+        d_in = None
+        dh_all = None if dh_all is None else dh_all.contiguous()
+        dh_last = None if dh_last is None else dh_last.contiguous()
+        for k in range(n - 1, -1, -1):
+            p = flat[k * per:(k + 1) * per]
+            w_ih, w_hh = p[0], p[1]
+            b_ih, b_hh = (p[2], p[3]) if ctx.has_bias else (None, None)
+            first_ids = k == 0 and ids is not None
+            want_dx = k > 0 or (need[0] if first_ids else need[1])
+            want_dw = any(need[7 + k * per:7 + (k + 1) * per])
+            if not (want_dx or want_dw):
+                break  # (nothing below this layer asks for a gradient either)
+            got = hip.gru_bwd(ids if first_ids else None, e if first_ids else None,
+                              None if first_ids else (x if k == 0 else hs[k - 1]), w_ih, w_hh, b_ih, b_hh, steps, last, hs[k],
+                              dh_all, dh_last if k == n - 1 else None, want_dx, want_dw)
+            dh_all = got[0]
+            if want_dw:
+                grads[k * per:(k + 1) * per] = got[1:1 + per]
+            if k == 0:
+                d_in = got[0]
+        de = dx = None
+        if ids is not None and need[0] and d_in is not None:
+            de = hip.zeros(tuple(ctx.e_shape), torch.float32, d_in.device)
+            hip.hist_rows_bwd(ids, d_in, de)
+        elif ids is None and need[1]:
+            dx = d_in
+        return (de, dx, None, None, None, None, None, *grads)
+
+
+def _gru_torch(rnn, e, steps, last, packed: bool):
+    """torch's nn.GRU over e [B, L, in]: the reference's pack / unpack when packed (a zero length raises, as there)"""
+    L = e.shape[1]
+    if packed:
+        seq = torch.nn.utils.rnn.pack_padded_sequence(e, steps.cpu().to(torch.int64), batch_first=True, enforce_sorted=False)
+        out, _ = rnn(seq, None)
+        h_all, _ = torch.nn.utils.rnn.pad_packed_sequence(out, batch_first=True, total_length=L)
+    else:
+        h_all, _ = rnn(e)
+    ok = (last >= 0) & (last < steps)
+    idx = last.clamp(min=0).to(torch.int64).view(-1, 1, 1).expand(-1, 1, h_all.shape[-1])
+    h_last = h_all.gather(1, idx).squeeze(1) * ok.unsqueeze(-1).to(h_all.dtype)
+    return h_all, h_last
+
+
+def gru_encode(rnn, steps: torch.Tensor, last: torch.Tensor, x: torch.Tensor = None, ids: torch.Tensor = None,
+               item_weight: torch.Tensor = None, packed: bool = True, check_indices: str = "sync"):
+    """A multi-layer, one-direction nn.GRU `rnn` (the parameter holder) over a batch of histories, h_0 = 0 ->
+    (H_all [B, L, H], h_last [B, H]) of the top layer.  Input: either ids int64 [B, L] + item_weight [V, in] (the rows of
+    nn.Embedding(padding_idx=0), gathered inside the kernel: no [B, L, in] tensor) or a dense x [B, L, in].  steps [B]: row b
+    takes steps[b] steps (packed: its length, H_all zero behind it; full: L); h_last[b] = H_all[b, last[b]], zero where
+    last[b] < 0 or >= steps[b].  On the HIP device one rp_gru_fwd / rp_gru_bwd launch per layer; on CPU tensors torch's nn.GRU
+    (packed: the reference's pack / unpack, which raises for a zero length)."""
+    dev_t = x if x is not None else item_weight
+    layers = _gru_layers(rnn)
+    if rnn.bidirectional or (rnn.dropout and rnn.training) or getattr(rnn, "proj_size", 0):
+        raise NotImplementedError("gru_encode: one direction, no dropout between the layers, no projection")
+    if not dev_t.is_cuda:
+        e = x if x is not None else torch.nn.functional.embedding(ids, item_weight, padding_idx=0)
+        return _gru_torch(rnn, e, steps, last, packed)
+    n_in, H = layers[0][0].shape[1], rnn.hidden_size
+    if dev_t.dtype != torch.float32 or not hip.gru_fits(n_in, H):
+        hip.note_torch_path(f"gru_encode at in={n_in}, H={H}, {dev_t.dtype} (the kernels take fp32 up to "
+                            f"{hip.gru_geometry()['max_h']} columns)")
+        e = x if x is not None else torch.nn.functional.embedding(ids, item_weight, padding_idx=0)
+        return _gru_torch(rnn, e, steps, last, packed)
+    per = 4 if rnn.bias else 2
+    flat = [p for lay in layers for p in lay[:per]]
+    steps32, last32 = steps.to(torch.int32).contiguous(), last.to(torch.int32).contiguous()
+    h_all, h_last = _GRUEncode.apply(item_weight if ids is not None else None, None if x is None else x.contiguous(),
+                                     None if ids is None else ids.contiguous(), steps32, last32, rnn.num_layers, bool(rnn.bias),
+                                     *flat)
+    if ids is not None and check_indices == "sync":
+        _raise_if_flagged(dev_t.device, "index out of range in self")
+    return h_all, h_last
+
+
+def hist_rows(item_weight: torch.Tensor, hist: torch.Tensor, check_indices: str = "sync"):
+    """nn.Embedding(V, D, padding_idx=0)(hist) as a [B, L, D] tensor: the lookup on its own (row 0 takes no gradient)"""
+    if not item_weight.is_cuda or item_weight.dtype != torch.float32:
+        if item_weight.is_cuda:
+            hip.note_torch_path(f"hist_rows over a {item_weight.dtype} table (the kernels take fp32)")
+        return torch.nn.functional.embedding(hist, item_weight, padding_idx=0)
+    out = _HistRows.apply(item_weight, hist.contiguous())
+    if check_indices == "sync":
+        _raise_if_flagged(item_weight.device, "index out of range in self")
+    return out
+
+
+class _NarmAttention(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, q1, q2, v, ids, gru_out, ht):
+        q1, q2, v, g, ht = q1.contiguous(), q2.contiguous(), v.contiguous().view(-1), gru_out.contiguous(), ht.contiguous()
+        out, alpha = hip.narm_attn_fwd(q1, q2, v, ids, g, ht)
+        ctx.save_for_backward(q1, q2, v, ids, g, alpha)
+        ctx.v_shape = v.shape
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q1, q2, v, ids, g, alpha = ctx.saved_tensors
+        dq1, dq2, dv, dg, dht = hip.narm_attn_bwd(q1, q2, v, ids, g, alpha, dout.contiguous())
+        return dq1, dq2, dv, None, dg, dht
+
+
+def narm_attention(q1: torch.Tensor, q2: torch.Tensor, v: torch.Tensor, ids: torch.Tensor, gru_out: torch.Tensor,
+                   ht: torch.Tensor):
+    """NARM's readout (reference models/sequence/narm.py:54-61): alpha = (mask * sigmoid(q1 + q2[:, None])) @ v with
+    mask = ids > 0, c_local = sum_l alpha * gru_out -> cat([c_local, ht], 1) [B, 2H].  q1, gru_out [B, L, H]; q2, ht [B, H];
+    v [H] (v_t.weight.view(-1)); ids int64 [B, L].  On the HIP device one launch each way plus dv's finishing sum."""
+    H = gru_out.shape[-1]
+    if not gru_out.is_cuda or gru_out.dtype != torch.float32 or not hip.narm_attn_fits(H):
+        if gru_out.is_cuda:
+            hip.note_torch_path(f"narm_attention at H={H}, {gru_out.dtype} (the kernels take fp32 up to H=128)")
+        mask = ids.gt(0).unsqueeze(2).expand_as(gru_out)
+        alpha = torch.matmul(mask * torch.sigmoid(q1 + q2.unsqueeze(1).expand_as(q1)), v.view(-1, 1))
+        return torch.cat([torch.sum(alpha.expand_as(gru_out) * gru_out, 1), ht], 1)
+    return _NarmAttention.apply(q1, q2, v.view(-1), ids.contiguous(), gru_out, ht)

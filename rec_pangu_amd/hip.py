@@ -2919,3 +2919,158 @@ def hist_mean_bwd(hist, mask, g, de):
         _check(lib().rp_hist_mean_bwd(sk.data_ptr(), sp.data_ptr(), B * L, L, D, V, mask.data_ptr(), g.data_ptr(),
                                       _rowmajor(g, "g"), de.data_ptr(), _stream()), "rp_hist_mean_bwd")
     return de
+
+
+# ---- sequence recall: the GRU recurrence (csrc/gru.hip) and NARM's attention readout (csrc/narm.hip) ----------------------
+def gru_geometry() -> dict:
+    """{"TB": batch rows per workgroup, "max_h": largest input / hidden width the kernels take}"""
+    tb, mh = _i32(0), _i32(0)
+    _check(lib().rp_gru_geometry(C.byref(tb), C.byref(mh)), "rp_gru_geometry")
+    return {"TB": tb.value, "max_h": mh.value}
+
+
+def gru_fits(n_in: int, H: int) -> bool:
+    mh = gru_geometry()["max_h"]
+    return 1 <= n_in <= mh and 1 <= H <= mh
+
+
+def gru_workspace_bytes(B: int, L: int, n_in: int, H: int, ids_mode: bool) -> int:
+    n = _sz(0)
+    _check(lib().rp_gru_workspace_bytes(B, L, n_in, H, int(ids_mode), C.byref(n)), "rp_gru_workspace_bytes")
+    return n.value
+
+
+def _gru_args(ids, e, x, w_ih, w_hh, b_ih, b_hh, steps, last):
+    H = w_hh.shape[1]
+    named = [("W_ih", w_ih), ("W_hh", w_hh)] + ([("b_ih", b_ih), ("b_hh", b_hh)] if b_ih is not None else [])
+    _params(named)
+    if (ids is None) == (x is None) or (b_ih is None) != (b_hh is None):
+        raise RuntimeError("gru: give either ids (+ item_weight) or x, and both biases or neither")
+    if ids is not None:
+        _params([("item_weight", e)])
+        _req(ids, torch.int64, "ids")
+        _req(e, torch.float32, "item_weight")
+        (B, L), (V, n_in) = ids.shape, e.shape
+        src = ids
+    else:
+        _req(x, torch.float32, "x")
+        B, L, n_in = x.shape
+        V, src = 0, x
+    if not src.is_contiguous() or w_ih.shape != (3 * H, n_in) or w_hh.shape != (3 * H, H) or \
+            (b_ih is not None and (b_ih.shape != (3 * H,) or b_hh.shape != (3 * H,))):
+        raise RuntimeError(f"gru: need a contiguous input, W_ih [3H, {n_in}], W_hh [3H, H] and biases [3H], H = {H}")
+    for name, t in (("steps", steps), ("last", last)):
+        _req(t, torch.int32, name)
+        if t.shape != (B,) or not t.is_contiguous():
+            raise RuntimeError(f"gru: {name} must be a contiguous int32 [{B}] tensor")
+    for name, t in named:
+        _req(t, torch.float32, name)
+    return B, L, V, n_in, H
+
+
+def gru_fwd(ids, e, x, w_ih, w_hh, b_ih, b_hh, steps, last, err_flag=None):
+    """rp_gru_fwd, one layer -> (H_all [B, L, H], h_last [B, H]); ids int64 [B, L] + e [V, in], or x [B, L, in]"""
+    B, L, V, n_in, H = _gru_args(ids, e, x, w_ih, w_hh, b_ih, b_hh, steps, last)
+    ws, nbytes = _workspace("gru", B, L, n_in, H, int(ids is not None), device=w_ih.device)
+    h_all, h_last = _new((B, L, H), torch.float32, w_ih.device), _new((B, H), torch.float32, w_ih.device)
+    with _Timed("gru_fwd", f"{B}x{L}x{n_in}x{H}", 4 * B * L * (n_in + H), 6 * B * L * H * (n_in + H)):
+        _check(lib().rp_gru_fwd(_ptr(ids), _ptr(e) if ids is not None else None, V, _ptr(x), B, L, n_in, H, w_ih.data_ptr(),
+                                w_hh.data_ptr(), _ptr(b_ih), _ptr(b_hh), steps.data_ptr(), last.data_ptr(), h_all.data_ptr(),
+                                h_last.data_ptr(), _ptr(err_flag), ws.data_ptr(), nbytes, _stream()), "rp_gru_fwd")
+    return h_all, h_last
+
+
+def gru_bwd(ids, e, x, w_ih, w_hh, b_ih, b_hh, steps, last, h_all, dh_all, dh_last, want_dx: bool, want_dw: bool):
+    """rp_gru_bwd, one layer -> (dX [B, L, in] or None, dW_ih, dW_hh, db_ih, db_hh; the last four None unless want_dw,
+    the biases' None without biases)"""
+    B, L, V, n_in, H = _gru_args(ids, e, x, w_ih, w_hh, b_ih, b_hh, steps, last)
+    dev = w_ih.device
+    for name, t, shape in (("H_all", h_all, (B, L, H)), ("dH_all", dh_all, (B, L, H)), ("dh_last", dh_last, (B, H))):
+        if t is not None:
+            _req(t, torch.float32, name)
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise RuntimeError(f"gru_bwd: {name} must be a contiguous {shape} tensor, got {tuple(t.shape)}/{t.stride()}")
+    ws, nbytes = _workspace("gru", B, L, n_in, H, int(ids is not None), device=dev)
+    dx = _new((B, L, n_in), torch.float32, dev) if want_dx else None
+    dwi = _new((3 * H, n_in), torch.float32, dev) if want_dw else None
+    dwh = _new((3 * H, H), torch.float32, dev) if want_dw else None
+    dbi = _new((3 * H,), torch.float32, dev) if (want_dw and b_ih is not None) else None
+    dbh = _new((3 * H,), torch.float32, dev) if (want_dw and b_ih is not None) else None
+    with _Timed("gru_bwd", f"{B}x{L}x{n_in}x{H}", 4 * B * L * (n_in + 8 * H), 18 * B * L * H * (n_in + H)):
+        _check(lib().rp_gru_bwd(_ptr(ids), _ptr(e) if ids is not None else None, V, _ptr(x), B, L, n_in, H, w_ih.data_ptr(),
+                                w_hh.data_ptr(), _ptr(b_ih), _ptr(b_hh), steps.data_ptr(), last.data_ptr(), h_all.data_ptr(),
+                                _ptr(dh_all), _ptr(dh_last), _ptr(dx), _ptr(dwi), _ptr(dwh), _ptr(dbi), _ptr(dbh),
+                                ws.data_ptr(), nbytes, _stream()), "rp_gru_bwd")
+    return dx, dwi, dwh, dbi, dbh
+
+
+def hist_rows_fwd(e, hist, err_flag):
+    """rp_hist_rows_fwd: e [V, D], hist int64 [B, L] -> e[hist] as a [B, L, D] tensor"""
+    _req(e, torch.float32, "item_weight")
+    _req(hist, torch.int64, "hist")
+    if not (e.is_contiguous() and hist.is_contiguous()):
+        raise RuntimeError("hist_rows: item_weight and hist must be contiguous")
+    (B, L), (V, D) = hist.shape, e.shape
+    out = _new((B, L, D), torch.float32, e.device)
+    with _Timed("hist_rows_fwd", f"D={D}", B * L * (D * 8 + 8)):
+        _check(lib().rp_hist_rows_fwd(e.data_ptr(), V, D, hist.data_ptr(), B * L, out.data_ptr(), err_flag.data_ptr(), _stream()),
+               "rp_hist_rows_fwd")
+    return out
+
+
+def hist_rows_bwd(hist, g, de):
+    """rp_hist_rows_bwd: de[hist[b, l]] += g[b, l] for every position whose id is not 0 (g [B, L, D], de [V, D], added into)"""
+    _req(g, torch.float32, "g")
+    _req(de, torch.float32, "dE")
+    B, L = hist.shape
+    V, D = de.shape
+    assert de.is_contiguous() and g.is_contiguous() and g.shape == (B, L, D)
+    sk, sp = sort_pairs(hist.reshape(-1).to(torch.int32))
+    with _Timed("hist_rows_bwd", f"D={D}", B * L * (D * 4 + 8)):
+        _check(lib().rp_hist_rows_bwd(sk.data_ptr(), sp.data_ptr(), B * L, D, V, g.data_ptr(), D, de.data_ptr(), _stream()),
+               "rp_hist_rows_bwd")
+    return de
+
+
+def narm_attn_fits(H: int) -> bool:
+    return 1 <= H <= 128
+
+
+def _narm_args(q1, q2, v, ids, g, ht):
+    B, L, H = g.shape
+    for name, t, shape in (("q1", q1, (B, L, H)), ("q2", q2, (B, H)), ("v", v, (H,)), ("gru_out", g, (B, L, H)),
+                           ("ht", ht, (B, H))):
+        _req(t, torch.float32, name)
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError(f"narm_attention: {name} must be a contiguous {shape} tensor, got {tuple(t.shape)}/{t.stride()}")
+    _req(ids, torch.int64, "ids")
+    if tuple(ids.shape) != (B, L) or not ids.is_contiguous():
+        raise RuntimeError(f"narm_attention: ids must be a contiguous int64 [{B}, {L}] tensor")
+    return B, L, H
+
+
+def narm_attn_fwd(q1, q2, v, ids, g, ht):
+    """rp_narm_attn_fwd -> (out [B, 2H], alpha [B, L])"""
+    B, L, H = _narm_args(q1, q2, v, ids, g, ht)
+    out, alpha = _new((B, 2 * H), torch.float32, g.device), _new((B, L), torch.float32, g.device)
+    with _Timed("narm_attn_fwd", f"{B}x{L}x{H}", 8 * B * L * H):
+        _check(lib().rp_narm_attn_fwd(q1.data_ptr(), q2.data_ptr(), v.data_ptr(), ids.data_ptr(), g.data_ptr(), ht.data_ptr(),
+                                      B, L, H, alpha.data_ptr(), out.data_ptr(), _stream()), "rp_narm_attn_fwd")
+    return out, alpha
+
+
+def narm_attn_bwd(q1, q2, v, ids, g, alpha, dout):
+    """rp_narm_attn_bwd -> (dq1, dq2, dv, dG, dht)"""
+    B, L, H = g.shape
+    _req(dout, torch.float32, "dout")
+    if tuple(dout.shape) != (B, 2 * H) or not dout.is_contiguous():
+        raise RuntimeError(f"narm_attention: the gradient must be a contiguous [{B}, {2 * H}] tensor")
+    dev = g.device
+    dq1, dg = _new((B, L, H), torch.float32, dev), _new((B, L, H), torch.float32, dev)
+    dq2, dht, dv = _new((B, H), torch.float32, dev), _new((B, H), torch.float32, dev), _new((H,), torch.float32, dev)
+    ws, nbytes = _workspace("narm_attn", B, H, device=dev)
+    with _Timed("narm_attn_bwd", f"{B}x{L}x{H}", 16 * B * L * H):
+        _check(lib().rp_narm_attn_bwd(q1.data_ptr(), q2.data_ptr(), v.data_ptr(), ids.data_ptr(), g.data_ptr(),
+                                      alpha.data_ptr(), dout.data_ptr(), B, L, H, dq1.data_ptr(), dq2.data_ptr(), dg.data_ptr(),
+                                      dht.data_ptr(), dv.data_ptr(), ws.data_ptr(), nbytes, _stream()), "rp_narm_attn_bwd")
+    return dq1, dq2, dv, dg, dht

@@ -6,9 +6,10 @@ from .interaction import (InnerProductLayer, FM_Layer, CrossInteractionLayer, Cr
                           CompressedInteractionNet, MaskBlock, GeneralizedInteractionNet,
                           GeneralizedInteraction, BilinearInteractionLayer, SENET_Layer)
 from .attention import ScaledDotProductAttention, MultiHeadAttention, MultiHeadSelfAttention
-from .sequence import MaskedAveragePooling, MaskedSumPooling, KMaxPooling
+from .sequence import MaskedAveragePooling, MaskedSumPooling, KMaxPooling, GRU4RecEncoder
 
 __all__ = ["Dice", "get_activation", "EmbeddingLayer", "MLP", "LR_Layer", "InnerProductLayer", "FM_Layer",
            "CrossInteractionLayer", "CrossNet", "CompressedInteractionNet", "MaskBlock", "GeneralizedInteractionNet",
            "GeneralizedInteraction", "BilinearInteractionLayer", "SENET_Layer", "ScaledDotProductAttention",
-           "MultiHeadAttention", "MultiHeadSelfAttention", "MaskedAveragePooling", "MaskedSumPooling", "KMaxPooling"]
+           "MultiHeadAttention", "MultiHeadSelfAttention", "MaskedAveragePooling", "MaskedSumPooling", "KMaxPooling",
+           "GRU4RecEncoder"]
