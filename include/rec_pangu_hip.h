@@ -1190,6 +1190,48 @@ int rp_narm_attn_bwd(const float *q1, const float *q2, const float *v, const int
                      const float *dout, int64_t B, int64_t L, int H, float *dq1, float *dq2, float *dG, float *dht, float *dv,
                      void *workspace, size_t workspace_bytes, rp_stream_t stream);
 
+/* ---- sequence recall: the multi-interest encoder of MIND and ComirecDR (csrc/capsule.hip) ------------------------------------
+ * replaces CapsuleNetwork of rec_pangu/models/layers/multi_interest.py:56-161 with its autograd and the readout loop of
+ * rec_pangu/models/sequence/mind.py:44-49 / comirec.py:100-105.  Only rp_capsule_project_bwd_w takes a workspace.
+ *
+ * Projection (bilinear_type 2):  U[b, s, n] = sum_d W[s, n, d] X[b, s, d],  X [B, L, D], W [L, N, D] (N = K D), U [B, L, N];
+ * one launch for all L positions on the exact-fp32 matrix core; the [B, L, N, D] product is never formed.
+ *   rp_capsule_project_bwd_x WRITES dX[b, s, :] = dU[b, s, :] W[s];
+ *   rp_capsule_project_bwd_w WRITES dW[s] = sum_b dU[b, s, :]^T X[b, s, :]: one workgroup per (position, 32 output rows, batch
+ *   split) walks its rows front to back; with S > 1 splits a second launch adds the S partial sums in split order: a fixed
+ *   order, no float atomics.  S = min(32, max(1, ceil(B / 512))) splits of R = 64 ceil(ceil(B / S) / 64) rows (so ceil(B / R)
+ *   of them); workspace: rp_capsule_workspace_bytes(B, L, N, D) = 4 ceil(B / R) L N D bytes, 0 when one split covers the batch.
+ * 1 <= D <= 128, 1 <= N <= 2048, 1 <= L <= 65535, RP_ERR_ARG otherwise (nothing is launched).
+ *
+ * Routing: per (b, k), Uk = U[b sb + k sk + l sl + d] (strides in floats; sk = 0: all K interests read the same [L, D] rows),
+ * mask float [B, L] (non-zero = valid), b0 [B, K, L] initial logits or NULL for zeros, eps = 1e-9:
+ *   for i = 0, 1, 2:  p = softmax_l(b_i) over ALL L positions;  c = p where mask != 0, else 0 (not renormalised);
+ *                     s = c^T Uk;  n = |s|^2;  v = s n / (1 + n) / sqrt(n + eps);  if i < 2: b_{i+1} = b_i + Uk v
+ *   out[b, k, :] = v of round 2.       A fully masked row gives exact zeros.
+ * rp_capsule_route_bwd recomputes the rounds and WRITES dU with U's strides (sk = 0: the K contributions added in interest
+ * order); stop_grad != 0: rounds 0 and 1 give U no gradient.  b0 takes no gradient.  Every result is bit-identical between runs.
+ * Limits (rp_capsule_geometry): 1 <= K <= max_k (8), 1 <= L <= max_l (64), 1 <= D <= max_d (128) and
+ * 4 max(K, 2) L (D + 1) <= lds_bytes (147456), RP_ERR_ARG otherwise (nothing is launched).  proj_tb / proj_tn: batch rows /
+ * output columns per workgroup of the projection's forward.
+ *
+ * Readout: kidx[b] = argmax_k interests[b, k, :] . E[target[b], :] (the first maximum wins), best[b, :] = interests[b, kidx[b], :];
+ * a target outside [0, V) sets *err_flag and reads row 0.  rp_interest_pick_bwd WRITES dout [B, K, D]: dbest[b] at kidx[b],
+ * exact zeros elsewhere (no gradient through the scores). */
+int rp_capsule_geometry(int *proj_tb, int *proj_tn, int *max_k, int *max_l, int *max_d, int *lds_bytes);
+int rp_capsule_project_fwd(const float *X, const float *W, int64_t B, int64_t L, int N, int D, float *U, rp_stream_t stream);
+int rp_capsule_project_bwd_x(const float *dU, const float *W, int64_t B, int64_t L, int N, int D, float *dX,
+                             rp_stream_t stream);
+int rp_capsule_workspace_bytes(int64_t B, int64_t L, int N, int D, size_t *bytes);
+int rp_capsule_project_bwd_w(const float *dU, const float *X, int64_t B, int64_t L, int N, int D, float *dW, void *workspace,
+                             size_t workspace_bytes, rp_stream_t stream);
+int rp_capsule_route_fwd(const float *U, int64_t sb, int64_t sk, int64_t sl, const float *mask, const float *b0, int64_t B,
+                         int K, int L, int D, float *out, rp_stream_t stream);
+int rp_capsule_route_bwd(const float *U, int64_t sb, int64_t sk, int64_t sl, const float *mask, const float *b0,
+                         const float *dout, int64_t B, int K, int L, int D, int stop_grad, float *dU, rp_stream_t stream);
+int rp_interest_pick_fwd(const float *interests, const float *E, int64_t V, const int64_t *target, int64_t B, int K, int D,
+                         float *best, int32_t *kidx, int32_t *err_flag, rp_stream_t stream);
+int rp_interest_pick_bwd(const float *dbest, const int32_t *kidx, int64_t B, int K, int D, float *dout, rp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2233,3 +2233,139 @@ def narm_attention(q1: torch.Tensor, q2: torch.Tensor, v: torch.Tensor, ids: tor
         alpha = torch.matmul(mask * torch.sigmoid(q1 + q2.unsqueeze(1).expand_as(q1)), v.view(-1, 1))
         return torch.cat([torch.sum(alpha.expand_as(gru_out) * gru_out, 1), ht], 1)
     return _NarmAttention.apply(q1, q2, v.view(-1), ids.contiguous(), gru_out, ht)
+
+
+# ----------------------------------------------------------------------------------------------
+# sequence recall: the multi-interest encoder of MIND / ComirecDR (models/layers/multi_interest.py:96-161 of the reference) and
+# the hard readout (models/sequence/mind.py:44-49).  Saved between forward and backward: the projected rows, the mask and the
+# initial logits of the routing, one int32 per row of the readout.  No [B, L, K D, D] tensor exists on the HIP path.
+# ----------------------------------------------------------------------------------------------
+class _CapsuleProject(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, w):
+        x = x.contiguous()
+        w3 = w.reshape(w.shape[-3], w.shape[-2], w.shape[-1]).contiguous()
+        ctx.save_for_backward(x, w3)
+        ctx.w_shape = w.shape
+        return hip.capsule_project_fwd(x, w3)
+
+    @staticmethod
+    def backward(ctx, du):
+        x, w3 = ctx.saved_tensors
+        dx, dw = hip.capsule_project_bwd(du.contiguous(), x, w3, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+        return dx, None if dw is None else dw.view(ctx.w_shape)
+
+
+def capsule_project(x: torch.Tensor, w: torch.Tensor):
+    """ComirecDR's per-position projection (reference multi_interest.py:103-105): sum(w[:, :L] * x.unsqueeze(2), dim=3) with
+    x [B, L, D] and w [1, L, K D, D] (or [L, K D, D]) -> [B, L, K D].  On the HIP device one launch each for the forward, dX and
+    dW on the exact-fp32 matrix core and no [B, L, K D, D] product; on CPU tensors the reference's formula."""
+    L = x.shape[1]
+    w4 = w if w.dim() == 4 else w.unsqueeze(0)
+    if not x.is_cuda:
+        return torch.sum(w4[:, :L, :, :] * torch.unsqueeze(x, dim=2), dim=3)
+    N, D = w4.shape[2], w4.shape[3]
+    if x.dtype != torch.float32 or w.dtype != torch.float32 or not hip.capsule_project_fits(L, N, D):
+        hip.note_torch_path(f"capsule_project at K D={N}, D={D}, {x.dtype} (the kernels take fp32, D <= 128, K D <= 2048)")
+        return torch.einsum("lnd,bld->bln", w4[0, :L], x)
+    return _CapsuleProject.apply(x, w4[:, :L])
+
+
+class _CapsuleRoute(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u_hat, mask, b0, K: int, shared: bool, stop_grad: bool):
+        u_hat = u_hat.contiguous()
+        ctx.save_for_backward(u_hat, mask, b0)  # the inputs themselves: the backward recomputes the three rounds
+        ctx.cfg = (K, shared, stop_grad)
+        return hip.capsule_route_fwd(u_hat, mask, b0, K, shared)
+
+    @staticmethod
+    def backward(ctx, dout):
+        u_hat, mask, b0 = ctx.saved_tensors
+        K, shared, stop_grad = ctx.cfg
+        return hip.capsule_route_bwd(u_hat, mask, b0, dout.contiguous(), K, shared, stop_grad), None, None, None, None, None
+
+
+def _capsule_route_torch(u_hat, mask, K: int, b0, shared: bool, stop_grad: bool, rounds: int = 3):
+    """the reference's formulation, op for op (multi_interest.py:99, 107-156)"""
+    B, L, W = u_hat.shape
+    D = W if shared else W // K
+    item_eb_hat = u_hat.repeat(1, 1, K) if shared else u_hat
+    item_eb_hat = torch.reshape(item_eb_hat, (-1, L, K, D))
+    item_eb_hat = torch.transpose(item_eb_hat, 1, 2).contiguous()
+    item_eb_hat_iter = item_eb_hat.detach() if stop_grad else item_eb_hat
+    capsule_weight = torch.zeros(B, K, L, device=u_hat.device, dtype=u_hat.dtype) if b0 is None else b0
+    interest_capsule = None
+    for i in range(rounds):
+        atten_mask = torch.unsqueeze(mask, 1).repeat(1, K, 1)
+        paddings = torch.zeros_like(atten_mask, dtype=u_hat.dtype)
+        c = torch.nn.functional.softmax(capsule_weight, dim=-1)
+        c = torch.unsqueeze(torch.where(torch.eq(atten_mask, 0), paddings, c), 2)
+        src = item_eb_hat_iter if i < 2 else item_eb_hat
+        interest_capsule = torch.matmul(c, src)
+        cap_norm = torch.sum(torch.square(interest_capsule), -1, True)
+        interest_capsule = cap_norm / (1 + cap_norm) / torch.sqrt(cap_norm + 1e-9) * interest_capsule
+        if i < 2:
+            delta = torch.matmul(src, torch.transpose(interest_capsule, 2, 3).contiguous())
+            capsule_weight = capsule_weight + torch.reshape(delta, (-1, K, L))
+    return torch.reshape(interest_capsule, (-1, K, D))
+
+
+def capsule_route(u_hat: torch.Tensor, mask: torch.Tensor, K: int, b0: torch.Tensor = None, shared: bool = False,
+                  stop_grad: bool = False, rounds: int = 3):
+    """Three rounds of dynamic routing (reference multi_interest.py:125-154) -> the interest capsules [B, K, D].
+    u_hat: the projected history rows, [B, L, K D] (interest k reads the columns [k D, k D + D)) or, shared, [B, L, D] read by
+    all K interests (MIND: the reference's .repeat(1, 1, K) is a stride here).  mask [B, L] (0 = padding, any dtype);
+    b0 [B, K, L]: the initial routing logits, None for zeros; it takes no gradient.  The softmax runs over all L positions and
+    the masked weights are not renormalised; a fully masked row gives zeros.  stop_grad: rounds 0 and 1 read a detached
+    u_hat.  rounds: the reference's routing_times; the logits stop changing after round 1, so every count from 3 up gives
+    round 2's capsules.  On the HIP device one launch each way (the backward recomputes the rounds); outside
+    rp_capsule_geometry's limits, or with fewer than 3 rounds, the composed torch formulas on the device, counted; on CPU
+    tensors the reference's formulas."""
+    if rounds < 1:
+        raise ValueError("capsule_route: at least one routing round")
+    if b0 is not None:
+        b0 = b0.detach().to(u_hat.device)
+    if not u_hat.is_cuda:
+        return _capsule_route_torch(u_hat, mask, K, b0, shared, stop_grad, rounds)
+    B, L, W = u_hat.shape
+    D = W if shared else W // K
+    if u_hat.dtype != torch.float32 or rounds < 3 or not hip.capsule_route_fits(K, L, D):
+        g = hip.capsule_geometry()
+        hip.note_torch_path(f"capsule_route at K={K}, L={L}, D={D}, {rounds} rounds, {u_hat.dtype} (the kernel takes fp32, "
+                            f"3 rounds, K <= {g['max_k']}, L <= {g['max_l']}, D <= {g['max_d']} and 4 max(K, 2) L (D + 1) <= "
+                            f"{g['lds_bytes']} bytes)")
+        return _capsule_route_torch(u_hat, mask, K, b0, shared, stop_grad, rounds)
+    b0 = None if b0 is None else b0.float().contiguous()
+    return _CapsuleRoute.apply(u_hat, mask.float().contiguous(), b0, K, shared, stop_grad)
+
+
+class _InterestPick(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, interests, item_weight, target):
+        best, kidx = hip.interest_pick_fwd(interests.contiguous(), item_weight.contiguous(), target, _seq_flag(interests.device))
+        ctx.save_for_backward(kidx)
+        ctx.K = interests.shape[1]
+        return best
+
+    @staticmethod
+    def backward(ctx, dbest):
+        (kidx,) = ctx.saved_tensors
+        return hip.interest_pick_bwd(dbest.contiguous(), kidx, ctx.K), None, None
+
+
+def interest_pick(interests: torch.Tensor, item_weight: torch.Tensor, target: torch.Tensor, check_indices: str = "sync"):
+    """The hard readout of the multi-interest models (reference mind.py:44-49): per row the interest that scores highest
+    against the target's item row, interests [B, K, D], item_weight [V, D], target int64 [B] -> [B, D].  The first maximum
+    wins, as torch.argmax; no gradient flows through the scores.  On the HIP device one launch each way instead of the
+    reference's Python loop over the batch; check_indices as in full_softmax_ce."""
+    if not interests.is_cuda or interests.dtype != torch.float32 or item_weight.dtype != torch.float32:
+        if interests.is_cuda:
+            hip.note_torch_path(f"interest_pick over {interests.dtype} / {item_weight.dtype} (the kernels take fp32)")
+        item_e = torch.nn.functional.embedding(target, item_weight, padding_idx=0)
+        k_index = torch.argmax(torch.bmm(interests, item_e.unsqueeze(-1)), dim=1)
+        return interests.gather(1, k_index.view(-1, 1, 1).expand(-1, 1, interests.shape[2])).squeeze(1)
+    best = _InterestPick.apply(interests, item_weight, target.contiguous())
+    if check_indices == "sync":
+        _raise_if_flagged(interests.device, f"Target out of bounds: every target must lie in [0, {item_weight.shape[0]})")
+    return best

@@ -3074,3 +3074,125 @@ def narm_attn_bwd(q1, q2, v, ids, g, alpha, dout):
                                       alpha.data_ptr(), dout.data_ptr(), B, L, H, dq1.data_ptr(), dq2.data_ptr(), dg.data_ptr(),
                                       dht.data_ptr(), dv.data_ptr(), ws.data_ptr(), nbytes, _stream()), "rp_narm_attn_bwd")
     return dq1, dq2, dv, dg, dht
+
+
+# ---- sequence recall: the multi-interest encoder of MIND / ComirecDR and the hard readout (csrc/capsule.hip) -------------
+def capsule_geometry() -> dict:
+    """{"proj_tb", "proj_tn": batch rows / output columns per workgroup of the projection's forward; "max_k", "max_l",
+    "max_d", "lds_bytes": the routing launch takes K <= max_k, L <= max_l, D <= max_d with 4 max(K, 2) L (D + 1) <= lds_bytes}"""
+    v = [_i32(0) for _ in range(6)]
+    _check(lib().rp_capsule_geometry(*[C.byref(x) for x in v]), "rp_capsule_geometry")
+    return dict(zip(("proj_tb", "proj_tn", "max_k", "max_l", "max_d", "lds_bytes"), (x.value for x in v)))
+
+
+def capsule_project_fits(L: int, N: int, D: int) -> bool:
+    return 1 <= D <= 128 and 1 <= N <= 2048 and 1 <= L <= 65535
+
+
+def capsule_workspace_bytes(B: int, L: int, N: int, D: int) -> int:
+    n = _sz(0)
+    _check(lib().rp_capsule_workspace_bytes(B, L, N, D, C.byref(n)), "rp_capsule_workspace_bytes")
+    return n.value
+
+
+def capsule_route_fits(K: int, L: int, D: int) -> bool:
+    g = capsule_geometry()
+    return 1 <= K <= g["max_k"] and 1 <= L <= g["max_l"] and 1 <= D <= g["max_d"] and \
+        4 * max(K, 2) * L * (D + 1) <= g["lds_bytes"]
+
+
+def _capsule_dense(named):
+    for name, t, shape in named:
+        _req(t, torch.float32, name)
+        if tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise RuntimeError(f"capsule: {name} must be a contiguous {tuple(shape)} tensor, got {tuple(t.shape)}/{t.stride()}")
+
+
+def capsule_project_fwd(x, w):
+    """rp_capsule_project_fwd: x [B, L, D], w [L, N, D] -> U [B, L, N]"""
+    B, L, D = x.shape
+    N = w.shape[1]
+    _capsule_dense([("x", x, (B, L, D)), ("w", w, (L, N, D))])
+    u = _new((B, L, N), torch.float32, x.device)
+    with _Timed("capsule_project_fwd", f"{B}x{L}x{N}x{D}", 4 * (B * L * (D + N) + L * N * D), 2 * B * L * N * D):
+        _check(lib().rp_capsule_project_fwd(x.data_ptr(), w.data_ptr(), B, L, N, D, u.data_ptr(), _stream()),
+               "rp_capsule_project_fwd")
+    return u
+
+
+def capsule_project_bwd(du, x, w, want_dx: bool, want_dw: bool):
+    """rp_capsule_project_bwd_x / _bwd_w -> (dX [B, L, D] or None, dW [L, N, D] or None)"""
+    B, L, D = x.shape
+    N = w.shape[1]
+    _capsule_dense([("dU", du, (B, L, N)), ("x", x, (B, L, D)), ("w", w, (L, N, D))])
+    dx = dw = None
+    if want_dx:
+        dx = _new((B, L, D), torch.float32, x.device)
+        with _Timed("capsule_project_bwd_x", f"{B}x{L}x{N}x{D}", 4 * (B * L * (D + N) + L * N * D), 2 * B * L * N * D):
+            _check(lib().rp_capsule_project_bwd_x(du.data_ptr(), w.data_ptr(), B, L, N, D, dx.data_ptr(), _stream()),
+                   "rp_capsule_project_bwd_x")
+    if want_dw:
+        dw = _new((L, N, D), torch.float32, x.device)
+        ws, nbytes = _workspace("capsule", B, L, N, D, device=x.device)
+        with _Timed("capsule_project_bwd_w", f"{B}x{L}x{N}x{D}", 4 * (B * L * (D + N) + L * N * D), 2 * B * L * N * D):
+            _check(lib().rp_capsule_project_bwd_w(du.data_ptr(), x.data_ptr(), B, L, N, D, dw.data_ptr(),
+                                                  ws.data_ptr() if nbytes else None, nbytes, _stream()),
+                   "rp_capsule_project_bwd_w")
+    return dx, dw
+
+
+def _capsule_route_args(u_hat, mask, b0, K: int, shared: bool):
+    """u_hat [B, L, D] (shared) or [B, L, K D] -> (B, L, D, batch / interest / position strides in floats)"""
+    B, L, W = u_hat.shape
+    D = W if shared else W // K
+    if not shared and D * K != W:
+        raise RuntimeError(f"capsule_route: the rows of u_hat ({W} wide) do not split into {K} interests")
+    _capsule_dense([("u_hat", u_hat, (B, L, W)), ("mask", mask, (B, L))] + ([("b0", b0, (B, K, L))] if b0 is not None else []))
+    return B, L, D, L * W, 0 if shared else D, W
+
+
+def capsule_route_fwd(u_hat, mask, b0, K: int, shared: bool):
+    """rp_capsule_route_fwd -> out [B, K, D]"""
+    B, L, D, sb, sk, sl = _capsule_route_args(u_hat, mask, b0, K, shared)
+    out = _new((B, K, D), torch.float32, u_hat.device)
+    with _Timed("capsule_route_fwd", f"{B}x{K}x{L}x{D}", 4 * B * (u_hat.shape[2] * L + K * D)):
+        _check(lib().rp_capsule_route_fwd(u_hat.data_ptr(), sb, sk, sl, mask.data_ptr(), _ptr(b0), B, K, L, D, out.data_ptr(),
+                                          _stream()), "rp_capsule_route_fwd")
+    return out
+
+
+def capsule_route_bwd(u_hat, mask, b0, dout, K: int, shared: bool, stop_grad: bool):
+    """rp_capsule_route_bwd -> dU with u_hat's shape"""
+    B, L, D, sb, sk, sl = _capsule_route_args(u_hat, mask, b0, K, shared)
+    _capsule_dense([("dout", dout, (B, K, D))])
+    du = _new_like(u_hat)
+    with _Timed("capsule_route_bwd", f"{B}x{K}x{L}x{D}", 4 * B * (2 * u_hat.shape[2] * L + K * D)):
+        _check(lib().rp_capsule_route_bwd(u_hat.data_ptr(), sb, sk, sl, mask.data_ptr(), _ptr(b0), dout.data_ptr(), B, K, L, D,
+                                          int(stop_grad), du.data_ptr(), _stream()), "rp_capsule_route_bwd")
+    return du
+
+
+def interest_pick_fwd(interests, e, target, err_flag):
+    """rp_interest_pick_fwd: interests [B, K, D], e [V, D], target int64 [B] -> (best [B, D], kidx int32 [B])"""
+    B, K, D = interests.shape
+    _capsule_dense([("interests", interests, (B, K, D)), ("item_weight", e, (e.shape[0], D))])
+    _req(target, torch.int64, "target")
+    if tuple(target.shape) != (B,) or not target.is_contiguous():
+        raise RuntimeError(f"interest_pick: target must be a contiguous int64 [{B}] tensor")
+    best, kidx = _new((B, D), torch.float32, e.device), _new((B,), torch.int32, e.device)
+    with _Timed("interest_pick_fwd", f"{B}x{K}x{D}", 4 * B * D * (K + 2)):
+        _check(lib().rp_interest_pick_fwd(interests.data_ptr(), e.data_ptr(), e.shape[0], target.data_ptr(), B, K, D,
+                                          best.data_ptr(), kidx.data_ptr(), err_flag.data_ptr(), _stream()),
+               "rp_interest_pick_fwd")
+    return best, kidx
+
+
+def interest_pick_bwd(dbest, kidx, K: int):
+    """rp_interest_pick_bwd -> dout [B, K, D]: dbest[b] at kidx[b], zeros elsewhere"""
+    B, D = dbest.shape
+    _capsule_dense([("dbest", dbest, (B, D))])
+    dout = _new((B, K, D), torch.float32, dbest.device)
+    with _Timed("interest_pick_bwd", f"{B}x{K}x{D}", 4 * B * D * (K + 1)):
+        _check(lib().rp_interest_pick_bwd(dbest.data_ptr(), kidx.data_ptr(), B, K, D, dout.data_ptr(), _stream()),
+               "rp_interest_pick_bwd")
+    return dout

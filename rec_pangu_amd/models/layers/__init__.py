@@ -7,9 +7,10 @@ from .interaction import (InnerProductLayer, FM_Layer, CrossInteractionLayer, Cr
                           GeneralizedInteraction, BilinearInteractionLayer, SENET_Layer)
 from .attention import ScaledDotProductAttention, MultiHeadAttention, MultiHeadSelfAttention
 from .sequence import MaskedAveragePooling, MaskedSumPooling, KMaxPooling, GRU4RecEncoder
+from .multi_interest import CapsuleNetwork
 
 __all__ = ["Dice", "get_activation", "EmbeddingLayer", "MLP", "LR_Layer", "InnerProductLayer", "FM_Layer",
            "CrossInteractionLayer", "CrossNet", "CompressedInteractionNet", "MaskBlock", "GeneralizedInteractionNet",
            "GeneralizedInteraction", "BilinearInteractionLayer", "SENET_Layer", "ScaledDotProductAttention",
            "MultiHeadAttention", "MultiHeadSelfAttention", "MaskedAveragePooling", "MaskedSumPooling", "KMaxPooling",
-           "GRU4RecEncoder"]
+           "GRU4RecEncoder", "CapsuleNetwork"]
