@@ -1232,6 +1232,62 @@ int rp_interest_pick_fwd(const float *interests, const float *E, int64_t V, cons
                          float *best, int32_t *kidx, int32_t *err_flag, rp_stream_t stream);
 int rp_interest_pick_bwd(const float *dbest, const int32_t *kidx, int64_t B, int K, int D, float *dout, rp_stream_t stream);
 
+/* ---- sequence recall: SASRec's masked multi-head self-attention core (csrc/seq_attn.hip) --------------------------------------
+ * replaces, with its autograd, what rec_pangu/models/layers/trainformer.py:70-92 does between the three projections and
+ * `dense`.  Rows are already projected (biases added): q [., ldq] and kv [B L, ldkv] with K in columns [0, D) and V in
+ * [D, 2 D), D = heads dh, head h at columns [h dh, (h + 1) dh) of each.  A stacked [B L, 3 D] buffer is q = qkv, kv = qkv + D,
+ * ldq = ldkv = 3 D.  mask float [B, L], non-zero = content.  Per (b, head):
+ *   ctx[i, :] = sum_j keep[i, j] / (1 - p) softmax_j(q_i . k_j / sqrt(dh) + m[i, j]) v_j,   m[i, j] = 0 where mask[b, j] != 0
+ *   and j <= i, else -1e6f (added to the scaled fp32 score, as the reference adds its mask).  Keys j > i are skipped: a row
+ *   with a visible key has the softmax over all L keys exactly; a row without one gets the softmax over its j <= i masked
+ *   scores (finite; the reference's value there is quantised at the fp32 ulp of 1e6 and nothing should read it).
+ * Full mode (qpos NULL, q_compact 0): q [B L, ldq], ctx [B L, D] head-interleaved, lse [B, heads, L] (max + log of the sum),
+ *   the only thing kept for the backward; rp_seq_attn_bwd recomputes the probabilities from q, kv and lse, takes ctx and
+ *   dctx [B L, D] and WRITES dq [B L, lddq] and dkv [B L, lddkv] (dK | dV); one launch each way, no [B, heads, L, L] tensor,
+ *   no float atomics, bit-identical runs.
+ * Last-row mode (qpos int64 [B]): ONE query per sample, position qpos[b] (clamped to L - 1); ctx [B, D], lse [B, heads];
+ *   q_compact 0: the query is row b L + qpos[b] of q and the backward WRITES all L rows of the sample's dq (zeros but for
+ *   that row); q_compact 1: q and dq are [B, .] buffers, row b.  dkv is written for all positions.  qpos[b] < 0: a zero ctx
+ *   row, zero gradients, nothing of the sample is read.
+ * Dropout: p in [0, 1); keep[i, j] is a pure function of (seed, offset, b, head, i, j) on dropout.hip's Philox4x32-10 stream
+ *   (counter = ((b heads + head) L + i) * 32 + j / 4 and the offset, key = seed, draw j % 4, keep <=> draw >= p 2^32); one call
+ *   takes one offset; the backward regenerates the decisions from the same (seed, offset).  p = 0 draws nothing.  The _dev
+ *   forms read offset = *offset_dev + offset_delta on the device, as rp_dropout_fwd_dev.  rp_seq_attn_keep_mask WRITES the
+ *   same decisions as uint8 [B, heads, L, L] through the same device function (offset_dev may be NULL): for tests.
+ * Limits: 1 <= L <= 128, 1 <= dh <= 64, heads >= 1 (rp_seq_attn_fits: 1 inside, 0 outside; rp_seq_attn_geometry: max_l, max_dh,
+ *   row_tile = query rows per wave, min_dh_tile = the smallest head-width tile: dh is rounded up to min_dh_tile 2^k);
+ *   RP_ERR_ARG outside (nothing is launched).
+ *
+ * rp_seq_act_fwd / _bwd: the two feed-forward activations the GEMM epilogue lacks, elementwise over [M, N]:
+ *   RP_SEQ_ACT_GELU x 0.5 (1 + erf(x / sqrt 2)), RP_SEQ_ACT_SWISH x sigmoid(x); the backward reads the saved INPUT x.
+ * rp_seq_take_fwd: out[b, :] = x[b L + qpos[b], :D] (qpos clamped to L - 1; zeros for qpos[b] < 0), x [B L, ldx] -> [B, D];
+ * rp_seq_take_bwd WRITES dx [B L, D]: dout[b] at that row, zeros elsewhere. */
+#define RP_SEQ_ACT_GELU 0
+#define RP_SEQ_ACT_SWISH 1
+int rp_seq_attn_fits(int L, int heads, int dh);
+int rp_seq_attn_geometry(int *max_l, int *max_dh, int *row_tile, int *min_dh_tile);
+int rp_seq_attn_fwd(const float *q, int64_t ldq, int q_compact, const float *kv, int64_t ldkv, const float *mask,
+                    const int64_t *qpos, int64_t B, int L, int heads, int dh, float p, uint64_t seed, uint64_t offset, float *ctx,
+                    float *lse, rp_stream_t stream);
+int rp_seq_attn_fwd_dev(const float *q, int64_t ldq, int q_compact, const float *kv, int64_t ldkv, const float *mask,
+                        const int64_t *qpos, int64_t B, int L, int heads, int dh, float p, uint64_t seed, uint64_t offset_delta,
+                        const uint64_t *offset_dev, float *ctx, float *lse, rp_stream_t stream);
+int rp_seq_attn_bwd(const float *q, int64_t ldq, int q_compact, const float *kv, int64_t ldkv, const float *mask,
+                    const int64_t *qpos, const float *ctx, const float *dctx, const float *lse, int64_t B, int L, int heads,
+                    int dh, float p, uint64_t seed, uint64_t offset, float *dq, int64_t lddq, float *dkv, int64_t lddkv,
+                    rp_stream_t stream);
+int rp_seq_attn_bwd_dev(const float *q, int64_t ldq, int q_compact, const float *kv, int64_t ldkv, const float *mask,
+                        const int64_t *qpos, const float *ctx, const float *dctx, const float *lse, int64_t B, int L, int heads,
+                        int dh, float p, uint64_t seed, uint64_t offset_delta, const uint64_t *offset_dev, float *dq, int64_t lddq,
+                        float *dkv, int64_t lddkv, rp_stream_t stream);
+int rp_seq_attn_keep_mask(int64_t B, int L, int heads, float p, uint64_t seed, uint64_t offset, const uint64_t *offset_dev,
+                          uint8_t *keep, rp_stream_t stream);
+int rp_seq_act_fwd(const float *x, int64_t ldx, float *y, int64_t ldy, int64_t M, int N, int act, rp_stream_t stream);
+int rp_seq_act_bwd(const float *dy, int64_t lddy, const float *x, int64_t ldx, float *dx, int64_t lddx, int64_t M, int N, int act,
+                   rp_stream_t stream);
+int rp_seq_take_fwd(const float *x, int64_t ldx, const int64_t *qpos, int64_t B, int L, int D, float *out, rp_stream_t stream);
+int rp_seq_take_bwd(const float *dout, const int64_t *qpos, int64_t B, int L, int D, float *dx, rp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2369,3 +2369,159 @@ def interest_pick(interests: torch.Tensor, item_weight: torch.Tensor, target: to
     if check_indices == "sync":
         _raise_if_flagged(interests.device, f"Target out of bounds: every target must lie in [0, {item_weight.shape[0]})")
     return best
+
+
+# ----------------------------------------------------------------------------------------------
+# sequence recall: SASRec's masked multi-head self-attention core (models/layers/trainformer.py:70-92 of the reference) and
+# the feed-forward activations the GEMM epilogue lacks (trainformer.py:133-145).  Saved between forward and backward: the
+# projected rows, the mask, the output and one float per (b, head, query); no [B, heads, L, L] tensor exists on the HIP path.
+# ----------------------------------------------------------------------------------------------
+def seq_attention_reference(q, kv, mask, heads: int, keep=None, scale: float = 1.0, qpos=None, compact: bool = False):
+    """The composed formulation, op for op as the reference's MultiHeadAttention.forward between its projections and `dense`,
+    in the dtype of its inputs: q [B L, D] (or, with qpos and compact, [B, D]: one row per
+    sample), kv [B L, 2 D] (K | V), mask [B, L] -> ctx [B L, D], or [B, D] with qpos (a zero row where qpos[b] < 0).
+    keep: the dropout decisions [B, heads, L, L] (any dtype; None: no dropout), scale: 1 / (1 - p)."""
+    B, L = mask.shape
+    D = kv.shape[1] // 2
+    dh = D // heads
+    content = (mask != 0).to(q.dtype)
+    causal = torch.tril(torch.ones(L, L, dtype=q.dtype, device=q.device))
+    add = (1.0 - content.view(B, 1, 1, L) * causal.view(1, 1, L, L)) * -1e6  # get_attention_mask: [B, 1, L, L]
+    key_layer = kv[:, :D].reshape(B, L, heads, dh).permute(0, 2, 3, 1)
+    value_layer = kv[:, D:].reshape(B, L, heads, dh).permute(0, 2, 1, 3)
+    if qpos is None:
+        query_layer = q.reshape(B, L, heads, dh).permute(0, 2, 1, 3)
+    else:
+        rows = torch.arange(B, device=q.device)
+        idx = qpos.clamp(0, L - 1)
+        q_rows = q if compact else q.reshape(B, L, -1)[rows, idx]
+        query_layer = q_rows[:, :D].reshape(B, 1, heads, dh).permute(0, 2, 1, 3)
+        add = add[rows, 0, idx].view(B, 1, 1, L)
+        if keep is not None:
+            keep = keep[rows, :, idx].view(B, heads, 1, L)
+    attention_scores = torch.matmul(query_layer, key_layer) / (dh ** 0.5) + add
+    attention_probs = torch.softmax(attention_scores, dim=-1)
+    if keep is not None:
+        attention_probs = attention_probs * keep.to(q.dtype) * scale
+    context_layer = torch.matmul(attention_probs, value_layer).permute(0, 2, 1, 3).contiguous()
+    if qpos is None:
+        return context_layer.view(B * L, D)
+    return context_layer.view(B, D) * (qpos >= 0).to(q.dtype).view(B, 1)
+
+
+class _SeqAttention(torch.autograd.Function):
+    """inputs: rows = the stacked [B L, 3 D] buffer (q is None) or the [B L, 2 D] K | V buffer (q [B, D]: one query per sample)"""
+
+    @staticmethod
+    def forward(ctx, rows, q, mask, qpos, heads: int, p: float):
+        rows = _unit_inner(rows)
+        stacked = q is None
+        D = rows.shape[1] // (3 if stacked else 2)
+        qv = rows if stacked else _unit_inner(q)
+        kv = rows[:, D:] if stacked else rows
+        rng = hip.seq_attn_seed_offset(rows.device) if p > 0.0 else None
+        out, lse = hip.seq_attn_fwd(qv, kv, mask, heads, p, rng, qpos, compact=not stacked)
+        ctx.save_for_backward(rows, None if stacked else qv, mask, qpos, out, lse)
+        ctx.cfg = (heads, p, rng, D)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        rows, q, mask, qpos, out, lse = ctx.saved_tensors
+        heads, p, rng, D = ctx.cfg
+        if q is None:  # dqkv [B L, 3 D]: dQ | dK | dV, written in place by the one launch
+            drows = hip._new((rows.shape[0], 3 * D), torch.float32, rows.device)
+            hip.seq_attn_bwd(rows, rows[:, D:], mask, out, dout.contiguous(), lse, heads, p, rng, qpos, dq=drows, dkv=drows[:, D:])
+            return drows, None, None, None, None, None
+        dq, dkv = hip.seq_attn_bwd(q, rows, mask, out, dout.contiguous(), lse, heads, p, rng, qpos, compact=True)
+        return dkv, dq, None, None, None, None
+
+
+def seq_attention(qkv: torch.Tensor, mask: torch.Tensor, heads: int, p: float = 0.0, training: bool = False,
+                  qpos: torch.Tensor = None, q: torch.Tensor = None):
+    """The masked multi-head attention core of the reference's TransformerEncoder on already-projected rows:
+    qkv [B L, 3 D] (Q | K | V, biases added, head h at columns [h dh, (h + 1) dh) of each), mask [B, L] (non-zero = content, any
+    dtype) -> ctx [B L, D], head-interleaved: softmax(Q K^T / sqrt(dh) + m) V per (b, head) with m = 0 where the key is content
+    and not behind the query, else -1e6, and dropout (p, when training) on the probabilities.
+    qpos int64 [B]: last-row mode, one query position per sample -> ctx [B, D]; qpos[b] < 0 gives a zero row and no gradient.
+    With q [B, D] (the query rows themselves, one per sample; needs qpos) qkv holds K | V only, [B L, 2 D].
+    On the HIP device one launch each way (rp_seq_attn_*: nothing of size L x L is stored, the backward recomputes the
+    probabilities and regenerates the dropout decisions from one offset of the device generator's Philox stream); outside
+    rp_seq_attn_fits (L <= 128, dh <= 64) the composed torch formulation on the device, counted; on CPU tensors the same
+    formulation."""
+    if q is not None and qpos is None:
+        raise ValueError("seq_attention: q (one query row per sample) needs qpos")
+    B, L = mask.shape
+    D = qkv.shape[1] // (3 if q is None else 2)
+    if D % heads:
+        raise ValueError(f"seq_attention: {D} columns do not split into {heads} heads")
+    p = float(p) if training else 0.0
+    fits = qkv.is_cuda and qkv.dtype == torch.float32 and (q is None or q.dtype == torch.float32) and \
+        hip.seq_attn_fits(L, heads, D // heads)
+    if not fits:
+        if qkv.is_cuda:
+            g = hip.seq_attn_geometry()
+            hip.note_torch_path(f"seq_attention at L={L}, dh={D // heads}, {qkv.dtype} (the kernel takes fp32, L <= {g['max_l']}, "
+                                f"dh <= {g['max_dh']})")
+        qr, kv = (qkv[:, :D], qkv[:, D:]) if q is None else (q, qkv)
+        keep = None
+        if p > 0.0:
+            keep = torch.nn.functional.dropout(torch.ones(B, heads, L, L, dtype=qkv.dtype, device=qkv.device), p, True)
+        return seq_attention_reference(qr, kv, mask, heads, keep=keep, scale=1.0, qpos=qpos, compact=q is not None)
+    if qpos is not None:
+        qpos = qpos.to(torch.int64).contiguous()
+    return _SeqAttention.apply(qkv, q, mask.to(torch.float32).contiguous(), qpos, heads, p)
+
+
+SEQ_ACTS = {"gelu": hip.SEQ_ACT_GELU, "swish": hip.SEQ_ACT_SWISH}
+
+
+class _SeqAct(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, act: int):
+        x = _unit_inner(x)
+        ctx.act = act
+        ctx.save_for_backward(x)
+        return hip.seq_act_fwd(x, act)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return hip.seq_act_bwd(_unit_inner(dy), x, ctx.act), None
+
+
+def seq_act(x: torch.Tensor, name: str):
+    """The two feed-forward activations of the reference's FeedForward the GEMM epilogue lacks: 'gelu' (erf form,
+    x 0.5 (1 + erf(x / sqrt 2))) and 'swish' (x sigmoid(x)); x [..., N].  On the HIP device one launch each way; on CPU
+    tensors the reference's formulas."""
+    if name not in SEQ_ACTS:
+        raise KeyError(name)
+    if not x.is_cuda or x.dtype != torch.float32:
+        if x.is_cuda:
+            hip.note_torch_path(f"seq_act over {x.dtype} (the kernels take fp32)")
+        return x * 0.5 * (1.0 + torch.erf(x / (2.0 ** 0.5))) if name == "gelu" else x * torch.sigmoid(x)
+    return _SeqAct.apply(x.reshape(-1, x.shape[-1]), SEQ_ACTS[name]).reshape(x.shape)
+
+
+class _SeqTake(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, qpos, B: int, L: int):
+        ctx.save_for_backward(qpos)
+        ctx.dims = (B, L)
+        return hip.seq_take_fwd(_unit_inner(x), qpos, B, L)
+
+    @staticmethod
+    def backward(ctx, dout):
+        (qpos,) = ctx.saved_tensors
+        return hip.seq_take_bwd(dout.contiguous(), qpos, *ctx.dims), None, None, None
+
+
+def seq_take(x: torch.Tensor, qpos: torch.Tensor):
+    """x [B, L, D], qpos int64 [B] -> x[b, qpos[b]] as [B, D]; on the HIP device a zero row (and no gradient) where
+    qpos[b] < 0, on CPU tensors the reference's gather (SequenceBaseModel.gather_indexes), which raises there."""
+    B, L, D = x.shape
+    if not x.is_cuda or x.dtype != torch.float32:
+        if x.is_cuda:
+            hip.note_torch_path(f"seq_take over {x.dtype} (the kernels take fp32)")
+        return x.gather(dim=1, index=qpos.view(-1, 1, 1).expand(-1, -1, D)).squeeze(1)
+    return _SeqTake.apply(x.reshape(B * L, D), qpos.to(torch.int64).contiguous(), B, L)

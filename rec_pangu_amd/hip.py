@@ -3196,3 +3196,150 @@ def interest_pick_bwd(dbest, kidx, K: int):
         _check(lib().rp_interest_pick_bwd(dbest.data_ptr(), kidx.data_ptr(), B, K, D, dout.data_ptr(), _stream()),
                "rp_interest_pick_bwd")
     return dout
+
+
+# ---- sequence recall: SASRec's masked multi-head self-attention core and the feed-forward activations (csrc/seq_attn.hip) --
+SEQ_ACT_GELU, SEQ_ACT_SWISH = _RP["RP_SEQ_ACT_GELU"], _RP["RP_SEQ_ACT_SWISH"]
+
+
+def seq_attn_geometry() -> dict:
+    """{"max_l", "max_dh": the fused path takes L <= max_l and dh <= max_dh; "row_tile": query rows per wave; "min_dh_tile":
+    dh is rounded up to min_dh_tile * 2^k registers per row}"""
+    v = [_i32(0) for _ in range(4)]
+    _check(lib().rp_seq_attn_geometry(*[C.byref(x) for x in v]), "rp_seq_attn_geometry")
+    return dict(zip(("max_l", "max_dh", "row_tile", "min_dh_tile"), (x.value for x in v)))
+
+
+def seq_attn_fits(L: int, heads: int, dh: int) -> bool:
+    return bool(lib().rp_seq_attn_fits(L, heads, dh))
+
+
+def seq_attn_seed_offset(device):
+    """(seed, offset, clock) of one attention-dropout call: one offset of the device generator's stream, as a dropout call"""
+    return _dropout_seed_offset(device)
+
+
+def _seq_attn_args(q, kv, mask, qpos, heads: int, compact: bool):
+    """q: [B L, >= D] rows (full mode, or last-row mode on the stacked buffer) or [B, >= D] (compact); kv [B L, >= 2 D]: K | V;
+    mask float [B, L]; qpos int64 [B] or None -> (B, L, D, dh)"""
+    B, L = mask.shape
+    _req(mask, torch.float32, "mask")
+    if not mask.is_contiguous():
+        raise RuntimeError("seq_attn: mask must be contiguous")
+    if kv.shape[1] % 2 or (kv.shape[1] // 2) % heads:
+        raise RuntimeError(f"seq_attn: K | V rows of {kv.shape[1]} columns do not split into 2 x {heads} heads")
+    D = kv.shape[1] // 2
+    _req(q, torch.float32, "q")
+    _req(kv, torch.float32, "kv")
+    _rows(kv, "kv", 2 * D, B * L)
+    if compact and qpos is None:
+        raise RuntimeError("seq_attn: query rows as [B, D] need qpos")
+    _rows(q, "q", D, B if compact else B * L)
+    if qpos is not None:
+        _req(qpos, torch.int64, "qpos")
+        if tuple(qpos.shape) != (B,) or not qpos.is_contiguous():
+            raise RuntimeError(f"seq_attn: qpos must be a contiguous int64 [{B}] tensor")
+    return B, L, D, D // heads
+
+
+def seq_attn_fwd(q, kv, mask, heads: int, p: float = 0.0, rng=None, qpos=None, compact: bool = False):
+    """rp_seq_attn_fwd(_dev) -> (ctx [B L, D] or, with qpos, [B, D]; lse [B, heads, L] or [B, heads]).  rng: (seed, offset,
+    clock) from seq_attn_seed_offset when p > 0; compact: q holds one row per sample, [B, D] (needs qpos)."""
+    B, L, D, dh = _seq_attn_args(q, kv, mask, qpos, heads, compact)
+    rows = B if qpos is not None else B * L
+    ctx = _new((rows, D), torch.float32, q.device)
+    lse = _new((B, heads) if qpos is not None else (B, heads, L), torch.float32, q.device)
+    seed, offset, clock = rng if (p > 0.0 and rng is not None) else (0, 0, None)
+    head = (q.data_ptr(), _rowmajor(q, "q"), int(compact), kv.data_ptr(), _rowmajor(kv, "kv"), mask.data_ptr(), _ptr(qpos), B, L,
+            heads, dh, p, seed, offset)
+    with _Timed("seq_attn_fwd", f"{B}x{heads}x{L}x{dh}", 4 * (B * L * 3 * D + rows * D), 4 * B * heads * L * L * dh):
+        if clock is not None:
+            _check(lib().rp_seq_attn_fwd_dev(*head, clock.data_ptr(), ctx.data_ptr(), lse.data_ptr(), _stream()),
+                   "rp_seq_attn_fwd_dev")
+        else:
+            _check(lib().rp_seq_attn_fwd(*head, ctx.data_ptr(), lse.data_ptr(), _stream()), "rp_seq_attn_fwd")
+    return ctx, lse
+
+
+def seq_attn_bwd(q, kv, mask, ctx, dctx, lse, heads: int, p: float = 0.0, rng=None, qpos=None, compact: bool = False, dq=None,
+                 dkv=None):
+    """rp_seq_attn_bwd(_dev) -> (dq with q's rows x D, dkv [B L, 2 D]); dq / dkv: row buffers to write into (the column
+    blocks of one [B L, 3 D] buffer, for instance)"""
+    B, L, D, dh = _seq_attn_args(q, kv, mask, qpos, heads, compact)
+    rows = B if qpos is not None else B * L
+    _rows(ctx, "ctx", D, rows)
+    _rows(dctx, "dctx", D, rows)
+    if not (ctx.is_contiguous() and dctx.is_contiguous() and lse.is_contiguous()):
+        raise RuntimeError("seq_attn_bwd: ctx, dctx and lse must be contiguous")
+    _req(ctx, torch.float32, "ctx")
+    _req(dctx, torch.float32, "dctx")
+    _req(lse, torch.float32, "lse")
+    if dq is None:
+        dq = _new((q.shape[0], D), torch.float32, q.device)
+    if dkv is None:
+        dkv = _new((B * L, 2 * D), torch.float32, q.device)
+    _rows(dq, "dq", D, q.shape[0])
+    _rows(dkv, "dkv", 2 * D, B * L)
+    seed, offset, clock = rng if (p > 0.0 and rng is not None) else (0, 0, None)
+    head = (q.data_ptr(), _rowmajor(q, "q"), int(compact), kv.data_ptr(), _rowmajor(kv, "kv"), mask.data_ptr(), _ptr(qpos),
+            ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), B, L, heads, dh, p, seed, offset)
+    tail = (dq.data_ptr(), _rowmajor(dq, "dq"), dkv.data_ptr(), _rowmajor(dkv, "dkv"), _stream())
+    with _Timed("seq_attn_bwd", f"{B}x{heads}x{L}x{dh}", 4 * (B * L * 6 * D + 2 * rows * D), 14 * B * heads * L * L * dh // 2):
+        if clock is not None:
+            _check(lib().rp_seq_attn_bwd_dev(*head, clock.data_ptr(), *tail), "rp_seq_attn_bwd_dev")
+        else:
+            _check(lib().rp_seq_attn_bwd(*head, *tail), "rp_seq_attn_bwd")
+    return dq, dkv
+
+
+def seq_attn_keep_mask(B: int, heads: int, L: int, p: float, seed: int, offset: int, device) -> torch.Tensor:
+    """the keep decisions of an attention-dropout call at (seed, offset): uint8 [B, heads, L, L] (rp_seq_attn_keep_mask)"""
+    keep = _new((B, heads, L, L), torch.uint8, device)
+    _check(lib().rp_seq_attn_keep_mask(B, L, heads, p, seed, offset, None, keep.data_ptr(), _stream()), "rp_seq_attn_keep_mask")
+    return keep
+
+
+def seq_act_fwd(x, act: int):
+    """rp_seq_act_fwd: erf-GELU / swish of a 2-D x"""
+    _req(x, torch.float32, "x")
+    M, N = x.shape
+    y = _new((M, N), torch.float32, x.device)
+    with _Timed("seq_act_fwd", f"{M}x{N}", 8 * M * N):
+        _check(lib().rp_seq_act_fwd(x.data_ptr(), _rowmajor(x, "x"), y.data_ptr(), N, M, N, act, _stream()), "rp_seq_act_fwd")
+    return y
+
+
+def seq_act_bwd(dy, x, act: int):
+    """rp_seq_act_bwd: dy * act'(x) from the saved input"""
+    _req(dy, torch.float32, "dy")
+    M, N = x.shape
+    dx = _new((M, N), torch.float32, x.device)
+    with _Timed("seq_act_bwd", f"{M}x{N}", 12 * M * N):
+        _check(lib().rp_seq_act_bwd(dy.data_ptr(), _rowmajor(dy, "dy"), x.data_ptr(), _rowmajor(x, "x"), dx.data_ptr(), N, M, N,
+                                    act, _stream()), "rp_seq_act_bwd")
+    return dx
+
+
+def seq_take_fwd(x, qpos, B: int, L: int):
+    """rp_seq_take_fwd: x [B L, D], qpos int64 [B] -> [B, D], row qpos[b] of each sample (zeros where qpos[b] < 0)"""
+    D = x.shape[1]
+    _rows(x, "x", D, B * L)
+    _req(x, torch.float32, "x")
+    _req(qpos, torch.int64, "qpos")
+    out = _new((B, D), torch.float32, x.device)
+    with _Timed("seq_take_fwd", f"{B}x{L}x{D}", 8 * B * D):
+        _check(lib().rp_seq_take_fwd(x.data_ptr(), _rowmajor(x, "x"), qpos.data_ptr(), B, L, D, out.data_ptr(), _stream()),
+               "rp_seq_take_fwd")
+    return out
+
+
+def seq_take_bwd(dout, qpos, B: int, L: int):
+    """rp_seq_take_bwd -> dx [B L, D]: dout[b] at row qpos[b], zeros elsewhere"""
+    D = dout.shape[1]
+    _req(dout, torch.float32, "dout")
+    if tuple(dout.shape) != (B, D) or not dout.is_contiguous():
+        raise RuntimeError(f"seq_take_bwd: dout must be a contiguous [{B}, {D}] tensor")
+    dx = _new((B * L, D), torch.float32, dout.device)
+    with _Timed("seq_take_bwd", f"{B}x{L}x{D}", 4 * B * D * (L + 1)):
+        _check(lib().rp_seq_take_bwd(dout.data_ptr(), qpos.data_ptr(), B, L, D, dx.data_ptr(), _stream()), "rp_seq_take_bwd")
+    return dx

@@ -8,9 +8,10 @@ from .interaction import (InnerProductLayer, FM_Layer, CrossInteractionLayer, Cr
 from .attention import ScaledDotProductAttention, MultiHeadAttention, MultiHeadSelfAttention
 from .sequence import MaskedAveragePooling, MaskedSumPooling, KMaxPooling, GRU4RecEncoder
 from .multi_interest import CapsuleNetwork
+from .transformer import FeedForward, TransformerLayer, TransformerEncoder
 
 __all__ = ["Dice", "get_activation", "EmbeddingLayer", "MLP", "LR_Layer", "InnerProductLayer", "FM_Layer",
            "CrossInteractionLayer", "CrossNet", "CompressedInteractionNet", "MaskBlock", "GeneralizedInteractionNet",
            "GeneralizedInteraction", "BilinearInteractionLayer", "SENET_Layer", "ScaledDotProductAttention",
            "MultiHeadAttention", "MultiHeadSelfAttention", "MaskedAveragePooling", "MaskedSumPooling", "KMaxPooling",
-           "GRU4RecEncoder", "CapsuleNetwork"]
+           "GRU4RecEncoder", "CapsuleNetwork", "FeedForward", "TransformerLayer", "TransformerEncoder"]

@@ -3,6 +3,7 @@ from .gru4rec import GRU4Rec
 from .narm import NARM
 from .mind import MIND  # noqa: F401
 from .comirec import ComirecDR  # noqa: F401
+from .sasrec import SASRec  # noqa: F401
 
-# (MIND and ComirecDR are importable from here; __all__ keeps the list tests/test_gru_host.py pins)
+# (MIND, ComirecDR and SASRec are importable from here; __all__ keeps the list tests/test_gru_host.py pins)
 __all__ = ["YotubeDNN", "GRU4Rec", "NARM"]
