@@ -268,12 +268,6 @@ __device__ __forceinline__ void adam_zero_grad_closed(T &p, T &m, T &s, const Cf
 // The launch covers the stamps [l_lo, t_end): l_lo = t_from for a full build, = (last build's t_end) - J for the per-step
 // rebuild (stamps older than that were final already); with t_dev (graph replays: consecutive steps) the window is
 // [*t_dev - J - 4, *t_dev) whatever the launch arguments say.
-__device__ __forceinline__ double wave_sum_f64(double x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o, 64);
-    return x;
-}
-
 __global__ __launch_bounds__(256) void lazy_cf_table_kernel(const double2 *__restrict__ nsd, int t_end, int t_from,
                                                             int l_lo, int J, double b1e, double r,
                                                             CfEntry *__restrict__ out, const int32_t *__restrict__ t_dev) {
@@ -303,8 +297,8 @@ __global__ __launch_bounds__(256) void lazy_cf_table_kernel(const double2 *__res
             swa += w[u] * a[u];
         }
     }
-    sw = wave_sum_f64(sw);
-    swa = wave_sum_f64(swa);
+    sw = rp_lane_sum(sw);
+    swa = rp_lane_sum(swa);
     const double abar = (sw != 0.0) ? swa / sw : 1.0;  // every lr_j = 0: no movement, any abar will do
     double n2 = 0.0, n3 = 0.0, n4 = 0.0;
 #pragma unroll
@@ -314,9 +308,9 @@ __global__ __launch_bounds__(256) void lazy_cf_table_kernel(const double2 *__res
         n3 += w[u] * da2 * da;
         n4 += w[u] * da2 * da2;
     }
-    n2 = wave_sum_f64(n2);
-    n3 = wave_sum_f64(n3);
-    n4 = wave_sum_f64(n4);
+    n2 = rp_lane_sum(n2);
+    n3 = rp_lane_sum(n3);
+    n4 = rp_lane_sum(n4);
     if (lane == 0) {  // (pm / ps of this slot belong to k = l: lazy_cf_pow_kernel)
         out[l].abar = (float)abar;
         out[l].n0 = (float)sw;

@@ -68,12 +68,6 @@ __device__ __forceinline__ void aw_store(float *p, const AwVec<V> &r) {
     }
 }
 
-__device__ __forceinline__ float aw_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;  // the same value on every lane
-}
-
 // P = softmax over s of (q_t . k_s) * inv_scale for one sample; q0 = the sample's first QKV row
 template <int T, int V>
 __device__ __forceinline__ void aw_probs(const float *__restrict__ q0, int64_t ldq, int a, float inv_scale, int lane,
@@ -101,7 +95,7 @@ __device__ __forceinline__ void aw_probs(const float *__restrict__ q0, int64_t l
         float m = -INFINITY, l = 0.f;
 #pragma unroll
         for (int s = 0; s < T; ++s) {
-            P[t][s] = aw_wave_sum(P[t][s]) * inv_scale;
+            P[t][s] = rp_lane_sum(P[t][s]) * inv_scale;
             m = fmaxf(m, P[t][s]);
         }
 #pragma unroll
@@ -226,7 +220,7 @@ __global__ __launch_bounds__(AW_BLOCK) void attn_wide_bwd_kernel(const float *__
             float dot = 0.f;
 #pragma unroll
             for (int s = 0; s < T; ++s) {
-                dP[t][s] = aw_wave_sum(dP[t][s]);
+                dP[t][s] = rp_lane_sum(dP[t][s]);
                 dot += P[t][s] * dP[t][s];
             }
 #pragma unroll

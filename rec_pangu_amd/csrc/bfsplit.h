@@ -7,7 +7,8 @@
 //     lo likewise: three 8-bit windows cover the whole 24-bit significand, so hi + mid + lo == x exactly and nothing is
 //     dropped that rounding would have kept, and a piece costs an AND, a subtraction and half a v_perm_b32 instead of two
 //     conversions, a shift and a subtraction (the conversion-based split was 41 % of the weight-gradient kernel's
-//     issue cycles, more than its 6-product MFMA work: profiles/microbench/wgrad_one.py).
+//     issue cycles, more than its 6-product MFMA work: profiles/microbench/wgrad_one.py);
+//   three pieces by round-to-nearest (bf_round3_8): what the CIN kernels (cin_bs.hip, cin_last.hip) were validated with.
 #pragma once
 #include "common.h"
 
@@ -60,6 +61,27 @@ __device__ __forceinline__ void bf_trunc3_8(f32x8 v, bf16x8 (&p)[3]) {
     }
 }
 
+// one value, by truncation: the scalar form of bf_trunc3_*
+__device__ __forceinline__ void bf_trunc3_1(float v, __bf16 *p0, __bf16 *p1, __bf16 *p2) {
+    uint32_t u = __float_as_uint(v);
+    *reinterpret_cast<uint16_t *>(p0) = (uint16_t)(u >> 16);
+    v -= __uint_as_float(u & 0xFFFF0000u);
+    u = __float_as_uint(v);
+    *reinterpret_cast<uint16_t *>(p1) = (uint16_t)(u >> 16);
+    v -= __uint_as_float(u & 0xFFFF0000u);
+    u = __float_as_uint(v);
+    *reinterpret_cast<uint16_t *>(p2) = (uint16_t)(u >> 16);
+}
+
+// three pieces by ROUND-TO-NEAREST conversions (the CIN kernels): other bits than bf_trunc3_8, not interchangeable with it
+__device__ __forceinline__ void bf_round3_8(f32x8 v, bf16x8 (&p)[3]) {
+    p[0] = __builtin_convertvector(v, bf16x8);
+    v -= __builtin_convertvector(p[0], f32x8);
+    p[1] = __builtin_convertvector(v, bf16x8);
+    v -= __builtin_convertvector(p[1], f32x8);
+    p[2] = __builtin_convertvector(v, bf16x8);
+}
+
 template <int NP>
 __device__ __forceinline__ void bf_split4(f32x4 v, bf16x4 (&p)[NP]) {
     if constexpr (NP == 3) {
@@ -70,10 +92,6 @@ __device__ __forceinline__ void bf_split4(f32x4 v, bf16x4 (&p)[NP]) {
     if (NP > 1) {
         v -= __builtin_convertvector(p[0], f32x4);
         p[1] = __builtin_convertvector(v, bf16x4);
-    }
-    if (NP > 2) {
-        v -= __builtin_convertvector(p[1], f32x4);
-        p[2] = __builtin_convertvector(v, bf16x4);
     }
 }
 
@@ -87,10 +105,6 @@ __device__ __forceinline__ void bf_split8(f32x8 v, bf16x8 (&p)[NP]) {
     if (NP > 1) {
         v -= __builtin_convertvector(p[0], f32x8);
         p[1] = __builtin_convertvector(v, bf16x8);
-    }
-    if (NP > 2) {
-        v -= __builtin_convertvector(p[1], f32x8);
-        p[2] = __builtin_convertvector(v, bf16x8);
     }
 }
 

@@ -177,13 +177,6 @@ __global__ __launch_bounds__(BIL_T) void bil_fwd_kernel(const float *__restrict_
 }
 
 template <int D>
-__device__ __forceinline__ float bil_group_sum(float v) {  // a fixed butterfly over the D lanes of one sample
-#pragma unroll
-    for (int m = 1; m < D; m <<= 1) v += __shfl_xor(v, m, D);
-    return v;
-}
-
-template <int D>
 __device__ __forceinline__ void bil_load_w(const float *__restrict__ w, float *__restrict__ dst) {
     for (int e = threadIdx.x; e < D * D; e += BIL_T) dst[(e / D) * (D + 4) + (e % D)] = w[e];
 }
@@ -246,7 +239,7 @@ __global__ __launch_bounds__(BIL_T) void bil_bwd_rows_kernel(const float *__rest
             }
             const float ej = Et[sb * FD + j * D + d];
             if (R > 0) {
-                const float ds = bil_group_sum<D>(gq * (u * ej));
+                const float ds = rp_lane_sum_up<D>(gq * (u * ej));
                 if (d == 0) dAs[sb * F + i] += ds * aj, dAs[sb * F + j] += ds * ai;
             }
             dEt[sb * FD + j * D + d] += gg * u;

@@ -36,20 +36,6 @@ constexpr int CAP_MAX_L = 64;
 constexpr int CAP_LDS = 144 * 1024;  // routing: bytes of LDS the sample's tiles may take
 constexpr float CAP_EPS = 1e-9f;
 
-__device__ __forceinline__ int cap_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-static inline int cap_pad(int n, int to) { return (n + to - 1) / to * to; }
-
-__device__ __forceinline__ float cap_wave_sum(float s) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
-    return s;
-}
-__device__ __forceinline__ float cap_wave_max(float s) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s = fmaxf(s, __shfl_xor(s, o));
-    return s;
-}
-
 // ---- (a) projection ------------------------------------------------------------------------------------------------------
 // grid (ceil(B / 64), ceil(N / 128), L), 256 threads; dynamic LDS: xs [64][Dp + 4], ws [128][Dp + 4], Dp = D rounded up to 8
 __global__ __launch_bounds__(256) void cap_project_fwd_kernel(const float *__restrict__ X, const float *__restrict__ W,
@@ -88,7 +74,7 @@ __global__ __launch_bounds__(256) void cap_project_fwd_kernel(const float *__res
     if (n >= N) return;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int64_t ba = b0 + cap_row(r, h), bb = ba + 32;
+        const int64_t ba = b0 + rp_mfma32_row(r, h), bb = ba + 32;
         if (ba < B) U[(ba * L + s) * N + n] = acc0[r];
         if (bb < B) U[(bb * L + s) * N + n] = acc1[r];
     }
@@ -130,7 +116,7 @@ __global__ __launch_bounds__(256) void cap_project_bwd_x_kernel(const float *__r
     if (!mine || j >= D) return;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int64_t b = b0 + cap_row(r, h);
+        const int64_t b = b0 + rp_mfma32_row(r, h);
         if (b < B) dX[(b * L + s) * D + j] = acc[r];
     }
 }
@@ -170,7 +156,7 @@ __global__ __launch_bounds__(256) void cap_project_bwd_w_kernel(const float *__r
     float *dst = part != nullptr ? part + (int64_t)blockIdx.z * L * N * D : dW;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int n = n0 + cap_row(r, h);
+        const int n = n0 + rp_mfma32_row(r, h);
         if (n < N) dst[(s * N + n) * D + j] = acc[r];
     }
 }
@@ -196,9 +182,9 @@ __device__ __forceinline__ void cap_rounds(const float *u, int ld, int L, int D,
     const int dlo = D < 64 ? D : 64;
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
-        const float mx = cap_wave_max(pos ? bl : -INFINITY);
+        const float mx = rp_lane_max(pos ? bl : -INFINITY);
         const float e = pos ? expf(bl - mx) : 0.f;
-        const float p = e / cap_wave_sum(e);
+        const float p = e / rp_lane_sum(e);
         const float c = m ? p : 0.f;
         float a0 = 0.f, a1 = 0.f;
         for (int l = 0; l < L; ++l) {
@@ -206,7 +192,7 @@ __device__ __forceinline__ void cap_rounds(const float *u, int ld, int L, int D,
             if (u0) a0 += cl * u[l * ld + lane];
             if (u1) a1 += cl * u[l * ld + lane + 64];
         }
-        const float n = cap_wave_sum(a0 * a0 + a1 * a1);
+        const float n = rp_lane_sum(a0 * a0 + a1 * a1);
         const float f = n / (1.f + n) / sqrtf(n + CAP_EPS);
         R.p[i] = p, R.c[i] = c, R.s0[i] = a0, R.s1[i] = a1, R.n[i] = n;
         R.v0[i] = f * a0, R.v1[i] = f * a1;
@@ -286,7 +272,7 @@ __global__ __launch_bounds__(512) void cap_route_bwd_kernel(const float *__restr
         // squash: v = f(n) s, n = |s|^2  ->  ds = f g + 2 f'(n) (g . s) s
         const float n = R.n[i], rs = sqrtf(n + CAP_EPS), f = n / (1.f + n) / rs;
         const float fp = 1.f / ((1.f + n) * (1.f + n) * rs) - n / (2.f * (1.f + n) * (n + CAP_EPS) * rs);
-        const float gs = cap_wave_sum(g0 * R.s0[i] + g1 * R.s1[i]);
+        const float gs = rp_lane_sum(g0 * R.s0[i] + g1 * R.s1[i]);
         ds0[i] = f * g0 + 2.f * fp * gs * R.s0[i];
         ds1[i] = f * g1 + 2.f * fp * gs * R.s1[i];
         if (i > 0) {  // dc[l] = U[l, :] . ds, then through the masked softmax into the logits of this round
@@ -294,7 +280,7 @@ __global__ __launch_bounds__(512) void cap_route_bwd_kernel(const float *__restr
             for (int d = 0; d < dlo; ++d) dc += u[lrow * ld + d] * __shfl(ds0[i], d);
             for (int d = 64; d < D; ++d) dc += u[lrow * ld + d] * __shfl(ds1[i], d - 64);
             dc = m ? dc : 0.f;
-            const float tot = cap_wave_sum(R.p[i] * dc);
+            const float tot = rp_lane_sum(R.p[i] * dc);
             db += R.p[i] * (dc - tot);
         }
     }
@@ -347,7 +333,7 @@ __global__ __launch_bounds__(256) void cap_pick_fwd_kernel(const float *__restri
     for (int k = 0; k < K; ++k) {
         float s = 0.f;
         for (int d = lane; d < D; d += 64) s += rows[k * D + d] * e[d];
-        s = cap_wave_sum(s);
+        s = rp_lane_sum(s);
         if (k == 0 || s > top) top = s, kb = k;  // (strict: the first maximum wins)
     }
     for (int d = lane; d < D; d += 64) best[b * D + d] = rows[kb * D + d];
@@ -402,7 +388,7 @@ extern "C" int rp_capsule_project_fwd(const float *X, const float *W, int64_t B,
     CAP_CHECK_PROJECT("capsule_project_fwd");
     RP_REQUIRE(X && W && U, "capsule_project_fwd: null pointer");
     if (B == 0) return RP_OK;
-    const int Dp = cap_pad(D, 8);
+    const int Dp = rp_round_up(D, 8);
     const size_t lds = sizeof(float) * (size_t)(CAP_TB + CAP_TN) * (Dp + 4);
     (void)hipFuncSetAttribute(reinterpret_cast<const void *>(cap_project_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                               (int)lds);
@@ -418,7 +404,7 @@ extern "C" int rp_capsule_project_bwd_x(const float *dU, const float *W, int64_t
     RP_REQUIRE(dU && W && dX, "capsule_project_bwd_x: null pointer");
     if (B == 0) return RP_OK;
     hipLaunchKernelGGL(cap_project_bwd_x_kernel, dim3((unsigned)rp_cdiv(B, CAP_TBX), (unsigned)L), dim3(256), 0,
-                       (hipStream_t)stream, dU, W, B, L, N, D, cap_pad(D, 32), dX);
+                       (hipStream_t)stream, dU, W, B, L, N, D, rp_round_up(D, 32), dX);
     RP_LAUNCH_CHECK("capsule_project_bwd_x");
     return RP_OK;
 }
@@ -444,7 +430,7 @@ extern "C" int rp_capsule_project_bwd_w(const float *dU, const float *X, int64_t
     float *part = splits > 1 ? static_cast<float *>(workspace) : nullptr;
     // (B == 0 still launches: dW is WRITTEN, zeros then)
     hipLaunchKernelGGL(cap_project_bwd_w_kernel, dim3((unsigned)rp_cdiv(N, 32), (unsigned)L, (unsigned)splits), dim3(256), 0,
-                       (hipStream_t)stream, dU, X, B, L, N, D, cap_pad(D, 32), rows, part, dW);
+                       (hipStream_t)stream, dU, X, B, L, N, D, rp_round_up(D, 32), rows, part, dW);
     RP_LAUNCH_CHECK("capsule_project_bwd_w");
     if (splits > 1) {
         hipLaunchKernelGGL(cap_project_bwd_w_finish_kernel, dim3((unsigned)rp_cdiv(total, 256)), dim3(256), 0, (hipStream_t)stream,

@@ -52,8 +52,6 @@ struct CcpmArgs {
     int fwd_slots, bwd_slots;
 };
 
-static inline int ccpm_up(int n, int m) { return (n + m - 1) / m * m; }
-
 // fills the geometry; false outside the supported range
 static bool ccpm_geom(int F, int D, int nl, const int *channels, const int *heights, const int *ks, CcpmArgs *a) {
     if (nl < 1 || nl > CCPM_MAXL || F < 1 || F > CCPM_MAXLEN || D < 1 || D > 65536 || !channels || !heights || !ks) return false;
@@ -95,7 +93,7 @@ static bool ccpm_geom(int F, int D, int nl, const int *channels, const int *heig
         a->g_off[l] = (l & 1) ? g0 + gmax - size : g0;
     }
     a->bwd_slots = g0 + gmax;
-    a->wpad = ccpm_up(np, 64);
+    a->wpad = rp_round_up(np, 64);
     return a->wpad + CCPM_T * a->fwd_slots <= CCPM_LDS_FLOATS && 2 * a->wpad + CCPM_T * a->bwd_slots <= CCPM_LDS_FLOATS;
 }
 
@@ -190,26 +188,20 @@ __global__ __launch_bounds__(CCPM_T) void ccpm_fwd_kernel(const float *__restric
     }
 }
 
-__device__ __forceinline__ float ccpm_wave_sum(float v) {  // a fixed butterfly: every lane ends with the same sum
-#pragma unroll
-    for (int m = 1; m < CCPM_T; m <<= 1) v += __shfl_xor(v, m, CCPM_T);
-    return v;
-}
-
 template <class In>
 __device__ __forceinline__ void ccpm_bwd_channel(const float *__restrict__ w, In in, int cin, int kh, int lin, int lout,
                                                  const float *__restrict__ line, float *__restrict__ accw,
                                                  float *__restrict__ accb, float *__restrict__ gin, bool first) {
     float s = 0.f;
     for (int p = 0; p < lout; ++p) s += line[p * CCPM_T];
-    s = ccpm_wave_sum(s);
+    s = rp_lane_sum_up<CCPM_T>(s);
     if (threadIdx.x == 0) *accb += s;
     for (int ci = 0; ci < cin; ++ci) {
         for (int j = 0; j < kh; ++j) {  // dW[ci, j]: positions p with 0 <= p + j - (kh - 1) < lin
             const int plo = kh - 1 - j, phi = lin + kh - 1 - j < lout ? lin + kh - 1 - j : lout;
             float sw = 0.f;
             for (int p = plo; p < phi; ++p) sw += line[p * CCPM_T] * in(ci, p + j - (kh - 1));
-            sw = ccpm_wave_sum(sw);
+            sw = rp_lane_sum_up<CCPM_T>(sw);
             if (threadIdx.x == 0) accw[ci * kh + j] += sw;
         }
         for (int q = 0; q < lin; ++q) {  // (q + kh - 1 - j always lies inside the line)

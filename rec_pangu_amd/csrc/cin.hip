@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256) void cin_layer_fwd_kernel(const float *__restr
                     float v0 = 0.f, v1 = 0.f;
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
-                        const int ro = ((r & 3) + 8 * (r >> 2)) * Dpp;
+                        const int ro = rp_mfma32_row(r, 0) * Dpp;
                         v0 += acc0[r] * x0c[ro];
                         v1 += acc1[r] * x0c[ro + 32];
                     }
@@ -232,7 +232,7 @@ __global__ __launch_bounds__(256) void cin_layer_fwd_kernel(const float *__restr
             const float *x0c = X0s + (s * 32 + 4 * half) * Dpp + d;
             float v = 0.f;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) v += acc[r] * x0c[((r & 3) + 8 * (r >> 2)) * Dpp];
+            for (int r = 0; r < 16; ++r) v += acc[r] * x0c[rp_mfma32_row(r, 0) * Dpp];
             v += __shfl_xor(v, 32, 64);
             v += bo;
             const bool keep = (half == 0) && (d < D);
@@ -314,7 +314,7 @@ __device__ __forceinline__ void cin_store_tile(const f32x16 &acc, float *__restr
     if (d >= D) return;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int row = (r & 3) + 8 * (r >> 2) + 4 * half;
+        const int row = rp_mfma32_row(r, half);
         if (row < rows_valid) {
             float *p = dst + (int64_t)row * D + d;
             *p = add ? (*p + acc[r]) : acc[r];
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256) void cin_layer_bwd_x_kernel(
                     float *dst = Red + ((wave * nitems + it) * 1024);
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        dst[((r & 3) + 8 * (r >> 2) + 4 * half) * 32 + li] = (pass == 0 ? a0[it][r] : ap[it][r]);
+                        dst[(rp_mfma32_row(r, half)) * 32 + li] = (pass == 0 ? a0[it][r] : ap[it][r]);
                 }
             __syncthreads();
             const int rows = (pass == 0) ? H : M;
@@ -614,7 +614,7 @@ __global__ __launch_bounds__(256) void cin_layer_bwd_w_kernel(const float *__res
         if (m < M) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int h = (r & 3) + 8 * (r >> 2) + 4 * half;
+                const int h = rp_mfma32_row(r, half);
                 if (h < H) dst[h * M + m] = acc[mt][r];
             }
         }

@@ -17,20 +17,10 @@
 // per workgroup.  FULL = all of them exist: straight-line channel loop (counted vmcnt, see gemm.hip); the tail of the
 // batch runs the guarded instantiation.
 #include "common.h"
-
-typedef __bf16 cbbf8 __attribute__((ext_vector_type(8)));
-typedef float cbf8 __attribute__((ext_vector_type(8)));
+#include "bfsplit.h"  // bf_round3_8: the round-to-nearest three-piece split of every operand here
 
 #define CB_OG 4      // channels per LDS buffer
 #define CB_LD 40     // bf16 per LDS row (32 data + 8 pad -> 80 B, conflict-free ds_read_b128)
-
-__device__ __forceinline__ void cb_split(cbf8 v, cbbf8 (&p)[3]) {
-    p[0] = __builtin_convertvector(v, cbbf8);
-    v -= __builtin_convertvector(p[0], cbf8);
-    p[1] = __builtin_convertvector(v, cbbf8);
-    v -= __builtin_convertvector(p[1], cbf8);
-    p[2] = __builtin_convertvector(v, cbbf8);
-}
 
 // xk   : contraction operand X_{k-1} rows, [B, ldk] with Mc rows of D floats per sample (Mc <= 32)
 // xe   : MODE 0: X_0 ([B, lde], Hr rows of D floats) for the epilogue;  MODE 1: unused
@@ -62,18 +52,18 @@ __global__ __launch_bounds__(256, 2) void cin_bs_kernel(const float *__restrict_
         if (!ok[ti]) bt[ti] = B - 1;  // clamp: loads stay in range, stores are suppressed
     }
     // B fragments: lane = column (b, d), k = 16*ks + 8*hh + e
-    cbbf8 bf[2][2][3];
+    bf16x8 bf[2][2][3];
 #pragma unroll
     for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            cbf8 v;
+            f32x8 v;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 const int m = ks * 16 + 8 * hh + e;
                 v[e] = (m < Mc) ? xk[bt[ti] * ldk + (int64_t)m * D + dt[ti]] : 0.f;
             }
-            cb_split(v, bf[ti][ks]);
+            bf_round3_8(v, bf[ti][ks]);
         }
     // epilogue operands in the C layout: row h = (r&3) + 8*(r>>2) + 4*hh
     float ep[2][16];
@@ -81,7 +71,7 @@ __global__ __launch_bounds__(256, 2) void cin_bs_kernel(const float *__restrict_
     for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int h = (r & 3) + 8 * (r >> 2) + 4 * hh;
+            const int h = rp_mfma32_row(r, hh);
             if (MODE == 0) ep[ti][r] = (h < Hr) ? xe[bt[ti] * lde + (int64_t)h * D + dt[ti]] : 0.f;
             else ep[ti][r] = 0.f;  // dX accumulator
         }
@@ -137,12 +127,12 @@ __global__ __launch_bounds__(256, 2) void cin_bs_kernel(const float *__restrict_
         for (int oo = 0; oo < CB_OG; ++oo) {
             const int o = grp * CB_OG + oo;
             if (!FULL && o >= O) break;
-            cbbf8 a[2][3];
+            bf16x8 a[2][3];
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
                 for (int q = 0; q < 3; ++q)
-                    a[ks][q] = *reinterpret_cast<const cbbf8 *>(&Wl[buf][oo][q][i][ks * 16 + 8 * hh]);
+                    a[ks][q] = *reinterpret_cast<const bf16x8 *>(&Wl[buf][oo][q][i][ks * 16 + 8 * hh]);
             float ysum = 0.f;
 #pragma unroll
             for (int ti = 0; ti < 2; ++ti) {
@@ -186,8 +176,7 @@ __global__ __launch_bounds__(256, 2) void cin_bs_kernel(const float *__restrict_
             }
             if (MODE == 0 && pooled != nullptr && tps == 2) {
                 float s = (hh == 0) ? ysum : 0.f;
-#pragma unroll
-                for (int sh = 32; sh > 0; sh >>= 1) s += __shfl_xor(s, sh, 64);  // every lane: the total
+                s = rp_lane_sum(s);  // every lane: the total
                 if (FULL || (l == 0 && ok[0])) pooled[bt[0] * O + o] = s;
             }
             // keep the scheduler from interleaving the four channels of a group: it buys nothing (the matrix core is
@@ -200,7 +189,7 @@ __global__ __launch_bounds__(256, 2) void cin_bs_kernel(const float *__restrict_
         for (int ti = 0; ti < 2; ++ti)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int h = (r & 3) + 8 * (r >> 2) + 4 * hh;
+                const int h = rp_mfma32_row(r, hh);
                 if (h < Hr && ok[ti]) dx[bt[ti] * lddx + (int64_t)h * D + dt[ti]] = ep[ti][r];
             }
     }
@@ -303,7 +292,7 @@ __global__ __launch_bounds__(256) void cin_bs_bwd_w_kernel(const float *__restri
         for (int64_t b = bbeg; b < bend; ++b) {
             for (int ks = 0; ks < nks; ++ks) {
                 const int d0 = ks * 16 + 8 * hh;
-                cbf8 vx, vp;
+                f32x8 vx, vp;
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
                     vx[e] = 0.f;
@@ -329,13 +318,13 @@ __global__ __launch_bounds__(256) void cin_bs_bwd_w_kernel(const float *__restri
                         vp[4 + e] = q1[e];
                     }
                 }
-                cbbf8 bq[3];
-                cb_split(vp, bq);
+                bf16x8 bq[3];
+                bf_round3_8(vp, bq);
 #pragma unroll
                 for (int u = 0; u < CW_CH; ++u) {
                     int o = o0 + u;
                     if (o >= O) o = O - 1;  // a channel past the end recomputes the last one; its tile is never stored
-                    cbf8 vg;
+                    f32x8 vg;
 #pragma unroll
                     for (int e = 0; e < 8; ++e) vg[e] = 0.f;
                     if (gout != nullptr) {
@@ -353,8 +342,8 @@ __global__ __launch_bounds__(256) void cin_bs_bwd_w_kernel(const float *__restri
                         for (int e = 0; e < 8; ++e) vg[e] += gp;
                     }
                     bsum[u] += ((vg[0] + vg[1]) + (vg[2] + vg[3])) + ((vg[4] + vg[5]) + (vg[6] + vg[7]));
-                    cbbf8 a[3];
-                    cb_split(vg * vx, a);
+                    bf16x8 a[3];
+                    bf_round3_8(vg * vx, a);
                     acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bq[2], acc[u], 0, 0, 0);
                     acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2], bq[0], acc[u], 0, 0, 0);
                     acc[u] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1], bq[1], acc[u], 0, 0, 0);
@@ -373,7 +362,7 @@ __global__ __launch_bounds__(256) void cin_bs_bwd_w_kernel(const float *__restri
         float *Pz = P + ((int64_t)blockIdx.x * O + o) * 1024;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int h = (r & 3) + 8 * (r >> 2) + 4 * hh;
+            const int h = rp_mfma32_row(r, hh);
             Pz[h * 32 + i] = acc[u][r];
         }
         if (Pb != nullptr) {
@@ -462,7 +451,6 @@ extern "C" int rp_cin_bs_bwd_w(const float *x0, int64_t ld0, const float *xp, in
 // The next stage's loads are issued before this stage's MFMA block.  (Loading G 8 threads per 128-byte row, whole lines
 // per wave instruction, measured SLOWER than one 32-byte octet per thread: twice the LDS store instructions.)
 #define CP_LD 40
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 // products of the split-bf16 evaluation, smallest terms first (as BfProd in gemm.hip): piece 0 = hi, 1 = mid, 2 = lo
 template <int NPROD>
 struct CpProd {
@@ -538,7 +526,7 @@ __global__ __launch_bounds__(512, 4) void cin_pair_bwd_w_kernel(const float *__r
     };
     if (nstage > 0) load_stage();
     for (int64_t st = 0; st < nstage; ++st) {
-        cbf8 vg;
+        f32x8 vg;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             vg[e] = gq[0][e] + gpq;
@@ -547,33 +535,33 @@ __global__ __launch_bounds__(512, 4) void cin_pair_bwd_w_kernel(const float *__r
         if (do_bias) bsum += ((vg[0] + vg[1]) + (vg[2] + vg[3])) + ((vg[4] + vg[5]) + (vg[6] + vg[7]));
         __syncthreads();  // previous stage's fragment reads (and Xs reads) are done
         if (t < 256) *reinterpret_cast<f32x4 *>(&Xs[gr][4 * gs]) = xq;
-        cbbf8 pc[3];
-        cb_split(vg, pc);
+        bf16x8 pc[3];
+        bf_round3_8(vg, pc);
 #pragma unroll
-        for (int q = 0; q < NPC; ++q) *reinterpret_cast<cbbf8 *>(&At[q][c][8 * oct]) = pc[q];
+        for (int q = 0; q < NPC; ++q) *reinterpret_cast<bf16x8 *>(&At[q][c][8 * oct]) = pc[q];
         __syncthreads();  // Xs complete
         {
-            cbf8 a0, b0;
+            f32x8 a0, b0;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 a0[e] = Xs[h0][8 * oct + e];
                 b0[e] = Xs[m0_][8 * oct + e];
             }
-            cb_split(a0 * b0, pc);
+            bf_round3_8(a0 * b0, pc);
 #pragma unroll
-            for (int q = 0; q < NPC; ++q) *reinterpret_cast<cbbf8 *>(&Bt[q][c][8 * oct]) = pc[q];
+            for (int q = 0; q < NPC; ++q) *reinterpret_cast<bf16x8 *>(&Bt[q][c][8 * oct]) = pc[q];
         }
         if (st + 1 < nstage) load_stage();
         __syncthreads();
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            cbbf8 a[3], bq[2][3];
+            bf16x8 a[3], bq[2][3];
 #pragma unroll
             for (int q = 0; q < NPC; ++q) {
-                a[q] = *reinterpret_cast<const cbbf8 *>(&At[q][wa + i][ks * 16 + 8 * hh]);
+                a[q] = *reinterpret_cast<const bf16x8 *>(&At[q][wa + i][ks * 16 + 8 * hh]);
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
-                    bq[u][q] = *reinterpret_cast<const cbbf8 *>(&Bt[q][wb + 32 * u + i][ks * 16 + 8 * hh]);
+                    bq[u][q] = *reinterpret_cast<const bf16x8 *>(&Bt[q][wb + 32 * u + i][ks * 16 + 8 * hh]);
             }
             // product-major: consecutive MFMAs alternate between the two accumulators (smallest terms first)
 #pragma unroll
@@ -594,7 +582,7 @@ __global__ __launch_bounds__(512, 4) void cin_pair_bwd_w_kernel(const float *__r
         if (p >= npair) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = wa + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            const int o = wa + rp_mfma32_row(r, hh);
             if (o < O) Pz[(int64_t)o * npair + p] = acc[v][r];
         }
     }
@@ -750,19 +738,19 @@ __global__ __launch_bounds__(512, 4) void cin_pair_fwd_kernel(const float *__res
     const float *xcol = &Xs[0][col];
     for (int st = 0; st < nst; ++st) {
         // B tile: this thread's column, pair octets 2 oq and 2 oq + 1
-        cbbf8 pb[1][3];
+        bf16x8 pb[1][3];
 #pragma unroll
         for (int j = 0; j < 1; ++j) {
             const int k0 = st * 32 + 8 * oq;
             const u32x4 t0 = *reinterpret_cast<const u32x4 *>(&tab[k0]);
             const u32x4 t1 = *reinterpret_cast<const u32x4 *>(&tab[k0 + 4]);
-            cbf8 pr;
+            f32x8 pr;
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
                 pr[e] = xcol[t0[e] & 0xffffu] * xcol[t0[e] >> 16];
                 pr[4 + e] = xcol[t1[e] & 0xffffu] * xcol[t1[e] >> 16];
             }
-            cb_split(pr, pb[j]);
+            bf_round3_8(pr, pb[j]);
         }
         __syncthreads();  // previous stage's fragment reads are done
 #pragma unroll
@@ -772,18 +760,18 @@ __global__ __launch_bounds__(512, 4) void cin_pair_fwd_kernel(const float *__res
             *reinterpret_cast<f32x4 *>(&At[q][row][ch * 8]) = aq[u];
         }
 #pragma unroll
-        for (int q = 0; q < NPC; ++q) *reinterpret_cast<cbbf8 *>(&Bt[q][col][8 * oq]) = pb[0][q];
+        for (int q = 0; q < NPC; ++q) *reinterpret_cast<bf16x8 *>(&Bt[q][col][8 * oq]) = pb[0][q];
         if (st + 1 < nst) load_a(st + 1);
         __syncthreads();
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            cbbf8 a[1][3], bq[2][3];
+            bf16x8 a[1][3], bq[2][3];
 #pragma unroll
             for (int q = 0; q < NPC; ++q) {
-                a[0][q] = *reinterpret_cast<const cbbf8 *>(&At[q][wa + i][ks * 16 + 8 * hh]);
+                a[0][q] = *reinterpret_cast<const bf16x8 *>(&At[q][wa + i][ks * 16 + 8 * hh]);
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
-                    bq[u][q] = *reinterpret_cast<const cbbf8 *>(&Bt[q][wb + 32 * u + i][ks * 16 + 8 * hh]);
+                    bq[u][q] = *reinterpret_cast<const bf16x8 *>(&Bt[q][wb + 32 * u + i][ks * 16 + 8 * hh]);
             }
             // product-major: consecutive MFMAs go to four different accumulators (smallest terms first per accumulator)
 #pragma unroll
@@ -803,7 +791,7 @@ __global__ __launch_bounds__(512, 4) void cin_pair_fwd_kernel(const float *__res
     for (int u = 0; u < 1; ++u)
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int o = wa + 32 * u + (r & 3) + 8 * (r >> 2) + 4 * hh;
+            const int o = wa + 32 * u + rp_mfma32_row(r, hh);
             const float bo = (bias != nullptr && o < O) ? bias[o] : 0.f;
             float val[2], ps[2];
 #pragma unroll
@@ -946,25 +934,25 @@ __global__ __launch_bounds__(512, 4) void cin_pair_bwd_x_kernel(const float *__r
         }
         __syncthreads();  // the slab is complete
         {
-            cbf8 gv;
+            f32x8 gv;
 #pragma unroll
             for (int e = 0; e < 8; ++e) gv[e] = Gs[(8 * oq + e) * 132 + col];
-            cbbf8 pc[3];
-            cb_split(gv, pc);
+            bf16x8 pc[3];
+            bf_round3_8(gv, pc);
 #pragma unroll
-            for (int q = 0; q < NPC; ++q) *reinterpret_cast<cbbf8 *>(&Bt[q][col][8 * oq]) = pc[q];
+            for (int q = 0; q < NPC; ++q) *reinterpret_cast<bf16x8 *>(&Bt[q][col][8 * oq]) = pc[q];
         }
         if (st + 1 < nst) load_stage(st + 1);
         __syncthreads();
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            cbbf8 a[3], bq[2][3];
+            bf16x8 a[3], bq[2][3];
 #pragma unroll
             for (int q = 0; q < NPC; ++q) {
-                a[q] = *reinterpret_cast<const cbbf8 *>(&At[q][wa + i][ks * 16 + 8 * hh]);
+                a[q] = *reinterpret_cast<const bf16x8 *>(&At[q][wa + i][ks * 16 + 8 * hh]);
 #pragma unroll
                 for (int u = 0; u < 2; ++u)
-                    bq[u][q] = *reinterpret_cast<const cbbf8 *>(&Bt[q][wb + 32 * u + i][ks * 16 + 8 * hh]);
+                    bq[u][q] = *reinterpret_cast<const bf16x8 *>(&Bt[q][wb + 32 * u + i][ks * 16 + 8 * hh]);
             }
 #pragma unroll
             for (int pr = 0; pr < NPROD; ++pr) {
@@ -986,7 +974,7 @@ __global__ __launch_bounds__(512, 4) void cin_pair_bwd_x_kernel(const float *__r
                 for (int v = 0; v < 2; ++v)
 #pragma unroll
                     for (int r = 0; r < 16; ++r)
-                        Ts[(32 * (wr & 1) + (r & 3) + 8 * (r >> 2) + 4 * hh) * 132 + wb + 32 * v + i] = acc[v][r];
+                        Ts[(32 * (wr & 1) + rp_mfma32_row(r, hh)) * 132 + wb + 32 * v + i] = acc[v][r];
             }
             __syncthreads();
             const int lbase = (tile * 2 + half) * H;

@@ -16,6 +16,7 @@
 //                       operands are already "contraction-contiguous": 8 consecutive d of one (b,h) are one 32-byte
 //                       read).  Batch split over workgroups, deterministic second-stage sum.
 #include "common.h"
+#include "bfsplit.h"  // bf_round3_8
 
 #define CL_MAXH 32
 
@@ -130,17 +131,7 @@ extern "C" int rp_cin_last_bwd_x(const float *x0, int64_t ld0, const float *xp, 
 // 8o..8o+7 of X0 row h = c (c < 32) and of the two Xp rows m = 2c, 2c+1 (c < 64) as 2 x dwordx4 each, splits them
 // into bf16 pieces and writes ONE 16-byte LDS segment per piece — the LDS images are [h][r] / [m][r] and the MFMA
 // fragments (8 consecutive r per lane) are ds_read_b128.  Waves: 4 = the four 32-column m tiles.
-typedef __bf16 clbf8 __attribute__((ext_vector_type(8)));
-typedef float clf8 __attribute__((ext_vector_type(8)));
 #define CLV_LD 40
-
-__device__ __forceinline__ void cl_split(clf8 v, clbf8 (&p)[3]) {
-    p[0] = __builtin_convertvector(v, clbf8);
-    v -= __builtin_convertvector(p[0], clf8);
-    p[1] = __builtin_convertvector(v, clbf8);
-    v -= __builtin_convertvector(p[1], clf8);
-    p[2] = __builtin_convertvector(v, clbf8);
-}
 
 __global__ __launch_bounds__(256) void cin_last_bwd_v_kernel(const float *__restrict__ x0, int64_t ld0,
                                                              const float *__restrict__ xp, int64_t ldp,
@@ -165,14 +156,14 @@ __global__ __launch_bounds__(256) void cin_last_bwd_v_kernel(const float *__rest
         const float gb = g[b];
         for (int half = 0; half < nhalf; ++half) {
             const int d0 = half * 32 + 8 * o;
-            clf8 va, vb0, vb1;
+            f32x8 va, vb0, vb1;
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
                 va[e] = 0.f;
                 vb0[e] = 0.f;
                 vb1[e] = 0.f;
             }
-            auto load8 = [&](const float *row, clf8 &dst) {
+            auto load8 = [&](const float *row, f32x8 &dst) {
                 if (vec && d0 + 8 <= D) {
                     const f32x4 q0 = *reinterpret_cast<const f32x4 *>(row + d0);
                     const f32x4 q1 = *reinterpret_cast<const f32x4 *>(row + d0 + 4);
@@ -193,26 +184,26 @@ __global__ __launch_bounds__(256) void cin_last_bwd_v_kernel(const float *__rest
             if (mb < M) load8(xp + b * ldp + (int64_t)mb * D, vb1);
             va *= gb;
             __syncthreads();  // the previous stage's fragment reads are done
-            clbf8 pc[3];
+            bf16x8 pc[3];
             if (c < 32) {
-                cl_split(va, pc);
+                bf_round3_8(va, pc);
 #pragma unroll
-                for (int q = 0; q < 3; ++q) *reinterpret_cast<clbf8 *>(&At[q][c][8 * o]) = pc[q];
+                for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8 *>(&At[q][c][8 * o]) = pc[q];
             }
-            cl_split(vb0, pc);
+            bf_round3_8(vb0, pc);
 #pragma unroll
-            for (int q = 0; q < 3; ++q) *reinterpret_cast<clbf8 *>(&Bt[q][2 * c][8 * o]) = pc[q];
-            cl_split(vb1, pc);
+            for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8 *>(&Bt[q][2 * c][8 * o]) = pc[q];
+            bf_round3_8(vb1, pc);
 #pragma unroll
-            for (int q = 0; q < 3; ++q) *reinterpret_cast<clbf8 *>(&Bt[q][2 * c + 1][8 * o]) = pc[q];
+            for (int q = 0; q < 3; ++q) *reinterpret_cast<bf16x8 *>(&Bt[q][2 * c + 1][8 * o]) = pc[q];
             __syncthreads();
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                clbf8 a[3], bq[3];
+                bf16x8 a[3], bq[3];
 #pragma unroll
                 for (int q = 0; q < 3; ++q) {
-                    a[q] = *reinterpret_cast<const clbf8 *>(&At[q][i][ks * 16 + 8 * hh]);
-                    bq[q] = *reinterpret_cast<const clbf8 *>(&Bt[q][32 * w + i][ks * 16 + 8 * hh]);
+                    a[q] = *reinterpret_cast<const bf16x8 *>(&At[q][i][ks * 16 + 8 * hh]);
+                    bq[q] = *reinterpret_cast<const bf16x8 *>(&Bt[q][32 * w + i][ks * 16 + 8 * hh]);
                 }
                 // hi*lo + lo*hi + mid*mid + hi*mid + mid*hi + hi*hi  (smallest terms first)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0], bq[2], acc, 0, 0, 0);
@@ -230,7 +221,7 @@ __global__ __launch_bounds__(256) void cin_last_bwd_v_kernel(const float *__rest
     if (m < M) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int h = (r & 3) + 8 * (r >> 2) + 4 * hh;
+            const int h = rp_mfma32_row(r, hh);
             if (h < H) Pz[(int64_t)h * M + m] = acc[r];
         }
     }

@@ -87,12 +87,14 @@ static inline int64_t rp_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 
+#include "device.h"
+
 // activation of a GEMM epilogue (RP_ACT_MASK is handled at the call site: it needs aux)
 __device__ __forceinline__ float rp_act_apply(int act, float v) {
     switch (act) {
         case RP_ACT_RELU: return v > 0.f ? v : 0.f;
         case RP_ACT_TANH: return tanhf(v);
-        case RP_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
+        case RP_ACT_SIGMOID: return rp_sigmoid(v);
         case RP_ACT_LEAKY: return v > 0.f ? v : 0.01f * v;
         default: return v;
     }
@@ -107,9 +109,6 @@ __device__ __forceinline__ float rp_act_grad(int act, float dy, float y) {
         default: return dy;
     }
 }
-
-// wave64 constants: hard-coded, gfx950 only
-#define RP_WAVE 64
 
 // Matrix-core products per flop for a GEMM-shaped launch under the process-wide precision mode (gemm.hip):
 // 6 / 3 / 1 bf16 products, or 0 for the f32-input MFMA.  RP_MATMUL_AUTO picks 3 (~2^-16 per product) when the launch is

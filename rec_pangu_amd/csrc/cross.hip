@@ -16,15 +16,6 @@
 #define CROSS_J 8  // d <= 2048
 #define CROSS_MAXL 6
 
-__device__ __forceinline__ float block_allsum_256(float v, float *sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    __syncthreads();  // sh may still be read from the previous reduction
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
 // Forward: one 64-lane wave per row, persistent workgroups.  W (L rows), wfc and — when they fit in 64 KB of LDS
 // next to them — the biases are staged once per workgroup, zero-padded to 256-column chunks; lane l owns columns
 // 256j + 4l .. +3 of chunk j (dwordx4 global accesses, conflict-free ds_read_b128).  The row stays in registers
@@ -258,8 +249,7 @@ __global__ __launch_bounds__(256) void crossnet_bwd_rows_kernel(const float *__r
                 const f32x4 pr = g[j] * r0[j];
                 part += (pr.x + pr.y) + (pr.z + pr.w);
             }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+            part = rp_lane_sum(part);
             const float tl = part;
             if (lane == 0) {
                 Vb[l] = tl * a_run;

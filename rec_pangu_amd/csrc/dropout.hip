@@ -10,27 +10,6 @@
 // reference itself between CPU and GPU.  HBM-bound: 4 B read + 5 B written per element.
 #include "common.h"
 
-__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                              uint32_t (&out)[4]) {
-    constexpr uint32_t M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
-        const uint32_t hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n1 = lo1, n2 = hi0 ^ c3 ^ k1, n3 = lo0;
-        c0 = n0;
-        c1 = n1;
-        c2 = n2;
-        c3 = n3;
-        k0 += W0;
-        k1 += W1;
-    }
-    out[0] = c0;
-    out[1] = c1;
-    out[2] = c2;
-    out[3] = c3;
-}
-
 // element e = m * N + n (logical index, independent of the leading dimensions); group = e / 4
 template <bool VEC>
 __global__ __launch_bounds__(256) void dropout_fwd_kernel(const float *__restrict__ x, int64_t ldx, float *__restrict__ y,
@@ -43,8 +22,8 @@ __global__ __launch_bounds__(256) void dropout_fwd_kernel(const float *__restric
     for (int64_t grp = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; grp < ngroups;
          grp += (int64_t)gridDim.x * blockDim.x) {
         uint32_t r[4];
-        philox4x32_10((uint32_t)grp, (uint32_t)(grp >> 32), (uint32_t)offset, (uint32_t)(offset >> 32), (uint32_t)seed,
-                      (uint32_t)(seed >> 32), r);
+        rp_philox4x32_10((uint32_t)grp, (uint32_t)(grp >> 32), (uint32_t)offset, (uint32_t)(offset >> 32), (uint32_t)seed,
+                         (uint32_t)(seed >> 32), r);
         const int64_t e0 = grp * 4;
         if (VEC) {  // N % 4 == 0, 16-byte aligned rows: the four elements sit in one row
             const int64_t m = e0 / N;
@@ -118,10 +97,7 @@ static int dropout_fwd_impl(const float *x, int64_t ldx, float *y, int64_t ldy, 
     RP_REQUIRE(x && y && mask && M >= 0 && N >= 1 && ldx >= N && ldy >= N, "dropout_fwd: bad argument");
     RP_REQUIRE(p >= 0.f && p < 1.f, "dropout_fwd: p = %f outside [0, 1)", (double)p);
     if (M == 0) return RP_OK;
-    // keep <=> r >= thresh with r uniform on [0, 2^32): P(drop) = thresh / 2^32 = p
-    double t = (double)p * 4294967296.0;
-    if (t > 4294967295.0) t = 4294967295.0;
-    const uint32_t thresh = (uint32_t)t;
+    const uint32_t thresh = rp_keep_thresh(p);
     const float scale = 1.f / (1.f - p);
     const bool vec = (N % 4 == 0) && (ldx % 4 == 0) && (ldy % 4 == 0) && rp_aligned16(x) && rp_aligned16(y) &&
                      ((reinterpret_cast<uintptr_t>(mask) & 3u) == 0);

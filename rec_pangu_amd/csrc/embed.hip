@@ -541,7 +541,7 @@ __global__ __launch_bounds__(256, 2) void embed_gather_linear_kernel(
         const float bv = bias != nullptr ? bias[n] : 0.f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t m = blk * 128 + 32 * wv + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int64_t m = blk * 128 + 32 * wv + rp_mfma32_row(r, h);
             if (FULL || m < B) h1[m * 64 + n] = fmaxf(acc[nt][r] + bv, 0.f);
         }
     }
@@ -781,7 +781,7 @@ __global__ __launch_bounds__(256, 3) void embed_grad_gemm_kernel(
         if (FM_U) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const float *src = sum_in + (int64_t)tsmp[32 * wv + (r & 3) + 8 * (r >> 2) + 4 * h] * D + i;
+                const float *src = sum_in + (int64_t)tsmp[32 * wv + rp_mfma32_row(r, h)] * D + i;
                 uraw[0][r] = src[0];
                 uraw[1][r] = src[32];
             }
@@ -1593,7 +1593,7 @@ __global__ __launch_bounds__(256, (SEG == 8 ? 2 : 3)) void embed_grad_seg_kernel
         for (int mb = 0; mb < MB; ++mb)
             if (32 * (mh + 2 * mb) < P) {
 #pragma unroll
-                for (int r = 0; r < 16; ++r) HsT[32 * (mh + 2 * mb) + (r & 3) + 8 * (r >> 2) + 4 * h][32 * nb + i] = ag[mb][r];
+                for (int r = 0; r < 16; ++r) HsT[32 * (mh + 2 * mb) + rp_mfma32_row(r, h)][32 * nb + i] = ag[mb][r];
             }
         tile_keys_store(nk0, nk1);  // (this tile's keys were last read in front of barrier A)
         SEG_BARRIER();  // (C)

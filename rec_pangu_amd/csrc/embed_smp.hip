@@ -205,11 +205,11 @@ __global__ __launch_bounds__(256, 2) void embed_grad_smp_kernel(
         if (bb0 + R <= Bi) {  // (workgroup-uniform: a full unit needs no clamp, the row offsets are immediates)
             const float *src = sum_in + (r0 * (uint32_t)D + col);
 #pragma unroll
-            for (int r = 0; r < 16; ++r) sv[r] = src[((r & 3) + 8 * (r >> 2)) * D];
+            for (int r = 0; r < 16; ++r) sv[r] = src[rp_mfma32_row(r, 0) * D];
         } else {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                uint32_t b = r0 + (uint32_t)((r & 3) + 8 * (r >> 2));
+                uint32_t b = r0 + (uint32_t)rp_mfma32_row(r, 0);
                 b = b < (uint32_t)Bi ? b : (uint32_t)Bi - 1u;
                 sv[r] = sum_in[b * (uint32_t)D + col];
             }

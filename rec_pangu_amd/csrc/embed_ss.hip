@@ -414,7 +414,7 @@ __global__ __launch_bounds__(256, 2) void embed_ss_urows_kernel(
     for (int mb = 0; mb < MB; ++mb)
         if (32 * (mh + 2 * mb) < Mb) {
 #pragma unroll
-            for (int r2 = 0; r2 < 16; ++r2) HsT[32 * (mh + 2 * mb) + (r2 & 3) + 8 * (r2 >> 2) + 4 * h][32 * nb + i] = ag[mb][r2];
+            for (int r2 = 0; r2 < 16; ++r2) HsT[32 * (mh + 2 * mb) + rp_mfma32_row(r2, h)][32 * nb + i] = ag[mb][r2];
         }
     SS_BARRIER();  // (C)
     // ---- the rows' gradient: C + u - s v, one writer per row ---------------------------------------------------------------

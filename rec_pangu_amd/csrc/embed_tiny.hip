@@ -33,18 +33,6 @@ struct TinyTables {
     int acc0[ET_MAXF];   // its first accumulator row
 };
 
-__device__ __forceinline__ void tiny_split3(float v, __bf16 *p0, __bf16 *p1, __bf16 *p2) {
-    // truncation split: hi + mid + lo == v exactly (bfsplit.h)
-    uint32_t u = __float_as_uint(v);
-    *reinterpret_cast<uint16_t *>(p0) = (uint16_t)(u >> 16);
-    v -= __uint_as_float(u & 0xFFFF0000u);
-    u = __float_as_uint(v);
-    *reinterpret_cast<uint16_t *>(p1) = (uint16_t)(u >> 16);
-    v -= __uint_as_float(u & 0xFFFF0000u);
-    u = __float_as_uint(v);
-    *reinterpret_cast<uint16_t *>(p2) = (uint16_t)(u >> 16);
-}
-
 __global__ __launch_bounds__(256, 2) void embed_grad_tiny_partial_kernel(
     const int32_t *__restrict__ keys, int64_t B, TinyTables tt, const float *__restrict__ dh, int64_t lddh,
     const float *__restrict__ sum_in, const float *__restrict__ gfm, int64_t per_blk, float *__restrict__ partial) {
@@ -114,12 +102,12 @@ __global__ __launch_bounds__(256, 2) void embed_grad_tiny_partial_kernel(
 #pragma unroll
             for (int e = 0; e < 16; ++e) {
                 const int col = 16 * q + e;
-                tiny_split3(vd[e >> 2][e & 3] * okf, &Zt[0][col][s], &Zt[1][col][s], &Zt[2][col][s]);
+                bf_trunc3_1(vd[e >> 2][e & 3] * okf, &Zt[0][col][s], &Zt[1][col][s], &Zt[2][col][s]);
                 const float uval = (sum_in != nullptr) ? g * vs[e >> 2][e & 3] : 0.f;
-                tiny_split3(uval, &Zt[0][64 + col][s], &Zt[1][64 + col][s], &Zt[2][64 + col][s]);
+                bf_trunc3_1(uval, &Zt[0][64 + col][s], &Zt[1][64 + col][s], &Zt[2][64 + col][s]);
             }
-            if (q == 0) tiny_split3(g, &Zt[0][128][s], &Zt[1][128][s], &Zt[2][128][s]);
-            if (q == 1) tiny_split3(okf, &Zt[0][129][s], &Zt[1][129][s], &Zt[2][129][s]);  // column 129 counts the lookups
+            if (q == 0) bf_trunc3_1(g, &Zt[0][128][s], &Zt[1][128][s], &Zt[2][128][s]);
+            if (q == 1) bf_trunc3_1(okf, &Zt[0][129][s], &Zt[1][129][s], &Zt[2][129][s]);  // column 129 counts the lookups
             if (t < tt.n * ET_CHUNK) rid[t >> 6][t & 63] = (uint8_t)rloc0;
             if (t + 256 < tt.n * ET_CHUNK) rid[(t + 256) >> 6][t & 63] = (uint8_t)rloc1;
             for (int idx = t + 512; idx < tt.n * ET_CHUNK; idx += 256) {  // more than 8 tables: straight from memory

@@ -196,7 +196,7 @@ __global__ __launch_bounds__(256) void linear_wgrad_partial_kernel(const float *
         if (k >= K) continue;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int n = n0 + nt + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int n = n0 + nt + rp_mfma32_row(r, h);
             if (n < N) Pz[(int64_t)n * K + k] = (kk == 0 ? acc0[r] : acc1[r]);
         }
     }
@@ -380,7 +380,7 @@ __global__ __launch_bounds__(64 * WM * WN) void linear_fwd_bf16_kernel(const flo
         for (int mi = 0; mi < MI; ++mi) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t m = m0 + arow0 + 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int64_t m = m0 + arow0 + 32 * mi + rp_mfma32_row(r, h);
                 if (m >= M) continue;
                 float v = acc[mi][ni][r] + bv;
                 if (act == RP_ACT_MASK)
@@ -577,7 +577,7 @@ __global__ __launch_bounds__(512) void linear_fwd_bf16_wide_kernel(const float *
         for (int mi = 0; mi < 2; ++mi) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t m = m0 + arow0 + 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int64_t m = m0 + arow0 + 32 * mi + rp_mfma32_row(r, h);
                 float v = acc[mi][ni][r] + bv;
                 if (act == RP_ACT_MASK)
                     v = (aux[m * ldaux + n] > 0.f) ? v : 0.f;
@@ -659,7 +659,7 @@ __global__ __launch_bounds__(256) void linear_fwd_bf16_smallk_kernel(const float
     if (ROWADD) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int64_t m = m0 + 32 * w + (r & 3) + 8 * (r >> 2) + 4 * h;
+            const int64_t m = m0 + 32 * w + rp_mfma32_row(r, h);
             rsv[r] = rs[m];
             sv[0][r] = radd[m * ldadd + i];
             sv[1][r] = radd[m * ldadd + 32 + i];
@@ -732,23 +732,23 @@ __global__ __launch_bounds__(256) void linear_fwd_bf16_smallk_kernel(const float
                     const float *ap = aux + (m0 + 32 * w + 4 * h) * ldaux + n;
                     float mk[16];
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) mk[r] = ap[((r & 3) + 8 * (r >> 2)) * ldaux];
+                    for (int r = 0; r < 16; ++r) mk[r] = ap[rp_mfma32_row(r, 0) * ldaux];
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) cp[((r & 3) + 8 * (r >> 2)) * ldc] = (mk[r] > 0.f) ? acc[r] + bv : 0.f;
+                    for (int r = 0; r < 16; ++r) cp[rp_mfma32_row(r, 0) * ldc] = (mk[r] > 0.f) ? acc[r] + bv : 0.f;
                 } else {
                     const float fsel = (ROWADD && tile < nadd) ? 1.f : 0.f;  // (a select, not a branch)
 #pragma unroll
                     for (int r = 0; r < 16; ++r) {
                         float v = acc[r] + bv;
                         if (ROWADD) v = __builtin_fmaf(fsel * rsv[r], sv[nt][r], v);
-                        cp[((r & 3) + 8 * (r >> 2)) * ldc] = (ACT == RP_ACT_RELU) ? fmaxf(v, 0.f) : v;
+                        cp[rp_mfma32_row(r, 0) * ldc] = (ACT == RP_ACT_RELU) ? fmaxf(v, 0.f) : v;
                     }
                 }
             } else if (n < N) {
                 const float bv = (bias != nullptr) ? bias[n] : 0.f;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int64_t m = m0 + 32 * w + (r & 3) + 8 * (r >> 2) + 4 * h;
+                    const int64_t m = m0 + 32 * w + rp_mfma32_row(r, h);
                     if (m >= M) continue;
                     float v = acc[r] + bv;
                     if (ACT == RP_ACT_RELU)

@@ -147,7 +147,7 @@ __global__ __launch_bounds__(512) void linear_fwd_pieces_kernel(const char *__re
         for (int mi = 0; mi < 4; ++mi) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int64_t m = m0 + 128 * wm + 32 * mi + (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int64_t m = m0 + 128 * wm + 32 * mi + rp_mfma32_row(r, h);
                 if (!nok || m >= M) continue;
                 float v = acc[mi][ni][r] + bv;
                 if (act == RP_ACT_RELU)

@@ -43,7 +43,6 @@ struct GinGeom {
 };
 
 static inline int gin_pad_to(int n, int r, int mod) { return n + (((r - n) % mod) + mod) % mod; }  // >= n, = r (mod)
-static inline int gin_up4(int n) { return (n + 3) & ~3; }
 
 static bool gin_supported_d(int D) { return D == 8 || D == 16 || D == 20 || D == 32 || D == 64; }
 
@@ -56,7 +55,8 @@ static bool gin_geom(int F, int P, int O, int D, bool bwd, GinGeom *g) {
     if (S > GIN_THREADS / D) S = GIN_THREADS / D;
     if (S < 1) return false;
     g->S = S;
-    g->lds_floats = (bwd ? 2 : 1) * (gin_up4(S * g->RS) + gin_up4(S * g->BS)) + (bwd ? 2 * gin_up4(GIN_PC * GIN_KP) : 0);
+    g->lds_floats = (bwd ? 2 : 1) * (rp_round_up(S * g->RS, 4) + rp_round_up(S * g->BS, 4)) +
+                    (bwd ? 2 * rp_round_up(GIN_PC * GIN_KP, 4) : 0);
     return true;
 }
 

@@ -29,12 +29,6 @@ constexpr int GRU_TB = 32;
 constexpr int GRU_MAX = 128;
 constexpr size_t GRU_LDS_MAX = 160 * 1024 - 512;
 
-__device__ __forceinline__ float gru_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ int gru_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
-
-static inline int gru_pad32(int n) { return (n + 31) / 32 * 32; }
-static inline size_t gru_al(size_t n) { return (n + 255) / 256 * 256; }
-
 // dst_i [3 Hp][Kp], dst_h [3 Hp][Hp]: zero-padded copies of W_ih [3H][in], W_hh [3H][H]
 __global__ __launch_bounds__(256) void gru_pad_w_kernel(const float *__restrict__ wi, const float *__restrict__ wh, int in,
                                                         int H, int Kp, int Hp, float *__restrict__ di,
@@ -148,7 +142,7 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const int64_t *__restrict_
     int st[16], la[16], mine = 0;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int64_t b = b0 + gru_row(r, h);
+        const int64_t b = b0 + rp_mfma32_row(r, h);
         int s = b < B ? steps[b] : 0;
         s = s < 0 ? 0 : (s > L ? (int)L : s);
         st[r] = s;
@@ -173,12 +167,12 @@ __global__ __launch_bounds__(256) void gru_fwd_kernel(const int64_t *__restrict_
         __syncthreads();
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = gru_row(r, h);
+            const int row = rp_mfma32_row(r, h);
             const int64_t b = b0 + row;
             const bool active = t < st[r];
             float out = 0.f;
             if (active) {
-                const float rr = gru_sigmoid(ar[r] + bias.r), zz = gru_sigmoid(az[r] + bias.z);
+                const float rr = rp_sigmoid(ar[r] + bias.r), zz = rp_sigmoid(az[r] + bias.z);
                 const float nn = tanhf(ani[r] + bias.in + rr * (anh[r] + bias.hn));
                 out = hreg[r] = (1.f - zz) * nn + zz * hreg[r];
                 hs[row * ldh + j] = out;
@@ -213,7 +207,7 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const int64_t *__restrict_
     float dhc[16];
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int64_t b = b0 + gru_row(r, h);
+        const int64_t b = b0 + rp_mfma32_row(r, h);
         int s = b < B ? steps[b] : 0;
         st[r] = s < 0 ? 0 : (s > L ? (int)L : s);
         la[r] = b < B ? last[b] : -1;
@@ -238,7 +232,7 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const int64_t *__restrict_
         float keep[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
-            const int row = gru_row(r, h);
+            const int row = rp_mfma32_row(r, h);
             const int64_t b = b0 + row;
             const bool mine = b < B && j < H, active = mine && t < st[r];
             float dar = 0.f, daz = 0.f, dan = 0.f, dhn = 0.f;
@@ -248,7 +242,7 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const int64_t *__restrict_
                 if (dH_all != nullptr) dh += dH_all[(b * L + t) * H + j];
                 if (dh_last != nullptr && t == la[r]) dh += dh_last[b * H + j];
                 const float hp = hs[row * ldh + j];
-                const float rr = gru_sigmoid(ar[r] + bias.r), zz = gru_sigmoid(az[r] + bias.z);
+                const float rr = rp_sigmoid(ar[r] + bias.r), zz = rp_sigmoid(az[r] + bias.z);
                 const float ghn = anh[r] + bias.hn;
                 const float nn = tanhf(ani[r] + bias.in + rr * ghn);
                 dan = dh * (1.f - zz) * (1.f - nn * nn);
@@ -295,7 +289,7 @@ __global__ __launch_bounds__(256) void gru_bwd_kernel(const int64_t *__restrict_
                 }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) {
-                    const int64_t b = b0 + gru_row(r, h);
+                    const int64_t b = b0 + rp_mfma32_row(r, h);
                     if (b < B && col < in) dX[(b * L + t) * in + col] = acc[r];
                 }
             }
@@ -328,19 +322,19 @@ struct GruWs {
 };
 
 int gru_ws(int64_t B, int64_t L, int in, int H, int ids_mode, GruWs *o) {
-    const int Kp = gru_pad32(in), Hp = gru_pad32(H);
+    const int Kp = rp_round_up(in, 32), Hp = rp_round_up(H, 32);
     size_t off = 0, wa = 0, wb = 0;
-    o->wi = off, off += gru_al(sizeof(float) * 3 * Hp * Kp);
-    o->wh = off, off += gru_al(sizeof(float) * 3 * Hp * Hp);
-    o->dgi = off, off += gru_al(sizeof(float) * 3 * H * (size_t)B * L);
-    o->dghs = off, off += gru_al(sizeof(float) * 3 * H * (size_t)B * L);
-    o->slab = off, off += gru_al(sizeof(float) * H * (size_t)rp_cdiv(B, GRU_TB));
-    o->xg = off, off += ids_mode ? gru_al(sizeof(float) * in * (size_t)B * L) : 0;
+    o->wi = off, off += rp_round_up(sizeof(float) * 3 * Hp * Kp, 256);
+    o->wh = off, off += rp_round_up(sizeof(float) * 3 * Hp * Hp, 256);
+    o->dgi = off, off += rp_round_up(sizeof(float) * 3 * H * (size_t)B * L, 256);
+    o->dghs = off, off += rp_round_up(sizeof(float) * 3 * H * (size_t)B * L, 256);
+    o->slab = off, off += rp_round_up(sizeof(float) * H * (size_t)rp_cdiv(B, GRU_TB), 256);
+    o->xg = off, off += ids_mode ? rp_round_up(sizeof(float) * in * (size_t)B * L, 256) : 0;
     int rc = rp_linear_wgrad_workspace_bytes(B * L, 3 * H, in, &wa);
     if (rc != RP_OK) return rc;
     rc = rp_linear_wgrad_workspace_bytes(B * L, 3 * H, H, &wb);
     if (rc != RP_OK) return rc;
-    o->wgrad = off, o->wgrad_bytes = wa > wb ? wa : wb, off += gru_al(o->wgrad_bytes);
+    o->wgrad = off, o->wgrad_bytes = wa > wb ? wa : wb, off += rp_round_up(o->wgrad_bytes, 256);
     o->total = off;
     return RP_OK;
 }
@@ -381,7 +375,7 @@ extern "C" int rp_gru_fwd(const int64_t *ids, const float *E, int64_t V, const f
     if (rc != RP_OK) return rc;
     RP_REQUIRE(workspace_bytes >= ws.total && rp_aligned16(workspace), "gru_fwd: workspace too small or misaligned");
     if (B == 0) return RP_OK;
-    const int Kp = gru_pad32(in), Hp = gru_pad32(H);
+    const int Kp = rp_round_up(in, 32), Hp = rp_round_up(H, 32);
     float *wi = reinterpret_cast<float *>(static_cast<char *>(workspace) + ws.wi);
     float *wh = reinterpret_cast<float *>(static_cast<char *>(workspace) + ws.wh);
     hipStream_t s = (hipStream_t)stream;
@@ -423,7 +417,7 @@ extern "C" int rp_gru_bwd(const int64_t *ids, const float *E, int64_t V, const f
     if (rc != RP_OK) return rc;
     RP_REQUIRE(workspace_bytes >= ws.total && rp_aligned16(workspace), "gru_bwd: workspace too small or misaligned");
     if (B == 0) return RP_OK;
-    const int Kp = gru_pad32(in), Hp = gru_pad32(H);
+    const int Kp = rp_round_up(in, 32), Hp = rp_round_up(H, 32);
     char *base = static_cast<char *>(workspace);
     float *wi = reinterpret_cast<float *>(base + ws.wi), *wh = reinterpret_cast<float *>(base + ws.wh);
     float *dgi = reinterpret_cast<float *>(base + ws.dgi), *dghs = reinterpret_cast<float *>(base + ws.dghs);

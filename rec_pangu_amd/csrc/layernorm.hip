@@ -54,12 +54,6 @@ __device__ __forceinline__ f32x4 ln_valid4(int c, int N) {
 
 __device__ __forceinline__ float ln_hsum(f32x4 v) { return (v.x + v.y) + (v.z + v.w); }
 
-__device__ __forceinline__ float ln_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, RP_WAVE);
-    return v;
-}
-
 // y = out_scale * ((gamma * (x - mu) * r + beta) [* mul])  [+ y];  NV = quads per lane held in registers, 0 = re-read
 template <int NV>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float *__restrict__ x, int64_t ldx,
@@ -91,7 +85,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float *__restr
                 const f32x4 v = NV > 0 ? xv[j] : ln_load4(xr, (j * RP_WAVE + lane) * 4, N, vx);
                 s += ln_hsum(v);  // (columns that do not exist were loaded as 0)
             }
-            mu = ln_wave_sum(s) * invN;
+            mu = rp_lane_sum(s) * invN;
             float q = 0.f;
 #pragma unroll
             for (int j = 0; j < nq; ++j) {
@@ -100,7 +94,7 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(const float *__restr
                 const f32x4 d = (v - mu) * ln_valid4(c, N);
                 q += ln_hsum(d * d);
             }
-            r = 1.f / sqrtf(ln_wave_sum(q) * invN + eps);
+            r = 1.f / sqrtf(rp_lane_sum(q) * invN + eps);
             if (stats != nullptr && lane == 0) {
                 stats[2 * m] = mu;
                 stats[2 * m + 1] = r;
@@ -193,8 +187,8 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(const float *__restr
             }
         }
         first = false;
-        s1 = ln_wave_sum(s1) * invN;
-        s2 = ln_wave_sum(s2) * invN;
+        s1 = rp_lane_sum(s1) * invN;
+        s2 = rp_lane_sum(s2) * invN;
 #pragma unroll
         for (int j = 0; j < nq; ++j) {
             const int c = (j * RP_WAVE + lane) * 4;

@@ -11,18 +11,6 @@ struct ZPtrs {
     const float *p[4];
 };
 
-__device__ __forceinline__ float block_sum_256(float v, float *sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    const int w = threadIdx.x >> 6;
-    if ((threadIdx.x & 63) == 0) sh[w] = v;
-    __syncthreads();
-    float r = 0.f;
-    if (threadIdx.x == 0) r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return r;  // valid on thread 0
-}
-
 __global__ __launch_bounds__(LOSS_BLOCK) void sigmoid_bce_fwd_kernel(ZPtrs z, int n_add, int apply_sigmoid,
                                                                       const float *__restrict__ label, int64_t B,
                                                                       float p_eps, float *__restrict__ pred,
@@ -32,7 +20,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void sigmoid_bce_fwd_kernel(ZPtrs z, in
     for (int64_t b = (int64_t)blockIdx.x * LOSS_BLOCK + threadIdx.x; b < B; b += (int64_t)gridDim.x * LOSS_BLOCK) {
         float s = z.p[0][b];
         for (int a = 1; a < n_add; ++a) s += z.p[a][b];
-        const float p = apply_sigmoid ? 1.f / (1.f + expf(-s)) : s;
+        const float p = apply_sigmoid ? rp_sigmoid(s) : s;
         if (pred != nullptr) pred[b] = p;
         if (label != nullptr) {
             const float pe = p + p_eps, y = label[b];
@@ -40,7 +28,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void sigmoid_bce_fwd_kernel(ZPtrs z, in
             acc -= y * lp + (1.f - y) * l1p;
         }
     }
-    const float tot = block_sum_256(acc, sh);
+    const float tot = rp_block_sum_256(acc, sh);
     if (threadIdx.x == 0 && partial != nullptr) partial[blockIdx.x] = tot;
 }
 
@@ -51,7 +39,7 @@ __global__ __launch_bounds__(LOSS_BLOCK) void loss_finish_kernel(const float *__
     __shared__ float sh[4];
     float acc = 0.f;
     for (int i = threadIdx.x; i < n; i += LOSS_BLOCK) acc += partial[i];
-    const float tot = block_sum_256(acc, sh);
+    const float tot = rp_block_sum_256(acc, sh);
     if (threadIdx.x == 0) {
         const float term = __fmul_rn(tot, scale);  // (no contraction into an fma: the python sum rounds the product first)
         loss[0] = accumulate ? __fadd_rn(loss[0], term) : term;

@@ -138,7 +138,7 @@ __global__ __launch_bounds__(256, 2) void mlp_tail_fwd_kernel(const float *__res
             const float bv = a.b[ly] != nullptr ? a.b[ly][n] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int rl = rp_mfma32_row(r, h);
                 const float v = fmaxf(acc[nt][r] + bv, 0.f);
                 Ct[wv][rl][n] = v;
                 const int64_t m = (int64_t)blockIdx.x * 128 + 32 * wv + rl;
@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256, 2) void mlp_tail_fwd_kernel(const float *__res
                     for (int q = 1; q < bc.n_add; ++q) z += bc.add[q][row];
                     z += lg;
                 }
-                const float p = 1.f / (1.f + expf(-z));
+                const float p = rp_sigmoid(z);
                 bc.pred[row] = p;
                 const float pe = p + bc.p_eps, y = bc.label[row];
                 const float lp = fmaxf(logf(pe), -100.f), l1p = fmaxf(log1pf(-pe), -100.f);
@@ -189,8 +189,7 @@ __global__ __launch_bounds__(256, 2) void mlp_tail_fwd_kernel(const float *__res
         __syncthreads();
         if (threadIdx.x < 64) {  // fixed-order tree over the workgroup's 128 rows
             float v = lred[threadIdx.x] + lred[threadIdx.x + 64];
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+            v = rp_lane_sum(v);
             if (threadIdx.x == 0) bc.partial[blockIdx.x] = v;
         }
     }
@@ -433,7 +432,7 @@ __global__ __launch_bounds__(256, 2) void mlp_tail_bwd_kernel(const float *__res
             const int n = nt * 32 + i;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int rl = (r & 3) + 8 * (r >> 2) + 4 * h;
+                const int rl = rp_mfma32_row(r, h);
                 const float v = T1[wv][rl][n] > 0.f ? acc[nt][r] : 0.f;
                 if (ly - 1 == 0) {
                     const int64_t m = row0 + 32 * wv + rl;

@@ -11,13 +11,6 @@ namespace {
 constexpr int NARM_MAX_H = 128;
 constexpr int NARM_SLABS = 1024;
 
-__device__ __forceinline__ float narm_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
-__device__ __forceinline__ float narm_wave_sum(float s) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
-    return s;
-}
-
 __global__ __launch_bounds__(256) void narm_attn_fwd_kernel(const float *__restrict__ q1, const float *__restrict__ q2,
                                                             const float *__restrict__ v, const int64_t *__restrict__ ids,
                                                             const float *__restrict__ G, const float *__restrict__ ht, int64_t B,
@@ -36,9 +29,9 @@ __global__ __launch_bounds__(256) void narm_attn_fwd_kernel(const float *__restr
         float al = 0.f;
         if (ids[row] > 0) {  // (uniform over the wave)
             float s = 0.f;
-            if (u0) s += v0 * narm_sigmoid(q1[row * H + c0] + p0);
-            if (u1) s += v1 * narm_sigmoid(q1[row * H + c1] + p1);
-            al = narm_wave_sum(s);
+            if (u0) s += v0 * rp_sigmoid(q1[row * H + c0] + p0);
+            if (u1) s += v1 * rp_sigmoid(q1[row * H + c1] + p1);
+            al = rp_lane_sum(s);
         }
         if (lane == 0) alpha[row] = al;
         if (u0) a0 += al * G[row * H + c0];
@@ -73,13 +66,13 @@ __global__ __launch_bounds__(256) void narm_attn_bwd_kernel(const float *__restr
             float s = 0.f;
             if (u0) s += g0 * G[row * H + c0];
             if (u1) s += g1 * G[row * H + c1];
-            const float ds = ids[row] > 0 ? narm_wave_sum(s) : 0.f;  // d alpha through the mask
+            const float ds = ids[row] > 0 ? rp_lane_sum(s) : 0.f;  // d alpha through the mask
             if (u0) {
-                const float sg = narm_sigmoid(q1[row * H + c0] + p0), d = ds * v0 * sg * (1.f - sg);
+                const float sg = rp_sigmoid(q1[row * H + c0] + p0), d = ds * v0 * sg * (1.f - sg);
                 dq1[row * H + c0] = d, d20 += d, dv0 += ds * sg, dG[row * H + c0] = al * g0;
             }
             if (u1) {
-                const float sg = narm_sigmoid(q1[row * H + c1] + p1), d = ds * v1 * sg * (1.f - sg);
+                const float sg = rp_sigmoid(q1[row * H + c1] + p1), d = ds * v1 * sg * (1.f - sg);
                 dq1[row * H + c1] = d, d21 += d, dv1 += ds * sg, dG[row * H + c1] = al * g1;
             }
         }

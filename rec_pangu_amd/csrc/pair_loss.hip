@@ -14,17 +14,6 @@
 
 #define PL_BLOCK 256
 
-__device__ __forceinline__ float pl_block_sum(float v, float *sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float r = 0.f;
-    if (threadIdx.x == 0) r = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-    __syncthreads();
-    return r;  // valid on thread 0
-}
-
 __device__ __forceinline__ float pl_bce(float p, float y) {
     return -(y * fmaxf(logf(p), -100.f) + (1.f - y) * fmaxf(log1pf(-p), -100.f));
 }
@@ -40,8 +29,8 @@ __global__ __launch_bounds__(PL_BLOCK) void pair_loss_fwd_kernel(const float *__
     float s0 = 0.f, s1 = 0.f, s2 = 0.f;
     for (int64_t b = (int64_t)blockIdx.x * PL_BLOCK + threadIdx.x; b < B; b += (int64_t)gridDim.x * PL_BLOCK) {
         const float a1 = z1[b], a2 = z2[b];
-        const float p1 = apply_sigmoid ? 1.f / (1.f + expf(-a1)) : a1;
-        const float p2 = apply_sigmoid ? 1.f / (1.f + expf(-a2)) : a2;
+        const float p1 = apply_sigmoid ? rp_sigmoid(a1) : a1;
+        const float p2 = apply_sigmoid ? rp_sigmoid(a2) : a2;
         p1o[b] = p1;
         p2o[b] = p2;
         if (mode == RP_PAIR_ESSM) {
@@ -54,7 +43,7 @@ __global__ __launch_bounds__(PL_BLOCK) void pair_loss_fwd_kernel(const float *__
         }
     }
     const int nb = gridDim.x;
-    const float t0 = pl_block_sum(s0, sh), t1 = pl_block_sum(s1, sh), t2 = pl_block_sum(s2, sh);
+    const float t0 = rp_block_sum_256(s0, sh), t1 = rp_block_sum_256(s1, sh), t2 = rp_block_sum_256(s2, sh);
     if (threadIdx.x == 0) {
         partial[blockIdx.x] = t0;
         partial[nb + blockIdx.x] = t1;
@@ -72,7 +61,7 @@ __global__ __launch_bounds__(PL_BLOCK) void pair_loss_finish_kernel(const float 
         s1 += partial[nb + i];
         s2 += partial[2 * nb + i];
     }
-    const float t0 = pl_block_sum(s0, sh), t1 = pl_block_sum(s1, sh), t2 = pl_block_sum(s2, sh);
+    const float t0 = rp_block_sum_256(s0, sh), t1 = rp_block_sum_256(s1, sh), t2 = rp_block_sum_256(s2, sh);
     if (threadIdx.x == 0) {
         const float m0 = __fmul_rn(t0, inv_b), m1 = __fmul_rn(t1, inv_b);
         loss[0] = mode == RP_PAIR_ESSM ? __fadd_rn(m0, __fmul_rn(coef, m1))

@@ -58,9 +58,6 @@
 
 namespace {
 
-// row of the 32 x 32 accumulator tile held in register i of lane half h (the column is lane & 31)
-__device__ __forceinline__ int sce_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
-
 // 8 consecutive floats of one row from column c on, zero beyond D / for a row outside the matrix
 __device__ __forceinline__ f32x8 sce_load8(const float *__restrict__ base, int64_t ld, int64_t row, bool valid, int c, int D,
                                            bool fast) {
@@ -85,14 +82,15 @@ __device__ __forceinline__ f32x8 sce_load8(const float *__restrict__ base, int64
     return v;
 }
 
-// the operand that meets an accumulator tile used as a fragment: element j of k-step s is the tile row sce_row(8 s + j, h)
+// the operand that meets an accumulator tile used as a fragment: element j of k-step s is the tile row
+// rp_mfma32_row(8 s + j, h)
 // (cdna4: registers 8s .. 8s+7 of the accumulator are rows 16 s + 8 (j >> 2) + 4 h + (j & 3)); column c of `base`
 __device__ __forceinline__ f32x8 sce_load_rows(const float *__restrict__ base, int64_t ld, int64_t row0, int64_t nrows, int s,
                                                int h, int c, int D) {
     f32x8 v;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-        const int64_t row = row0 + sce_row(8 * s + j, h);
+        const int64_t row = row0 + rp_mfma32_row(8 * s + j, h);
         v[j] = (row < nrows && c < D) ? base[row * ld + c] : 0.f;
     }
     return v;
@@ -141,11 +139,11 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_fwd_kernel(const float *__restr
             for (int pr = 0; pr < NPROD; ++pr)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ef[BfProd<NPROD>::pa(pr)], uf[ks][BfProd<NPROD>::pb(pr)], acc, 0, 0, 0);
         }
-        // acc[i] = s[b0 + r, v0 + sce_row(i, h)]
+        // acc[i] = s[b0 + r, v0 + rp_mfma32_row(i, h)]
         float tm = -INFINITY;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            if (v0 + sce_row(i, h) >= V) acc[i] = -INFINITY;
+            if (v0 + rp_mfma32_row(i, h) >= V) acc[i] = -INFINITY;
             tm = fmaxf(tm, acc[i]);
         }
         if (tm > -INFINITY) {
@@ -279,7 +277,7 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_du_kernel(const float *__restri
     for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(sce_load8(U, ldu, b0 + r, bvalid, 16 * ks + 8 * h, D, fastU), uf[ks]);
     const float lse_b = bvalid ? lse[b0 + r] : 0.f;
     const int64_t tb = bvalid ? sce_target(tgt, b0 + r, V) : -1;
-    f32x16 dacc[DT];  // dU^T[d = 32 dt + sce_row(i, h), b = b0 + r]
+    f32x16 dacc[DT];  // dU^T[d = 32 dt + rp_mfma32_row(i, h), b = b0 + r]
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -297,10 +295,10 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_du_kernel(const float *__restri
             for (int pr = 0; pr < NPROD; ++pr)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ef[BfProd<NPROD>::pa(pr)], uf[ks][BfProd<NPROD>::pb(pr)], acc, 0, 0, 0);
         }
-        // acc[i] = s[b0 + r, v] at v = v0 + sce_row(i, h), the forward's bits
+        // acc[i] = s[b0 + r, v] at v = v0 + rp_mfma32_row(i, h), the forward's bits
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int64_t v = v0 + sce_row(i, h);
+            const int64_t v = v0 + rp_mfma32_row(i, h);
             acc[i] = (v < V && bvalid) ? expf(acc[i] - lse_b) - (v == tb ? 1.f : 0.f) : 0.f;
         }
 #pragma unroll
@@ -328,7 +326,7 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_du_kernel(const float *__restri
         for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int d = 32 * dt + sce_row(i, h);
+                const int d = 32 * dt + rp_mfma32_row(i, h);
                 if (d < D) o[d] = dacc[dt][i];
             }
     }
@@ -363,7 +361,7 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_de_kernel(const float *__restri
     bf16x8 ef[KS][NP];  // B[k][col r] = E[v0 + r, k]
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(sce_load8(E, D, v0 + r, v0 + r < V, 16 * ks + 8 * h, D, fastE), ef[ks]);
-    f32x16 zacc[DT];  // dE[v = v0 + sce_row(i, h), d = 32 dt + r]
+    f32x16 zacc[DT];  // dE[v = v0 + rp_mfma32_row(i, h), d = 32 dt + r]
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -374,7 +372,7 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_de_kernel(const float *__restri
         float lse_r[16], hit[16];  // lse[b] and [v0 + r == t_b] of register row b; hit = -1 marks a row beyond B
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-            const int64_t b = b0 + sce_row(i, h);
+            const int64_t b = b0 + rp_mfma32_row(i, h);
             const bool ok = b < B;
             acc[i] = 0.f;
             lse_r[i] = ok ? lse[b] : 0.f;
@@ -389,7 +387,7 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_de_kernel(const float *__restri
                 // (the forward pairs piece pa of E with piece pb of U: the same pairs in the same order here)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(uf[BfProd<NPROD>::pb(pr)], ef[ks][BfProd<NPROD>::pa(pr)], acc, 0, 0, 0);
         }
-        // acc[i] = s[b, v0 + r] at b = b0 + sce_row(i, h)
+        // acc[i] = s[b, v0 + r] at b = b0 + rp_mfma32_row(i, h)
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = (hit[i] >= 0.f) ? expf(acc[i] - lse_r[i]) - hit[i] : 0.f;
 #pragma unroll
@@ -418,7 +416,7 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_de_kernel(const float *__restri
             const int d = 32 * dt + r;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const int64_t v = v0 + sce_row(i, h);
+                const int64_t v = v0 + rp_mfma32_row(i, h);
                 if (v < V && d < D) dE[v * D + d] = zacc[dt][i] * scale;
             }
         }

@@ -8,7 +8,7 @@ rounded up to 4, 8, 16, 32, 64 registers, dh <= 64): B = 1, 3, 70; L = 1, 2, 7, 
 mask[:, 0] = 1 in every compared row, so that every query has a visible key (a query without one is quantised at the fp32 ulp
 of 1e6 in the reference and is compared nowhere; one such row runs for finiteness).  Last-row mode at the same shapes against
 row qpos[b] of the full float64 result, qpos = 0, L - 1 and -1 among them.  Dropout at p = 0.1 and 0.5 with the decisions read
-back through rp_seq_attn_keep_mask and fed to the float64 reference."""
+back through rp_seq_attn_keep_mask and fed to the float64 reference; the same decisions byte for byte from rp_dropout_fwd."""
 import functools
 import math
 
@@ -281,3 +281,18 @@ def test_seq_take_is_the_selected_row_and_its_scatter():
     dx = torch.zeros(B, L, D)
     dx[torch.arange(B)[live], qpos[live]] = g[live]
     assert torch.equal(out.detach().cpu(), want) and torch.equal(xd.grad.cpu(), dx)
+
+
+@pytest.mark.parametrize("p", [0.3, 0.9])
+@pytest.mark.parametrize("B,heads,L", [(2, 2, 5), (1, 3, 128)])  # a row that ends inside a Philox group; the kernel's limit
+def test_attention_dropout_and_mlp_dropout_draw_from_one_generator(B, heads, L, p):
+    """Element (m, n) of a 128-wide dropout matrix is in Philox group 32 m + n / 4; attention row m = (b heads + head) L + i,
+    key n is in group 32 m + n / 4 too: at one (seed, offset) the two masks agree byte for byte on the first L columns."""
+    require_gpu()
+    from rec_pangu_amd import hip
+    seed, offset = 20240611, 40
+    rows = B * heads * L
+    keep = hip.seq_attn_keep_mask(B, heads, L, p, seed, offset, torch.device(DEV)).view(rows, L)
+    _, mask = hip.dropout_fwd(torch.ones(rows, 128, device=DEV), p, seed, offset)
+    assert mask.dtype == keep.dtype == torch.uint8 and mask.shape == (rows, 128)
+    assert torch.equal(keep.cpu(), mask[:, :L].cpu())
