@@ -1288,6 +1288,41 @@ int rp_seq_act_bwd(const float *dy, int64_t lddy, const float *x, int64_t ldx, f
 int rp_seq_take_fwd(const float *x, int64_t ldx, const int64_t *qpos, int64_t B, int L, int D, float *out, rp_stream_t stream);
 int rp_seq_take_bwd(const float *dout, const int64_t *qpos, int64_t B, int L, int D, float *dx, rp_stream_t stream);
 
+/* ---- sequence recall: NextItNet's residual blocks of dilated causal convolutions (csrc/causal_conv.hip) ------------------------
+ * replaces ResBlockTwoMasked / ResBlockOneMasked of rec_pangu/models/layers/conv.py with their autograd: ONE block per call.
+ *   two-masked (one_masked 0): out = relu(LN1(conv1_{2d}(relu(LN0(conv0_d(x)))))) + x, both convs C -> C with k taps;
+ *   one-masked (one_masked 1): out = conv2(relu(LN2(conv1_d(relu(LN1(conv0(relu(LN0(x))))))))) + x, conv0 C -> C/2 and conv2
+ *                              C/2 -> C are 1x1, conv1 C/2 -> C/2 has k taps.
+ *   A conv's output position t reads input positions t - (k - 1 - j) dilation, j < k, zero where that is negative; weights
+ *   [Cout, Cin, taps] and biases as nn.Conv1d keeps them.  LN: over the channels of one position, biased variance, eps 1e-5.
+ * X [B, L, C]; lens int64 [B] (clamped to [0, L]): positions >= lens[b] are READ AS ZERO (the reference's masked_fill).
+ * params / grads: HOST arrays of 12 device pointers — conv weight 0..2, conv bias 0..2, LN gamma 0..2, LN beta 0..2, in the
+ *   order of the stages above (the third conv and LN are NULL for a two-masked block).
+ * Full mode (last 0): out [B, L, C], every position; dout [B, L, C].
+ * Last mode (last 1): out [B, C] = the block's output at position lens[b] - 1 (L - 1 when lens[b] = 0), computed from the
+ *   R = 3 (k - 1) + 1 (two-masked) or k (one-masked) positions it depends on, anchor - i dilation; dout [B, C].
+ * The forward keeps nothing but its output.  rp_causal_conv_bwd recomputes the stages from X and WRITES dX [B, L, C] (every
+ *   element: zeros at positions >= lens[b] and, in last mode, at positions the read row does not depend on) and every
+ *   gradient of `grads`: conv weights and biases by one rp_linear_wgrad per conv over buffers in the workspace, gamma / beta
+ *   through per-workgroup slabs added in workgroup order.  No float atomics; bit-identical runs.
+ * Launches, whatever B: forward 2; backward 7 (two-masked) or 9 (one-masked).
+ * Limits (rp_causal_conv_fits: 1 inside, 0 outside; rp_causal_conv_geometry): 2 <= C <= max_c (128), 1 <= k <= max_k (5),
+ *   1 <= L <= max_l (128), L C <= max_lc (8192), dilation >= 1; two tiles of the padded rows must fit lds_bytes.  Outside, a
+ *   null pointer or a workspace that is too small: RP_ERR_ARG, nothing is launched.
+ * Workspace (16-byte aligned), A(x) = x rounded up to 256, p(x) = x rounded up to 32, per conv c (Cin, Cout, taps):
+ *   forward: sum_c 2 A(4 taps p(Cout) p(Cin));   backward: that + sum_c [A(4 B R Cout) if a LayerNorm follows conv c]
+ *   + sum_c A(4 B R Cin taps) (B Cin for the one-masked conv2 in last mode) + A(4 ceil(B / TS) slab width)
+ *   + A(max_c rp_linear_wgrad_workspace_bytes), R = L in full mode. */
+int rp_causal_conv_fits(int L, int C, int k, int one_masked);
+int rp_causal_conv_geometry(int *max_c, int *max_k, int *max_l, int *max_lc, int *lds_bytes);
+int rp_causal_conv_workspace_bytes(int64_t B, int L, int C, int k, int one_masked, int last, int backward, size_t *bytes);
+int rp_causal_conv_fwd(const float *X, const int64_t *lens, int64_t B, int L, int C, int k, int64_t dilation, int one_masked,
+                       int last, const float *const *params, float *out, void *workspace, size_t workspace_bytes,
+                       rp_stream_t stream);
+int rp_causal_conv_bwd(const float *X, const int64_t *lens, const float *dout, int64_t B, int L, int C, int k, int64_t dilation,
+                       int one_masked, int last, const float *const *params, float *dX, float *const *grads, void *workspace,
+                       size_t workspace_bytes, rp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2525,3 +2525,56 @@ def seq_take(x: torch.Tensor, qpos: torch.Tensor):
             hip.note_torch_path(f"seq_take over {x.dtype} (the kernels take fp32)")
         return x.gather(dim=1, index=qpos.view(-1, 1, 1).expand(-1, -1, D)).squeeze(1)
     return _SeqTake.apply(x.reshape(B * L, D), qpos.to(torch.int64).contiguous(), B, L)
+
+
+# ----------------------------------------------------------------------------------------------
+# sequence recall: one residual block of NextItNet (models/layers/conv.py: ResBlockTwoMasked / ResBlockOneMasked) as ONE
+# autograd node; the forward keeps the block's input and nothing else (csrc/causal_conv.hip)
+# ----------------------------------------------------------------------------------------------
+class _CausalConvBlock(torch.autograd.Function):
+    """inputs: x, lens, k, dilation, one_masked, last, then the block's 12 parameter slots (None where it has none)"""
+
+    @staticmethod
+    def forward(ctx, x, lens, k: int, dilation: int, one_masked: bool, last: bool, *params):
+        x = x.contiguous()
+        ps = [None if p is None else p.contiguous() for p in params]
+        ctx.cfg = (k, dilation, one_masked, last)
+        ctx.have = [p is not None for p in ps]
+        ctx.save_for_backward(x, lens, *[p for p in ps if p is not None])
+        return hip.causal_conv_fwd(x, lens, ps, k, dilation, one_masked, last)
+
+    @staticmethod
+    def backward(ctx, dout):
+        x, lens, *held = ctx.saved_tensors
+        it = iter(held)
+        ps = [next(it) if h else None for h in ctx.have]
+        dx, grads = hip.causal_conv_bwd(x, lens, dout.contiguous(), ps, *ctx.cfg)
+        return (dx, None, None, None, None, None, *grads)
+
+
+def causal_conv_block_reference(x, lens, block, last: bool):
+    """the block in torch ops (the reference's formulas, any device and dtype): rows at positions >= lens read as zero"""
+    B, L, _ = x.shape
+    behind = torch.arange(L, device=x.device).unsqueeze(0) >= lens.unsqueeze(-1)
+    y = block(torch.masked_fill(x, behind.unsqueeze(-1), 0).transpose(1, 2))
+    if last:
+        return y[torch.arange(B, device=x.device), :, lens - 1]  # (lens = 0 reads position L - 1)
+    return y.transpose(1, 2)
+
+
+def causal_conv_block(x: torch.Tensor, lens: torch.Tensor, block, last: bool):
+    """One residual block of NextItNet over x [B, L, C] with lengths lens int64 [B] (rows at positions >= lens[b] are read as
+    zero; the residual adds the row as read).  last = False -> [B, L, C], every position; last = True -> [B, C], the block's
+    output at position lens[b] - 1 (L - 1 for lens[b] = 0), computed on the HIP device from the few rows it depends on.
+    `block`: a ResBlockTwoMasked / ResBlockOneMasked (the parameter holder).  One rp_causal_conv_fwd / _bwd per call on the
+    HIP device inside the kernel's limits; the torch formulas on CPU tensors and, counted, outside the limits."""
+    if not x.is_cuda:
+        return causal_conv_block_reference(x, lens, block, last)
+    B, L, Cw = x.shape
+    lens = lens.to(torch.int64).contiguous()
+    k, d = block.kernel_size, block.dilation
+    if x.dtype != torch.float32 or d < 1 or not hip.causal_conv_fits(L, Cw, k, block.one_masked):
+        hip.note_torch_path(f"causal_conv_block at L={L}, C={Cw}, k={k}, {x.dtype} (the kernel takes fp32 inside "
+                            f"{hip.causal_conv_geometry()})")
+        return causal_conv_block_reference(x, lens.clamp(0, L), block, last)
+    return _CausalConvBlock.apply(x, lens, int(k), int(d), bool(block.one_masked), bool(last), *block.stage_params())

@@ -3343,3 +3343,104 @@ def seq_take_bwd(dout, qpos, B: int, L: int):
     with _Timed("seq_take_bwd", f"{B}x{L}x{D}", 4 * B * D * (L + 1)):
         _check(lib().rp_seq_take_bwd(dout.data_ptr(), qpos.data_ptr(), B, L, D, dx.data_ptr(), _stream()), "rp_seq_take_bwd")
     return dx
+
+
+# ---- sequence recall: NextItNet's residual blocks of dilated causal convolutions (csrc/causal_conv.hip) ------------------------
+def causal_conv_geometry() -> dict:
+    v = [_i32(0) for _ in range(5)]
+    _check(lib().rp_causal_conv_geometry(*[C.byref(x) for x in v]), "rp_causal_conv_geometry")
+    return dict(zip(("max_c", "max_k", "max_l", "max_lc", "lds_bytes"), (x.value for x in v)))
+
+
+def causal_conv_fits(L: int, Cw: int, k: int, one_masked: bool) -> bool:
+    return bool(lib().rp_causal_conv_fits(L, Cw, k, int(one_masked)))
+
+
+def causal_conv_rows(k: int, one_masked: bool) -> int:
+    """virtual rows per sample of a last-mode launch: the positions the read row depends on"""
+    return k if one_masked else 3 * (k - 1) + 1
+
+
+def causal_conv_stages(Cw: int, k: int, one_masked: bool):
+    """-> ([(Cin, Cout, taps)] per conv, [width] per LayerNorm) in stage order"""
+    mid = Cw // 2
+    if one_masked:
+        return [(Cw, mid, 1), (mid, mid, k), (mid, Cw, 1)], [Cw, mid, mid]
+    return [(Cw, Cw, k), (Cw, Cw, k)], [Cw, Cw]
+
+
+def _causal_conv_args(x, lens, params, k: int, one_masked: bool):
+    """params: 12 entries, conv weight 0..2, conv bias 0..2, LayerNorm gamma 0..2, beta 0..2 (None where the block has none)"""
+    if x.dim() != 3:
+        raise RuntimeError(f"causal_conv: x must be [B, L, C], got {tuple(x.shape)}")
+    B, L, Cw = x.shape
+    _rows(x.view(B * L, Cw) if x.is_contiguous() else x.reshape(B * L, Cw), "x", Cw, B * L)
+    if not x.is_contiguous():
+        raise RuntimeError("causal_conv: x must be contiguous")
+    convs, lns = causal_conv_stages(Cw, k, one_masked)
+    if len(params) != 12:
+        raise RuntimeError("causal_conv: params holds 12 entries")
+    named = []
+    for c in range(3):
+        want = convs[c] if c < len(convs) else None
+        for slot, shape in ((c, None if want is None else (want[1], want[0], want[2])), (3 + c, None if want is None else (want[1],))):
+            t = params[slot]
+            if (t is None) != (shape is None) or (t is not None and tuple(t.shape) != shape):
+                raise RuntimeError(f"causal_conv: parameter {slot} must be {shape}, got {None if t is None else tuple(t.shape)}")
+            if t is not None:
+                named.append((f"param{slot}", t))
+        n = lns[c] if c < len(lns) else None
+        for slot in (6 + c, 9 + c):
+            t = params[slot]
+            if (t is None) != (n is None) or (t is not None and t.numel() != n):
+                raise RuntimeError(f"causal_conv: parameter {slot} must hold {n} elements")
+            if t is not None:
+                named.append((f"param{slot}", t))
+    _params(named)
+    if lens.dtype != torch.int64 or tuple(lens.shape) != (B,) or not lens.is_contiguous():
+        raise RuntimeError(f"causal_conv: lens must be a contiguous int64 [{B}] tensor")
+    _req(x, torch.float32, "x")
+    _req(lens, torch.int64, "lens")
+    for name, t in named:
+        _req(t, torch.float32, name)
+    return B, L, Cw
+
+
+def _ptrs12(ts):
+    return (C.c_void_p * 12)(*[None if t is None else t.data_ptr() for t in ts])
+
+
+def _causal_conv_cost(B, R, Cw, k, one_masked):
+    convs, _ = causal_conv_stages(Cw, k, one_masked)
+    return 2 * B * R * sum(ci * co * t for ci, co, t in convs), 4 * sum(ci * co * t + co for ci, co, t in convs)
+
+
+def causal_conv_fwd(x, lens, params, k: int, dilation: int, one_masked: bool, last: bool):
+    """rp_causal_conv_fwd, one block -> out [B, L, C] (full mode) or [B, C] (last mode: the row at lens - 1)"""
+    B, L, Cw = _causal_conv_args(x, lens, params, k, one_masked)
+    R = causal_conv_rows(k, one_masked) if last else L
+    ws, nbytes = _workspace("causal_conv", B, L, Cw, k, int(one_masked), int(last), 0, device=x.device)
+    out = _new((B, Cw) if last else (B, L, Cw), torch.float32, x.device)
+    flops, wbytes = _causal_conv_cost(B, R, Cw, k, one_masked)
+    with _Timed("causal_conv_fwd", f"{B}x{R}x{Cw}k{k}{'o' if one_masked else 't'}", 4 * (2 * B * R * Cw + out.numel()) + wbytes, flops):
+        _check(lib().rp_causal_conv_fwd(x.data_ptr(), lens.data_ptr(), B, L, Cw, k, int(dilation), int(one_masked), int(last),
+                                        _ptrs12(params), out.data_ptr(), ws.data_ptr(), nbytes, _stream()), "rp_causal_conv_fwd")
+    return out
+
+
+def causal_conv_bwd(x, lens, dout, params, k: int, dilation: int, one_masked: bool, last: bool):
+    """rp_causal_conv_bwd -> (dx [B, L, C], 12 gradients in the order of params, None where params has None)"""
+    B, L, Cw = _causal_conv_args(x, lens, params, k, one_masked)
+    _req(dout, torch.float32, "dout")
+    if tuple(dout.shape) != ((B, Cw) if last else (B, L, Cw)) or not dout.is_contiguous():
+        raise RuntimeError(f"causal_conv_bwd: dout must be a contiguous {(B, Cw) if last else (B, L, Cw)} tensor, got {tuple(dout.shape)}")
+    R = causal_conv_rows(k, one_masked) if last else L
+    ws, nbytes = _workspace("causal_conv", B, L, Cw, k, int(one_masked), int(last), 1, device=x.device)
+    dx = _new((B, L, Cw), torch.float32, x.device)
+    grads = [None if p is None else _new(tuple(p.shape), torch.float32, x.device) for p in params]
+    flops, wbytes = _causal_conv_cost(B, R, Cw, k, one_masked)
+    with _Timed("causal_conv_bwd", f"{B}x{R}x{Cw}k{k}{'o' if one_masked else 't'}", nbytes + 4 * (2 * B * R * Cw + B * L * Cw) + 2 * wbytes, 4 * flops):
+        _check(lib().rp_causal_conv_bwd(x.data_ptr(), lens.data_ptr(), dout.data_ptr(), B, L, Cw, k, int(dilation), int(one_masked),
+                                        int(last), _ptrs12(params), dx.data_ptr(), _ptrs12(grads), ws.data_ptr(), nbytes,
+                                        _stream()), "rp_causal_conv_bwd")
+    return dx, grads

@@ -4,6 +4,7 @@ from .narm import NARM
 from .mind import MIND  # noqa: F401
 from .comirec import ComirecDR  # noqa: F401
 from .sasrec import SASRec  # noqa: F401
+from .nextitnet import NextItNet  # noqa: F401
 
-# (MIND, ComirecDR and SASRec are importable from here; __all__ keeps the list tests/test_gru_host.py pins)
+# (MIND, ComirecDR, SASRec and NextItNet are importable from here; __all__ keeps the list tests/test_gru_host.py pins)
 __all__ = ["YotubeDNN", "GRU4Rec", "NARM"]
