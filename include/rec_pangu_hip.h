@@ -1323,6 +1323,58 @@ int rp_causal_conv_bwd(const float *X, const int64_t *lens, const float *dout, i
                        int one_masked, int last, const float *const *params, float *dX, float *const *grads, void *workspace,
                        size_t workspace_bytes, rp_stream_t stream);
 
+/* ---- sequence recall: session graphs and their gated graph cell (csrc/session_graph.hip) -------------------------------------
+ * replaces generate_graph (rec_pangu/models/utils.py) and SRGNNConv / SRGNNCell (rec_pangu/models/layers/graph.py) with their
+ * autograd, for SRGNN, NISER and GCSAN.  Sample b keeps its nodes in its own L slots: node v is row b L + v, [B, L, ...].
+ *
+ * rp_session_graph: hist int64 [B, L].  Per sample, over its items with id > 0 in order, s_0 .. s_{n-1}:
+ *   nodes  int64 [B, L]  the distinct ids in ascending order (torch.unique's), 0 behind the node count;
+ *   alias  int32 [B, L]  alias[l] = the node number of s_l for l < n, -1 behind (the items are compacted: a hole in hist does
+ *                        not leave one here); transition l is alias[l] -> alias[l + 1];
+ *   count  int32 [B]     the node count;
+ *   indeg / outdeg int32 [B, L]  per node, counted over the multiset of the n - 1 transitions (0 behind the node count).
+ *   1 <= L <= max_l (64, rp_session_graph_geometry; a wave per sample, samples_per_workgroup of them in a workgroup).
+ *   One launch, integer work only.
+ *
+ * rp_ggnn_cell_fwd: ONE step of the cell over H [B, L, D] (rows behind the node count are read as zero) with the graph given
+ *   by alias alone (lengths, node counts and degrees are counted from it; an entry outside [0, L) ends the sample's list):
+ *     p_in = H W_in^T + b_in, p_out = H W_out^T + b_out,
+ *     in[v] = sum over transitions u -> v of p_in[u] / outdeg(u), out[u] = sum over transitions u -> v of p_out[v] / indeg(v)
+ *     (each sum in position order; zero without such a transition),
+ *     gi = [in | out] W_ih^T + b_ih, gh = H W_hh^T + b_hh, r = s(gi_r + gh_r), z = s(gi_z + gh_z), n = tanh(gi_n + r gh_n),
+ *     h' = (1 - z) H + z n   on the rows of nodes, zero behind the node count.
+ *   params / grads: HOST arrays of 8 device pointers: W_in [D, D], b_in [D], W_out [D, D], b_out [D], W_ih [3 D, 2 D],
+ *   b_ih [3 D], W_hh [3 D, D], b_hh [3 D] (incomming_conv.lin, outcomming_conv.lin, lin_ih, lin_hh as nn.Linear keeps them).
+ *   Outputs, each optional (NULL), at least one: Hout [B, L, D] = h'; seq_hidden [B, L, D], row l = h'[alias[l]] for l < n and
+ *   zero behind; ht [B, D] = h'[alias[n - 1]], zero for n = 0.  Nothing is kept but the outputs.
+ * rp_ggnn_cell_bwd: recomputes the step from H and WRITES dH [B, L, D] (zero behind the node count) and all 8 gradients.
+ *   The arriving gradient of h' is dHout + the rows of dseq_hidden at the positions that name the node, in position order,
+ *   + dht at the node of the last position; each of the three may be NULL.  Both reverse aggregations gather; dW and db of
+ *   each Linear are one rp_linear_wgrad over rows stacked in the workspace.  No float atomics; bit-identical runs.
+ * Launches, whatever B: forward 2 (padded weight copies + the cell); backward 2 + the four rp_linear_wgrad.
+ * Limits (rp_ggnn_fits: 1 inside, 0 outside; rp_ggnn_geometry): 1 <= D <= max_d (128), 1 <= L <= max_l (64), B L < 2^29; a
+ *   workgroup takes floor(rows_per_workgroup / L) samples; its tiles must fit lds_bytes.  Outside, a null pointer or a
+ *   workspace that is too small: RP_ERR_ARG, nothing is launched.
+ * Workspace (16-byte aligned), A(x) = x rounded up to 256, p = D rounded up to 32, s3 = 3 D rounded up to 4, k3 = s3 rounded
+ *   up to 8: forward 2 A(4 p p) + A(24 p p) + A(12 p p); backward that + 2 A(4 p p) + A(8 p k3) + A(4 p k3) + A(8 B L D)
+ *   + 2 A(4 B L s3) + 2 A(4 B L D) + A(the largest rp_linear_wgrad_workspace_bytes of the four).
+ *
+ * rp_l2norm_fwd / _bwd: y = x / max(|x|_2, 1e-12) per row of x [M, D] (F.normalize) and its gradient from x and dy; a row of
+ *   zeros stays zero and passes a zero gradient; below 1e-12 the clamp is a constant (dx = dy / 1e-12). */
+int rp_session_graph_geometry(int *max_l, int *samples_per_workgroup);
+int rp_session_graph(const int64_t *hist, int64_t B, int L, int64_t *nodes, int32_t *alias, int32_t *count, int32_t *indeg,
+                     int32_t *outdeg, rp_stream_t stream);
+int rp_ggnn_geometry(int *max_d, int *max_l, int *rows_per_workgroup, int *lds_bytes);
+int rp_ggnn_fits(int L, int D);
+int rp_ggnn_cell_workspace_bytes(int64_t B, int L, int D, int backward, size_t *bytes);
+int rp_ggnn_cell_fwd(const float *H, const int32_t *alias, int64_t B, int L, int D, const float *const *params, float *Hout,
+                     float *seq_hidden, float *ht, void *workspace, size_t workspace_bytes, rp_stream_t stream);
+int rp_ggnn_cell_bwd(const float *H, const int32_t *alias, const float *dHout, const float *dseq_hidden, const float *dht,
+                     int64_t B, int L, int D, const float *const *params, float *dH, float *const *grads, void *workspace,
+                     size_t workspace_bytes, rp_stream_t stream);
+int rp_l2norm_fwd(const float *x, float *y, int64_t M, int D, rp_stream_t stream);
+int rp_l2norm_bwd(const float *x, const float *dy, float *dx, int64_t M, int D, rp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2578,3 +2578,162 @@ def causal_conv_block(x: torch.Tensor, lens: torch.Tensor, block, last: bool):
                             f"{hip.causal_conv_geometry()})")
         return causal_conv_block_reference(x, lens.clamp(0, L), block, last)
     return _CausalConvBlock.apply(x, lens, int(k), int(d), bool(block.one_masked), bool(last), *block.stage_params())
+
+
+# ----------------------------------------------------------------------------------------------
+# sequence recall: the session graphs of SRGNN / NISER / GCSAN (models/utils.py: generate_graph), their gated graph cell
+# (models/layers/graph.py: SRGNNConv, SRGNNCell) and the row L2 normalisation of NISER (csrc/session_graph.hip).
+# Sample b keeps its nodes in its own L slots: node v is row b L + v of [B, L, ...].  A step is ONE autograd node that keeps
+# its input and nothing else; the graph is the alias list.
+# ----------------------------------------------------------------------------------------------
+def session_graph(hist: torch.Tensor):
+    """hist int64 [B, L] -> (nodes int64 [B, L], alias int32 [B, L], count int32 [B], indeg int32 [B, L], outdeg int32 [B, L]).
+    Per sample, over its items with id > 0 in order s_0 .. s_{n-1}: nodes = the distinct ids ascending (torch.unique's order), 0
+    behind the node count; alias[l] = the node number of s_l, -1 for l >= n; transition l is alias[l] -> alias[l + 1], and the
+    degrees count the multiset of the n - 1 transitions.  On the HIP device one rp_session_graph launch (no host copy of the
+    lengths); on CPU tensors, and counted beyond the kernel's L, batched torch ops that give the same integers."""
+    if hist.dim() != 2:
+        raise RuntimeError(f"session_graph: hist must be [B, L], got {tuple(hist.shape)}")
+    L = hist.shape[1]
+    if hist.is_cuda:
+        if L <= hip.session_graph_geometry()["max_l"]:
+            return hip.session_graph(hist.to(torch.int64).contiguous())
+        hip.note_torch_path(f"session_graph at L={L} (the kernel takes L <= {hip.session_graph_geometry()['max_l']})")
+    return session_graph_reference(hist)
+
+
+def session_graph_reference(hist: torch.Tensor):
+    """session_graph in batched torch ops (any device): a stable sort moves the items with id > 0 to the front, a node number
+    is the count of smaller first occurrences, degrees are scatter_adds of integers"""
+    B, L = hist.shape
+    hist = hist.to(torch.int64)
+    dev = hist.device
+    valid = hist > 0
+    n = valid.sum(1)
+    pos = torch.arange(L, device=dev).unsqueeze(0)
+    order = torch.sort((~valid).to(torch.int8), dim=1, stable=True).indices  # the items with id > 0 first, in order
+    inside = pos < n.unsqueeze(1)
+    s = torch.where(inside, hist.gather(1, order), torch.zeros_like(hist))
+    same = (s.unsqueeze(2) == s.unsqueeze(1)) & torch.ones(L, L, dtype=torch.bool, device=dev).tril(-1)  # [b, j, k]: k < j
+    first = inside & ~same.any(2)
+    rank = ((s.unsqueeze(1) < s.unsqueeze(2)) & first.unsqueeze(1)).sum(2)  # [b, i] = #{j first: s_j < s_i}
+    alias = torch.where(inside, rank, torch.full_like(rank, -1))
+    nodes = torch.zeros(B, L + 1, dtype=torch.int64, device=dev)
+    nodes.scatter_(1, torch.where(first, rank, torch.full_like(rank, L)), s)  # (column L collects what is no first occurrence)
+    nodes = nodes[:, :L].contiguous()
+    a = alias.clamp(min=0)
+    leaves = (pos < (n - 1).unsqueeze(1)).to(torch.int64)  # position l starts a transition
+    ends = (inside & (pos > 0)).to(torch.int64)            # position l ends one
+    outdeg = torch.zeros(B, L, dtype=torch.int64, device=dev).scatter_add_(1, a, leaves)
+    indeg = torch.zeros(B, L, dtype=torch.int64, device=dev).scatter_add_(1, a, ends)
+    return nodes, alias.to(torch.int32), first.sum(1).to(torch.int32), indeg.to(torch.int32), outdeg.to(torch.int32)
+
+
+def _cell_params(cell):
+    return [cell.incomming_conv.lin.weight, cell.incomming_conv.lin.bias, cell.outcomming_conv.lin.weight,
+            cell.outcomming_conv.lin.bias, cell.lin_ih.weight, cell.lin_ih.bias, cell.lin_hh.weight, cell.lin_hh.bias]
+
+
+def ggnn_cell_reference(h, alias, params, final: bool):
+    """one step of the cell in torch ops over the padded [B, L, D] layout (any device and dtype): the reference's formulas with
+    the message passing written as gather / scatter_add over the sample's transitions"""
+    w_in, b_in, w_out, b_out, w_ih, b_ih, w_hh, b_hh = params
+    B, L, D = h.shape
+    dev = h.device
+    a = alias.clamp(min=0).to(torch.int64)
+    n = (alias >= 0).sum(1)
+    cnt = (alias.max(dim=1).values.to(torch.int64) + 1).clamp(min=0)
+    pos = torch.arange(L, device=dev).unsqueeze(0)
+    node = (pos < cnt.unsqueeze(1)).to(h.dtype).unsqueeze(-1)
+    h = h * node
+    src, dst = a[:, :-1], a[:, 1:]
+    em = (pos[:, :L - 1] < (n - 1).unsqueeze(1)).to(h.dtype)
+    outdeg = torch.zeros(B, L, dtype=h.dtype, device=dev).scatter_add(1, src, em)
+    indeg = torch.zeros(B, L, dtype=h.dtype, device=dev).scatter_add(1, dst, em)
+    src_d, dst_d = src.unsqueeze(-1).expand(-1, -1, D), dst.unsqueeze(-1).expand(-1, -1, D)
+    p_in = torch.nn.functional.linear(h, w_in, b_in)
+    p_out = torch.nn.functional.linear(h, w_out, b_out)
+    m_in = p_in.gather(1, src_d) * (em / outdeg.gather(1, src).clamp(min=1)).unsqueeze(-1)
+    m_out = p_out.gather(1, dst_d) * (em / indeg.gather(1, dst).clamp(min=1)).unsqueeze(-1)
+    agg_in = torch.zeros_like(h).scatter_add(1, dst_d, m_in)
+    agg_out = torch.zeros_like(h).scatter_add(1, src_d, m_out)
+    gi = torch.nn.functional.linear(torch.cat([agg_in, agg_out], dim=-1), w_ih, b_ih)
+    gh = torch.nn.functional.linear(h, w_hh, b_hh)
+    i_r, i_i, i_n = gi.chunk(3, -1)
+    h_r, h_i, h_n = gh.chunk(3, -1)
+    reset_gate = torch.sigmoid(i_r + h_r)
+    input_gate = torch.sigmoid(i_i + h_i)
+    new_gate = torch.tanh(i_n + reset_gate * h_n)
+    hy = ((1 - input_gate) * h + input_gate * new_gate) * node
+    if not final:
+        return hy
+    seq = hy.gather(1, a.unsqueeze(-1).expand(-1, -1, D)) * (alias >= 0).to(h.dtype).unsqueeze(-1)
+    ht = seq.gather(1, (n - 1).clamp(min=0).view(-1, 1, 1).expand(-1, 1, D)).squeeze(1) * (n > 0).to(h.dtype).unsqueeze(-1)
+    return seq, ht
+
+
+class _GGNNCell(torch.autograd.Function):
+    """inputs: h, alias, final, then the cell's 8 parameters; saved: h, alias and the parameters themselves"""
+
+    @staticmethod
+    def forward(ctx, h, alias, final: bool, *params):
+        ctx.set_materialize_grads(False)
+        h = h.contiguous()
+        ps = [p.contiguous() for p in params]
+        ctx.final = final
+        ctx.save_for_backward(h, alias, *ps)
+        return hip.ggnn_cell_fwd(h, alias, ps, final)
+
+    @staticmethod
+    def backward(ctx, *douts):
+        h, alias, *ps = ctx.saved_tensors
+        douts = [None if d is None else d.contiguous() for d in douts]
+        if all(d is None for d in douts):
+            return (None,) * (3 + len(ps))
+        if ctx.final:
+            dh, grads = hip.ggnn_cell_bwd(h, alias, ps, dseq=douts[0], dht=douts[1])
+        else:
+            dh, grads = hip.ggnn_cell_bwd(h, alias, ps, dhout=douts[0])
+        return (dh, None, None, *grads)
+
+
+def ggnn_cell(h: torch.Tensor, alias: torch.Tensor, cell, final: bool = False):
+    """One step of the session-graph gated cell (`cell`: an SRGNNCell, the parameter holder) over node states h [B, L, D]
+    (node v of sample b at row v of its L slots, rows behind the node count read as zero) on the graphs alias int32 [B, L]
+    describes (session_graph's).  final = False -> h' [B, L, D], zero behind the node count; final = True -> the last step's
+    read-back in sequence order: (seq_hidden [B, L, D] with row l = h'[alias[l]] and ZERO rows at padding, ht [B, D] =
+    seq_hidden at the last item, zero for a sample without items).  One rp_ggnn_cell_fwd / _bwd per call on the HIP device
+    inside the kernel's limits; ggnn_cell_reference on CPU tensors and, counted, outside the limits."""
+    params = _cell_params(cell)
+    if not h.is_cuda:
+        return ggnn_cell_reference(h, alias, params, final)
+    B, L, D = h.shape
+    if h.dtype != torch.float32 or not hip.ggnn_fits(L, D):
+        hip.note_torch_path(f"ggnn_cell at L={L}, D={D}, {h.dtype} (the kernel takes fp32 inside {hip.ggnn_geometry()})")
+        return ggnn_cell_reference(h, alias, params, final)
+    return _GGNNCell.apply(h, alias.to(torch.int32).contiguous(), bool(final), *params)
+
+
+class _L2Normalize(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        x = x.contiguous()
+        ctx.save_for_backward(x)
+        return hip.l2norm_fwd(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return hip.l2norm_bwd(x, dy.contiguous())
+
+
+def l2_normalize(x: torch.Tensor, eps: float = 1e-12):
+    """F.normalize(x, dim=-1): x / max(|x|_2, eps) over the last axis, any leading shape.  A row of zeros stays zero and passes a
+    ZERO gradient (F.normalize passes dy / eps there: the padded node rows of a session are such rows, and nothing reads
+    them).  On the HIP device rp_l2norm_fwd / _bwd (eps is the kernel's 1e-12); torch ops on CPU tensors."""
+    if not x.is_cuda or x.dtype != torch.float32 or eps != 1e-12:
+        if x.is_cuda:
+            hip.note_torch_path(f"l2_normalize over {x.dtype}, eps={eps} (the kernels take fp32 at eps 1e-12)")
+        nrm = x.norm(dim=-1, keepdim=True)
+        return x * torch.where(nrm > 0, 1.0 / nrm.clamp_min(eps), torch.zeros_like(nrm))
+    return _L2Normalize.apply(x.reshape(-1, x.shape[-1])).reshape(x.shape)

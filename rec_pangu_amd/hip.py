@@ -3444,3 +3444,119 @@ def causal_conv_bwd(x, lens, dout, params, k: int, dilation: int, one_masked: bo
                                         int(last), _ptrs12(params), dx.data_ptr(), _ptrs12(grads), ws.data_ptr(), nbytes,
                                         _stream()), "rp_causal_conv_bwd")
     return dx, grads
+
+
+# ---- sequence recall: session graphs, the gated graph cell and the row L2 normalisation (csrc/session_graph.hip) --------------
+def session_graph_geometry() -> dict:
+    v = [_i32(0) for _ in range(2)]
+    _check(lib().rp_session_graph_geometry(*[C.byref(x) for x in v]), "rp_session_graph_geometry")
+    return dict(zip(("max_l", "samples_per_workgroup"), (x.value for x in v)))
+
+
+def session_graph(hist):
+    """rp_session_graph: hist int64 [B, L] -> (nodes int64 [B, L], alias int32 [B, L], count int32 [B], indeg, outdeg int32 [B, L])"""
+    if hist.dim() != 2 or hist.dtype != torch.int64 or not hist.is_contiguous():
+        raise RuntimeError(f"session_graph: hist must be a contiguous int64 [B, L] tensor, got {hist.dtype} {tuple(hist.shape)}")
+    _req(hist, torch.int64, "hist")
+    B, L = hist.shape
+    dev = hist.device
+    nodes = _new((B, L), torch.int64, dev)
+    alias, indeg, outdeg = (_new((B, L), torch.int32, dev) for _ in range(3))
+    count = _new((B,), torch.int32, dev)
+    with _Timed("session_graph", f"{B}x{L}", 8 * B * L + 20 * B * L):
+        _check(lib().rp_session_graph(hist.data_ptr(), B, L, nodes.data_ptr(), alias.data_ptr(), count.data_ptr(), indeg.data_ptr(),
+                                      outdeg.data_ptr(), _stream()), "rp_session_graph")
+    return nodes, alias, count, indeg, outdeg
+
+
+def ggnn_geometry() -> dict:
+    v = [_i32(0) for _ in range(4)]
+    _check(lib().rp_ggnn_geometry(*[C.byref(x) for x in v]), "rp_ggnn_geometry")
+    return dict(zip(("max_d", "max_l", "rows_per_workgroup", "lds_bytes"), (x.value for x in v)))
+
+
+def ggnn_fits(L: int, D: int) -> bool:
+    return bool(lib().rp_ggnn_fits(L, D))
+
+
+def _ggnn_args(h, alias, params):
+    """params: W_in, b_in, W_out, b_out, W_ih, b_ih, W_hh, b_hh"""
+    if h.dim() != 3:
+        raise RuntimeError(f"ggnn_cell: h must be [B, L, D], got {tuple(h.shape)}")
+    B, L, D = h.shape
+    if h.dtype != torch.float32 or not h.is_contiguous():
+        raise RuntimeError("ggnn_cell: h must be a contiguous float32 tensor")
+    if alias.dtype != torch.int32 or tuple(alias.shape) != (B, L) or not alias.is_contiguous():
+        raise RuntimeError(f"ggnn_cell: alias must be a contiguous int32 [{B}, {L}] tensor")
+    shapes = [(D, D), (D,), (D, D), (D,), (3 * D, 2 * D), (3 * D,), (3 * D, D), (3 * D,)]
+    if len(params) != 8 or any(tuple(p.shape) != s for p, s in zip(params, shapes)):
+        raise RuntimeError(f"ggnn_cell: params must have the shapes {shapes}, got {[tuple(p.shape) for p in params]}")
+    named = [(f"param{i}", p) for i, p in enumerate(params)]
+    _params(named)
+    _req(h, torch.float32, "h")
+    _req(alias, torch.int32, "alias")
+    for name, t in named:
+        _req(t, torch.float32, name)
+    return B, L, D
+
+
+def _ptrs8(ts):
+    return (C.c_void_p * 8)(*[t.data_ptr() for t in ts])
+
+
+def ggnn_cell_fwd(h, alias, params, final: bool):
+    """rp_ggnn_cell_fwd, one step -> h' [B, L, D], or with final (seq_hidden [B, L, D], ht [B, D]): the alias read-back"""
+    B, L, D = _ggnn_args(h, alias, params)
+    ws, nbytes = _workspace("ggnn_cell", B, L, D, 0, device=h.device)
+    if final:
+        outs = (_new((B, L, D), torch.float32, h.device), _new((B, D), torch.float32, h.device))
+        ptrs = (None, outs[0].data_ptr(), outs[1].data_ptr())
+    else:
+        outs = _new((B, L, D), torch.float32, h.device)
+        ptrs = (outs.data_ptr(), None, None)
+    with _Timed("ggnn_cell_fwd", f"{B}x{L}x{D}", 8 * B * L * D + 4 * 11 * D * D, 2 * B * L * 11 * D * D):
+        _check(lib().rp_ggnn_cell_fwd(h.data_ptr(), alias.data_ptr(), B, L, D, _ptrs8(params), *ptrs, ws.data_ptr(), nbytes,
+                                      _stream()), "rp_ggnn_cell_fwd")
+    return outs
+
+
+def ggnn_cell_bwd(h, alias, params, dhout=None, dseq=None, dht=None):
+    """rp_ggnn_cell_bwd -> (dh [B, L, D], the 8 gradients in the order of params); each arriving gradient may be None"""
+    B, L, D = _ggnn_args(h, alias, params)
+    for name, t, shape in (("dhout", dhout, (B, L, D)), ("dseq", dseq, (B, L, D)), ("dht", dht, (B, D))):
+        if t is not None:
+            if tuple(t.shape) != shape or not t.is_contiguous():
+                raise RuntimeError(f"ggnn_cell_bwd: {name} must be a contiguous {shape} tensor, got {tuple(t.shape)}")
+            _req(t, torch.float32, name)
+    ws, nbytes = _workspace("ggnn_cell", B, L, D, 1, device=h.device)
+    dh = _new((B, L, D), torch.float32, h.device)
+    grads = [_new(tuple(p.shape), torch.float32, h.device) for p in params]
+    with _Timed("ggnn_cell_bwd", f"{B}x{L}x{D}", nbytes + 16 * B * L * D, 6 * B * L * 11 * D * D):
+        _check(lib().rp_ggnn_cell_bwd(h.data_ptr(), alias.data_ptr(), _ptr(dhout), _ptr(dseq), _ptr(dht), B, L, D, _ptrs8(params),
+                                      dh.data_ptr(), _ptrs8(grads), ws.data_ptr(), nbytes, _stream()), "rp_ggnn_cell_bwd")
+    return dh, grads
+
+
+def l2norm_fwd(x):
+    """rp_l2norm_fwd: x [M, D] contiguous -> x / max(|x|_2, 1e-12) per row"""
+    _req(x, torch.float32, "x")
+    if x.dim() != 2 or not x.is_contiguous():
+        raise RuntimeError(f"l2norm_fwd: x must be a contiguous 2-D tensor, got {tuple(x.shape)}")
+    M, D = x.shape
+    y = _new((M, D), torch.float32, x.device)
+    with _Timed("l2norm_fwd", f"{M}x{D}", 8 * M * D):
+        _check(lib().rp_l2norm_fwd(x.data_ptr(), y.data_ptr(), M, D, _stream()), "rp_l2norm_fwd")
+    return y
+
+
+def l2norm_bwd(x, dy):
+    """rp_l2norm_bwd -> dx from the saved input and dy (both [M, D] contiguous)"""
+    _req(x, torch.float32, "x")
+    _req(dy, torch.float32, "dy")
+    if x.dim() != 2 or x.shape != dy.shape or not x.is_contiguous() or not dy.is_contiguous():
+        raise RuntimeError(f"l2norm_bwd: x and dy must be contiguous [M, D] tensors, got {tuple(x.shape)}, {tuple(dy.shape)}")
+    M, D = x.shape
+    dx = _new((M, D), torch.float32, x.device)
+    with _Timed("l2norm_bwd", f"{M}x{D}", 12 * M * D):
+        _check(lib().rp_l2norm_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), M, D, _stream()), "rp_l2norm_bwd")
+    return dx

@@ -10,10 +10,11 @@ from .sequence import MaskedAveragePooling, MaskedSumPooling, KMaxPooling, GRU4R
 from .multi_interest import CapsuleNetwork
 from .transformer import FeedForward, TransformerLayer, TransformerEncoder
 from .conv import NextItNetLayer, ResBlockOneMasked, ResBlockTwoMasked, MaskedConv1d, LayerNorm
+from .graph import SRGNNConv, SRGNNCell
 
 __all__ = ["Dice", "get_activation", "EmbeddingLayer", "MLP", "LR_Layer", "InnerProductLayer", "FM_Layer",
            "CrossInteractionLayer", "CrossNet", "CompressedInteractionNet", "MaskBlock", "GeneralizedInteractionNet",
            "GeneralizedInteraction", "BilinearInteractionLayer", "SENET_Layer", "ScaledDotProductAttention",
            "MultiHeadAttention", "MultiHeadSelfAttention", "MaskedAveragePooling", "MaskedSumPooling", "KMaxPooling",
            "GRU4RecEncoder", "CapsuleNetwork", "FeedForward", "TransformerLayer", "TransformerEncoder", "NextItNetLayer",
-           "ResBlockOneMasked", "ResBlockTwoMasked", "MaskedConv1d", "LayerNorm"]
+           "ResBlockOneMasked", "ResBlockTwoMasked", "MaskedConv1d", "LayerNorm", "SRGNNConv", "SRGNNCell"]

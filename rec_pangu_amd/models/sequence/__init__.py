@@ -5,6 +5,9 @@ from .mind import MIND  # noqa: F401
 from .comirec import ComirecDR  # noqa: F401
 from .sasrec import SASRec  # noqa: F401
 from .nextitnet import NextItNet  # noqa: F401
+from .srgnn import SRGNN  # noqa: F401
+from .niser import NISER  # noqa: F401
+from .gcsan import GCSAN  # noqa: F401
 
-# (MIND, ComirecDR, SASRec and NextItNet are importable from here; __all__ keeps the list tests/test_gru_host.py pins)
+# (MIND, ComirecDR, SASRec, NextItNet, SRGNN, NISER and GCSAN are importable from here; __all__ keeps the list tests/test_gru_host.py pins)
 __all__ = ["YotubeDNN", "GRU4Rec", "NARM"]
