@@ -1375,6 +1375,42 @@ int rp_ggnn_cell_bwd(const float *H, const int32_t *alias, const float *dHout, c
 int rp_l2norm_fwd(const float *x, float *y, int64_t M, int D, rp_stream_t stream);
 int rp_l2norm_bwd(const float *x, const float *dy, float *dx, int64_t M, int D, rp_stream_t stream);
 
+/* ---- sequence recall: two-layer additive attention + pooling of the same rows (csrc/attn_pool.hip) ---------------------------
+ * replaces STAMPLayer's attention (rec_pangu/models/layers/sequence.py:131-137) and MultiInterestSelfAttention.forward
+ * (rec_pangu/models/layers/multi_interest.py:37-51) with their autograd.  X [B, L, D], valid [B, L] of 0 / 1, W1 [D, Dh],
+ * W2 [Dh, K], c [B, Dh] or NULL:
+ *     S[b, l, k] = sum_h W2[h, k] act((X[b, l, :] . W1)[h] + c[b, h])               act: RP_ACT_SIGMOID or RP_ACT_TANH
+ *     norm RP_ATTN_POOL_MASK:    A = S valid; a sample without a valid position gives out = 0
+ *     norm RP_ATTN_POOL_SOFTMAX: the score of a position with valid = 0 is the CONSTANT -1e9 (no gradient passes to S
+ *                                there), then softmax over all L positions with max subtraction: a masked position has
+ *                                weight exactly 0 unless the sample has no valid position, which pools uniformly
+ *     out[b, k, :] = sum_l A[b, l, k] X[b, l, :]                     (rows at valid = 0 are read as they are)
+ * rp_attn_pool_fwd writes out [B, K, D] and A [B, L, K]; A is all the backward needs besides the inputs: the hidden
+ *   tensor [B, L, Dh] is never written.  rp_attn_pool_bwd recomputes it 32 columns at a time and WRITES dX [B, L, D],
+ *   dW1 [D, Dh], dW2 [Dh, K] and, with c, dc [B, Dh] (dc and c: both or neither).  dW1 is one rp_linear_wgrad over the
+ *   pre-activation gradients stacked in the workspace (transient, 4 B L Dhs bytes), dW2 goes through per-workgroup slabs
+ *   added in workgroup order.  No float atomics; bit-identical runs.
+ * Launches, whatever B: forward 2 (padded weight copy + the kernel); backward 3 + rp_linear_wgrad's.
+ * Limits (rp_attn_pool_fits: 1 inside, 0 outside; rp_attn_pool_geometry): 1 <= D <= max_d (128), 1 <= Dh <= max_dh (512),
+ *   1 <= K <= max_k (8), 1 <= L <= max_l (64), B L < 2^29; a workgroup takes floor(rows_per_workgroup / L) samples; its tiles
+ *   must fit lds_bytes.  Outside, another act / norm, a null pointer or a workspace that is too small: RP_ERR_ARG, nothing
+ *   is launched.
+ * Workspace (16-byte aligned), A(x) = x rounded up to 256, p(x) = x rounded up to 32, Dhs = Dh rounded up to 4, Kb = Dhs
+ *   rounded up to 8, n = ceil(B / floor(64 / L)) groups of samples walked by G = ceil(n / ceil(n / 1024)) workgroups:
+ *   forward A(4 p(Dh) p(D)); backward that + A(4 p(D) Kb) + A(4 B L Dhs) + A(4 G Dh K)
+ *   + A(rp_linear_wgrad_workspace_bytes(B L, D, Dh)). */
+#define RP_ATTN_POOL_MASK 0
+#define RP_ATTN_POOL_SOFTMAX 1
+int rp_attn_pool_geometry(int *max_d, int *max_dh, int *max_k, int *max_l, int *rows_per_workgroup, int *lds_bytes);
+int rp_attn_pool_fits(int L, int D, int Dh, int K);
+int rp_attn_pool_workspace_bytes(int64_t B, int L, int D, int Dh, int K, int backward, size_t *bytes);
+int rp_attn_pool_fwd(const float *X, const float *valid, const float *W1, const float *W2, const float *c, int64_t B, int L,
+                     int D, int Dh, int K, int act, int norm, float *out, float *A, void *workspace, size_t workspace_bytes,
+                     rp_stream_t stream);
+int rp_attn_pool_bwd(const float *X, const float *valid, const float *W1, const float *W2, const float *c, const float *A,
+                     const float *dout, int64_t B, int L, int D, int Dh, int K, int act, int norm, float *dX, float *dW1,
+                     float *dW2, float *dc, void *workspace, size_t workspace_bytes, rp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

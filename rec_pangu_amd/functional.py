@@ -2737,3 +2737,75 @@ def l2_normalize(x: torch.Tensor, eps: float = 1e-12):
         nrm = x.norm(dim=-1, keepdim=True)
         return x * torch.where(nrm > 0, 1.0 / nrm.clamp_min(eps), torch.zeros_like(nrm))
     return _L2Normalize.apply(x.reshape(-1, x.shape[-1])).reshape(x.shape)
+
+
+# ----------------------------------------------------------------------------------------------
+# sequence recall: two-layer additive attention over the history's rows + pooling of those rows — STAMPLayer's attention
+# (models/layers/sequence.py:131-137) and MultiInterestSelfAttention (models/layers/multi_interest.py:37-51) as ONE autograd
+# node (csrc/attn_pool.hip).  Saved between forward and backward: the inputs and the weights A [B, L, K];
+# the hidden tensor [B, L, Dh] exists on neither side.
+# ----------------------------------------------------------------------------------------------
+_ATTN_POOL_ACTS = {"sigmoid": ACT_SIGMOID, "tanh": ACT_TANH}
+_ATTN_POOL_NORMS = {"mask": hip.ATTN_POOL_MASK, "softmax": hip.ATTN_POOL_SOFTMAX}
+
+
+def attention_pool_reference(x, w1, w2, valid, bias=None, act: str = "tanh", norm: str = "softmax", return_weights: bool = False):
+    """attention_pool in torch ops (any device and dtype): materialises the hidden tensor [B, L, Dh].  The score of a
+    position with valid = 0 is the constant -1e9 under norm = "softmax" (what the reference's fp32 `S + -1e9` rounds to
+    for |S| < 32), so no gradient passes to S there."""
+    if act not in _ATTN_POOL_ACTS or norm not in _ATTN_POOL_NORMS:
+        raise ValueError(f"attention_pool: act must be one of {sorted(_ATTN_POOL_ACTS)} and norm of {sorted(_ATTN_POOL_NORMS)}")
+    pre = torch.matmul(x, w1)
+    if bias is not None:
+        pre = pre + bias.unsqueeze(1)
+    hidden = torch.sigmoid(pre) if act == "sigmoid" else torch.tanh(pre)
+    s = torch.matmul(hidden, w2)  # [B, L, K]
+    v = valid.to(x.dtype).unsqueeze(-1)
+    if norm == "mask":
+        a = s * v
+    else:
+        a = torch.softmax(torch.where(v != 0, s, torch.full_like(s, -1e9)), dim=1)
+    out = torch.matmul(a.transpose(1, 2), x)
+    return (out, a) if return_weights else out
+
+
+class _AttentionPool(torch.autograd.Function):
+    """inputs: x, valid, w1, w2, bias | None, act, norm; saved: those tensors and A"""
+
+    @staticmethod
+    def forward(ctx, x, valid, w1, w2, bias, act: int, norm: int):
+        x, valid, w1, w2 = x.contiguous(), valid.contiguous(), w1.contiguous(), w2.contiguous()
+        bias = None if bias is None else bias.contiguous()
+        out, A = hip.attn_pool_fwd(x, valid, w1, w2, bias, act, norm)
+        ctx.cfg = (act, norm, bias is not None)
+        ctx.save_for_backward(x, valid, w1, w2, A, *(() if bias is None else (bias,)))
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        act, norm, has_bias = ctx.cfg
+        x, valid, w1, w2, A, *rest = ctx.saved_tensors
+        bias = rest[0] if has_bias else None
+        dx, dw1, dw2, dc = hip.attn_pool_bwd(x, valid, w1, w2, bias, A, dout.contiguous(), act, norm)
+        return dx, None, dw1, dw2, dc, None, None
+
+
+def attention_pool(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, valid: torch.Tensor, bias=None, act: str = "tanh",
+                   norm: str = "softmax"):
+    """out[b, k, :] = sum_l A[b, l, k] x[b, l, :] with S = act(x w1 + bias[:, None]) w2 and A = S valid (norm "mask") or the
+    softmax over l of (valid ? S : -1e9) (norm "softmax"): x [B, L, D], w1 [D, Dh], w2 [Dh, K], valid [B, L] of 0 / 1 (any
+    dtype), bias [B, Dh] or None, act "sigmoid" | "tanh" -> [B, K, D].  Rows of x at valid = 0 are read as they are.  Under
+    "mask" a sample without a valid position gives zeros; under "softmax" it pools uniformly over all L rows (the
+    reference's behaviour) and passes no gradient to the scores.  One rp_attn_pool_fwd / _bwd per call on the HIP device
+    inside the kernel's limits; attention_pool_reference on CPU tensors and, counted, outside the limits."""
+    if act not in _ATTN_POOL_ACTS or norm not in _ATTN_POOL_NORMS:
+        raise ValueError(f"attention_pool: act must be one of {sorted(_ATTN_POOL_ACTS)} and norm of {sorted(_ATTN_POOL_NORMS)}")
+    if not x.is_cuda:
+        return attention_pool_reference(x, w1, w2, valid, bias, act, norm)
+    B, L, D = x.shape
+    Dh, K = w2.shape
+    if x.dtype != torch.float32 or not hip.attn_pool_fits(L, D, Dh, K):
+        hip.note_torch_path(f"attention_pool at L={L}, D={D}, Dh={Dh}, K={K}, {x.dtype} (the kernel takes fp32 inside "
+                            f"{hip.attn_pool_geometry()})")
+        return attention_pool_reference(x, w1, w2, valid, bias, act, norm)
+    return _AttentionPool.apply(x, valid.to(torch.float32), w1, w2, bias, _ATTN_POOL_ACTS[act], _ATTN_POOL_NORMS[norm])

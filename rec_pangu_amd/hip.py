@@ -3560,3 +3560,65 @@ def l2norm_bwd(x, dy):
     with _Timed("l2norm_bwd", f"{M}x{D}", 12 * M * D):
         _check(lib().rp_l2norm_bwd(x.data_ptr(), dy.data_ptr(), dx.data_ptr(), M, D, _stream()), "rp_l2norm_bwd")
     return dx
+
+
+# ---- sequence recall: two-layer additive attention + pooling of the same rows (csrc/attn_pool.hip) ---------------------------
+ATTN_POOL_MASK, ATTN_POOL_SOFTMAX = _RP["RP_ATTN_POOL_MASK"], _RP["RP_ATTN_POOL_SOFTMAX"]
+
+
+def attn_pool_geometry() -> dict:
+    v = [_i32(0) for _ in range(6)]
+    _check(lib().rp_attn_pool_geometry(*[C.byref(x) for x in v]), "rp_attn_pool_geometry")
+    return dict(zip(("max_d", "max_dh", "max_k", "max_l", "rows_per_workgroup", "lds_bytes"), (x.value for x in v)))
+
+
+def attn_pool_fits(L: int, D: int, Dh: int, K: int) -> bool:
+    return bool(lib().rp_attn_pool_fits(L, D, Dh, K))
+
+
+def _attn_pool_args(x, valid, w1, w2, c, act, norm):
+    if x.dim() != 3:
+        raise RuntimeError(f"attn_pool: x must be [B, L, D], got {tuple(x.shape)}")
+    B, L, D = x.shape
+    if w1.dim() != 2 or w2.dim() != 2 or w1.shape[0] != D or w2.shape[0] != w1.shape[1]:
+        raise RuntimeError(f"attn_pool: w1 must be [{D}, Dh] and w2 [Dh, K], got {tuple(w1.shape)}, {tuple(w2.shape)}")
+    Dh, K = w2.shape
+    if tuple(valid.shape) != (B, L):
+        raise RuntimeError(f"attn_pool: valid must be [{B}, {L}], got {tuple(valid.shape)}")
+    if c is not None and tuple(c.shape) != (B, Dh):
+        raise RuntimeError(f"attn_pool: the bias must be [{B}, {Dh}], got {tuple(c.shape)}")
+    if act not in (ACT_SIGMOID, ACT_TANH) or norm not in (ATTN_POOL_MASK, ATTN_POOL_SOFTMAX):
+        raise RuntimeError(f"attn_pool: act must be ACT_SIGMOID / ACT_TANH and norm ATTN_POOL_MASK / _SOFTMAX, got {act}, {norm}")
+    named = [("x", x), ("valid", valid), ("w1", w1), ("w2", w2)] + ([("bias", c)] if c is not None else [])
+    _params(named)
+    for name, t in named:
+        _req(t, torch.float32, name)
+    return B, L, D, Dh, K
+
+
+def attn_pool_fwd(x, valid, w1, w2, c, act: int, norm: int):
+    """rp_attn_pool_fwd -> (out [B, K, D], A [B, L, K]); c [B, Dh] or None"""
+    B, L, D, Dh, K = _attn_pool_args(x, valid, w1, w2, c, act, norm)
+    ws, nbytes = _workspace("attn_pool", B, L, D, Dh, K, 0, device=x.device)
+    out, A = _new((B, K, D), torch.float32, x.device), _new((B, L, K), torch.float32, x.device)
+    with _Timed("attn_pool_fwd", f"{B}x{L}x{D}h{Dh}k{K}", 4 * (B * L * D + B * K * D + B * L * K + D * Dh), 2 * B * L * Dh * (D + K) + 2 * B * L * K * D):
+        _check(lib().rp_attn_pool_fwd(x.data_ptr(), valid.data_ptr(), w1.data_ptr(), w2.data_ptr(), _ptr(c), B, L, D, Dh, K, act, norm,
+                                      out.data_ptr(), A.data_ptr(), ws.data_ptr(), nbytes, _stream()), "rp_attn_pool_fwd")
+    return out, A
+
+
+def attn_pool_bwd(x, valid, w1, w2, c, A, dout, act: int, norm: int):
+    """rp_attn_pool_bwd -> (dx [B, L, D], dw1 [D, Dh], dw2 [Dh, K], dc [B, Dh] or None) from the inputs, the kept A and dout"""
+    B, L, D, Dh, K = _attn_pool_args(x, valid, w1, w2, c, act, norm)
+    for name, t, shape in (("A", A, (B, L, K)), ("dout", dout, (B, K, D))):
+        if tuple(t.shape) != shape or not t.is_contiguous():
+            raise RuntimeError(f"attn_pool_bwd: {name} must be a contiguous {shape} tensor, got {tuple(t.shape)}")
+        _req(t, torch.float32, name)
+    ws, nbytes = _workspace("attn_pool", B, L, D, Dh, K, 1, device=x.device)
+    dx, dw1, dw2 = (_new(s, torch.float32, x.device) for s in ((B, L, D), (D, Dh), (Dh, K)))
+    dc = None if c is None else _new((B, Dh), torch.float32, x.device)
+    with _Timed("attn_pool_bwd", f"{B}x{L}x{D}h{Dh}k{K}", nbytes + 4 * (2 * B * L * D + B * K * D + B * L * K), 6 * B * L * Dh * (D + K) + 4 * B * L * K * D):
+        _check(lib().rp_attn_pool_bwd(x.data_ptr(), valid.data_ptr(), w1.data_ptr(), w2.data_ptr(), _ptr(c), A.data_ptr(),
+                                      dout.data_ptr(), B, L, D, Dh, K, act, norm, dx.data_ptr(), dw1.data_ptr(), dw2.data_ptr(),
+                                      _ptr(dc), ws.data_ptr(), nbytes, _stream()), "rp_attn_pool_bwd")
+    return dx, dw1, dw2, dc

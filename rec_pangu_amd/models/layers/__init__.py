@@ -6,8 +6,8 @@ from .interaction import (InnerProductLayer, FM_Layer, CrossInteractionLayer, Cr
                           CompressedInteractionNet, MaskBlock, GeneralizedInteractionNet,
                           GeneralizedInteraction, BilinearInteractionLayer, SENET_Layer)
 from .attention import ScaledDotProductAttention, MultiHeadAttention, MultiHeadSelfAttention
-from .sequence import MaskedAveragePooling, MaskedSumPooling, KMaxPooling, GRU4RecEncoder
-from .multi_interest import CapsuleNetwork
+from .sequence import MaskedAveragePooling, MaskedSumPooling, KMaxPooling, GRU4RecEncoder, STAMPLayer
+from .multi_interest import CapsuleNetwork, MultiInterestSelfAttention
 from .transformer import FeedForward, TransformerLayer, TransformerEncoder
 from .conv import NextItNetLayer, ResBlockOneMasked, ResBlockTwoMasked, MaskedConv1d, LayerNorm
 from .graph import SRGNNConv, SRGNNCell
@@ -17,4 +17,5 @@ __all__ = ["Dice", "get_activation", "EmbeddingLayer", "MLP", "LR_Layer", "Inner
            "GeneralizedInteraction", "BilinearInteractionLayer", "SENET_Layer", "ScaledDotProductAttention",
            "MultiHeadAttention", "MultiHeadSelfAttention", "MaskedAveragePooling", "MaskedSumPooling", "KMaxPooling",
            "GRU4RecEncoder", "CapsuleNetwork", "FeedForward", "TransformerLayer", "TransformerEncoder", "NextItNetLayer",
-           "ResBlockOneMasked", "ResBlockTwoMasked", "MaskedConv1d", "LayerNorm", "SRGNNConv", "SRGNNCell"]
+           "ResBlockOneMasked", "ResBlockTwoMasked", "MaskedConv1d", "LayerNorm", "SRGNNConv", "SRGNNCell", "STAMPLayer",
+           "MultiInterestSelfAttention"]

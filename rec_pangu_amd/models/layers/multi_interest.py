@@ -1,4 +1,5 @@
-"""CapsuleNetwork — drop-in for rec_pangu/models/layers/multi_interest.py:56-161: the multi-interest encoder of MIND
+"""MultiInterestSelfAttention — drop-in for rec_pangu/models/layers/multi_interest.py:11-53, ComirecSA's encoder (below) — and
+CapsuleNetwork — drop-in for rec_pangu/models/layers/multi_interest.py:56-161: the multi-interest encoder of MIND
 (bilinear_type 0) and ComirecDR (bilinear_type 2).  The same constructor, attributes and state_dict keys (`relu.0.weight`
 exists even when relu_layer is off; `linear.weight` for types 0 / 1, `w` [1, L, K D, D] for type 2).
 
@@ -18,6 +19,36 @@ import torch
 from torch import nn
 
 from ... import functional as Fh
+
+
+class MultiInterestSelfAttention(nn.Module):
+    """A = softmax over positions of tanh(x W1) W2 (masked positions at -1e9), interests = A^T x  [B, K, D].  The same
+    constructor and parameters W1 [D, d], W2 [d, K], W3 [D, D] in that order, drawn with torch.rand as the reference does
+    (the generator's stream); W3 exists, is initialised and is in the state_dict, and nothing reads it: its grad stays None.
+    The whole forward is one Fh.attention_pool node (csrc/attn_pool.hip): on the HIP device the hidden tensor
+    [B, L, d] (four times the input at the default d = 4 D) exists on neither side."""
+
+    def __init__(self, embedding_dim: int, num_attention_heads: int, d: int = None) -> None:
+        super(MultiInterestSelfAttention, self).__init__()
+        self.embedding_dim = embedding_dim
+        self.num_attention_heads = num_attention_heads
+        if d is None:
+            self.d = self.embedding_dim * 4
+        else:
+            self.d = d
+
+        self.W1 = nn.Parameter(torch.rand(self.embedding_dim, self.d), requires_grad=True)
+        self.W2 = nn.Parameter(torch.rand(self.d, self.num_attention_heads), requires_grad=True)
+        self.W3 = nn.Parameter(torch.rand(self.embedding_dim, self.embedding_dim), requires_grad=True)
+
+    def forward(self, sequence_embeddings: torch.Tensor, mask: torch.Tensor = None) -> torch.Tensor:
+        """sequence_embeddings [B, L, D]; mask [B, L, 1] or [B, L] of 0 / 1, None: every position counts"""
+        B, L, _ = sequence_embeddings.shape
+        if mask is None:
+            valid = torch.ones(B, L, dtype=sequence_embeddings.dtype, device=sequence_embeddings.device)
+        else:
+            valid = mask.reshape(B, L)
+        return Fh.attention_pool(sequence_embeddings, self.W1, self.W2, valid, act="tanh", norm="softmax")
 
 
 class CapsuleNetwork(nn.Module):

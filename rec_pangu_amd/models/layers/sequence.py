@@ -1,5 +1,5 @@
 """Sequence poolings of the reference (rec_pangu/models/layers/sequence.py:13-59), its KMaxPooling (:63-86) and its
-GRU4RecEncoder (:231-251) as drop-in modules.
+GRU4RecEncoder (:231-251) and its STAMPLayer (:89-144) as drop-in modules.
 
 On a HIP tensor they run rp_seq_pool_fwd / _bwd (one read of the [B, L, D] tensor); on the CPU the reference's own
 formulas.  When the pooled tensor comes straight from a `_seq` lookup, `EmbeddingLayer.lookup_pooled` fuses lookup and
@@ -72,3 +72,58 @@ class GRU4RecEncoder(nn.Module):
         if hidden.is_cuda:
             return Fh.linear_act(hidden, self.out.weight)
         return self.out(hidden)
+
+
+class STAMPLayer(nn.Module):
+    """STAMP's readout — sequence.py:89-144, the same constructor and the reference's six Linears under the same names in
+    the same creation order.  With valid = (position < lens):
+
+        m_s = sum_l valid x_l / lens,  x_t = x[lens - 1]
+        alpha_l = valid attn_e(sigmoid(attn_i(x_l) + attn_t(x_t) + attn_s(m_s))),  m_a = sum_l alpha_l x_l
+        sr = fc_a(m_a) * fc_t(x_t)
+
+    forward(emb_seqs, lens) as in the reference (feat_drop applied here); forward(emb_seqs, lens, m_s=...) takes the mean
+    from the caller and applies no dropout (STAMP's device path draws the rows' dropout itself and reads the mean off the
+    table when there is none).  On the HIP device attn_t / attn_s / fc_a / fc_t run on the library's Linear, attn_i and
+    attn_e inside ONE Fh.attention_pool node (csrc/attn_pool.hip) whose mask mode gives the rows at
+    valid = 0 weight 0: the reference's masked_fill of the rows needs no copy.
+
+    Deliberate difference: lens = 0 gives m_s = x_t = 0 and m_a = 0, hence sr = fc_a.bias * fc_t.bias, and no gradient
+    reaches the rows (the reference divides by zero: NaN)."""
+
+    def __init__(self, embedding_dim: int, feat_drop: float = 0.0):
+        super().__init__()
+        self.feat_drop = nn.Dropout(feat_drop) if feat_drop > 0 else None
+        self.fc_a = nn.Linear(embedding_dim, embedding_dim, bias=True)
+        self.fc_t = nn.Linear(embedding_dim, embedding_dim, bias=True)
+        self.attn_i = nn.Linear(embedding_dim, embedding_dim, bias=False)
+        self.attn_t = nn.Linear(embedding_dim, embedding_dim, bias=True)
+        self.attn_s = nn.Linear(embedding_dim, embedding_dim, bias=False)
+        self.attn_e = nn.Linear(embedding_dim, 1, bias=False)
+
+    def forward(self, emb_seqs: torch.Tensor, lens: torch.Tensor, m_s: torch.Tensor = None) -> torch.Tensor:
+        on_hip = emb_seqs.is_cuda
+        if m_s is None and self.feat_drop is not None:
+            if on_hip:
+                if self.training:
+                    emb_seqs = Fh.dropout(emb_seqs, self.feat_drop.p)
+            else:
+                emb_seqs = self.feat_drop(emb_seqs)
+        batch_size, max_len, _ = emb_seqs.size()
+        valid = (torch.arange(max_len, device=lens.device).unsqueeze(0) < lens.unsqueeze(-1)).to(emb_seqs.dtype)
+        some = (lens > 0).to(emb_seqs.dtype).unsqueeze(-1)
+        if on_hip:
+            if m_s is None:
+                m_s = Fh.seq_pool(emb_seqs * valid.unsqueeze(-1), "sum") / lens.clamp(min=1).unsqueeze(-1)
+            xt = Fh.seq_take(emb_seqs, lens.to(torch.int64) - 1)  # (a zero row where lens = 0)
+            c = Fh.linear_act(xt, self.attn_t.weight, self.attn_t.bias) + Fh.linear_act(m_s, self.attn_s.weight)
+        else:
+            if m_s is None:
+                m_s = (emb_seqs * valid.unsqueeze(-1)).sum(dim=1) / lens.clamp(min=1).unsqueeze(-1)
+            xt = emb_seqs[torch.arange(batch_size), (lens - 1).clamp(min=0)] * some
+            c = self.attn_t(xt) + self.attn_s(m_s)
+        ma = Fh.attention_pool(emb_seqs, self.attn_i.weight.t(), self.attn_e.weight.t(), valid, bias=c, act="sigmoid",
+                               norm="mask").squeeze(1)
+        if on_hip:
+            return Fh.linear_act(ma, self.fc_a.weight, self.fc_a.bias) * Fh.linear_act(xt, self.fc_t.weight, self.fc_t.bias)
+        return self.fc_a(ma) * self.fc_t(xt)

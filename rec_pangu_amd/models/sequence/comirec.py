@@ -1,6 +1,14 @@
-"""ComirecDR — drop-in for rec_pangu/models/sequence/comirec.py:67-118 (config key `K` is required).  ComirecSA pools by
-attention, not by routing, and is not here yet; it will share the readout.
+"""ComirecSA and ComirecDR — drop-ins for rec_pangu/models/sequence/comirec.py:12-64 and :67-118 (config key `K` is required).
 
+ComirecSA:
+    interests = MultiInterestSelfAttention(D, K)(item_emb(hist), hist_mask_list)        user_emb [B, K, D]
+              = softmax_l(tanh(x W1) W2, masked positions at -1e9)^T x
+    training:   the hard readout and the loss below
+On the HIP device: Fh.hist_rows -> multi_interest_sa as ONE Fh.attention_pool node (csrc/attn_pool.hip; the
+hidden tensor [B, L, 4 D] exists on neither side) -> Fh.interest_pick -> calculate_loss.  A row without history pools
+uniformly over all L rows, as the reference's; its masked scores are constants, so it passes no gradient to W1 / W2.
+
+ComirecDR:
     interests = CapsuleNetwork(bilinear_type=2)(item_emb(hist), hist_mask_list)        user_emb [B, K, D]
     training:   best[b] = interests[b, argmax_k interests[b, k] . item_emb(target[b])],  loss = full softmax CE of best
 On the HIP device: Fh.hist_rows -> Fh.capsule_project (every position its own [K D, D] matrix, one launch for all of them;
@@ -13,7 +21,20 @@ Deliberate differences, the same three as MIND's (models/sequence/mind.py):
     it (the CPU generator's stream and the fixtures match the reference), the device path does not;
   - a history whose second dimension is not max_length raises ValueError on both paths.
 """
-from .mind import CapsuleRecallModel
+from .mind import CapsuleRecallModel, MultiInterestRecallModel
+from ..layers.multi_interest import MultiInterestSelfAttention
+
+
+class ComirecSA(MultiInterestRecallModel):
+    def __init__(self, enc_dict, config):
+        super(ComirecSA, self).__init__(enc_dict, config)
+
+        self.multi_interest_sa = MultiInterestSelfAttention(embedding_dim=self.embedding_dim,
+                                                            num_attention_heads=self.config['K'])
+        self.reset_parameters()
+
+    def interests(self, seq_emb, mask):
+        return self.multi_interest_sa(seq_emb, mask.unsqueeze(-1).float())
 
 
 class ComirecDR(CapsuleRecallModel):

@@ -23,16 +23,12 @@ from ..base_model import SequenceBaseModel
 from ..layers.multi_interest import CapsuleNetwork
 
 
-class CapsuleRecallModel(SequenceBaseModel):
-    """what MIND and ComirecDR share: a CapsuleNetwork over the history's item rows and the hard readout"""
-    bilinear_type = 0
+class MultiInterestRecallModel(SequenceBaseModel):
+    """what MIND, ComirecDR and ComirecSA share: K interests [B, K, D] from the history's item rows (`interests`, the
+    subclass's encoder) and the hard readout"""
 
-    def __init__(self, enc_dict, config):
-        super(CapsuleRecallModel, self).__init__(enc_dict, config)
-
-        self.capsule = CapsuleNetwork(self.embedding_dim, self.max_length, bilinear_type=self.bilinear_type,
-                                      interest_num=self.config['K'])
-        self.reset_parameters()
+    def interests(self, seq_emb, mask):
+        raise NotImplementedError
 
     def forward(self, data: Dict[str, torch.Tensor], is_training: bool = True):
         item_seq = data['hist_item_list']
@@ -44,7 +40,7 @@ class CapsuleRecallModel(SequenceBaseModel):
         # while training one check covers every launch (they share the device flag): the loss makes it
         check = "deferred" if (is_training or self.check_indices != "sync") else "sync"
         seq_emb = Fh.hist_rows(self.item_emb.weight, item_seq, check_indices=check)  # Batch,Seq,Emb
-        multi_interest_emb = self.capsule(seq_emb, mask, self.device)  # Batch,K,Emb
+        multi_interest_emb = self.interests(seq_emb, mask)  # Batch,K,Emb
         if not is_training:
             return {'user_emb': multi_interest_emb}
         item = data['target_item'].view(-1)
@@ -53,6 +49,21 @@ class CapsuleRecallModel(SequenceBaseModel):
         best_interest_emb = Fh.interest_pick(multi_interest_emb, self.item_emb.weight, item, check_indices="deferred")
         loss = self.calculate_loss(best_interest_emb, item)
         return {'user_emb': multi_interest_emb, 'loss': loss}
+
+
+class CapsuleRecallModel(MultiInterestRecallModel):
+    """MIND and ComirecDR: a CapsuleNetwork over the rows"""
+    bilinear_type = 0
+
+    def __init__(self, enc_dict, config):
+        super(CapsuleRecallModel, self).__init__(enc_dict, config)
+
+        self.capsule = CapsuleNetwork(self.embedding_dim, self.max_length, bilinear_type=self.bilinear_type,
+                                      interest_num=self.config['K'])
+        self.reset_parameters()
+
+    def interests(self, seq_emb, mask):
+        return self.capsule(seq_emb, mask, self.device)
 
 
 class MIND(CapsuleRecallModel):
