@@ -1411,6 +1411,49 @@ int rp_attn_pool_bwd(const float *X, const float *valid, const float *W1, const 
                      const float *dout, int64_t B, int L, int D, int Dh, int K, int act, int norm, float *dX, float *dW1,
                      float *dW2, float *dc, void *workspace, size_t workspace_bytes, rp_stream_t stream);
 
+/* ---- sequence recall: the key-padding (non-causal) mode of the sequence attention core (csrc/seq_attn_keypad.hip) ----------------
+ * the attention of the reference's BERT4RecEncoder (rec_pangu/models/layers/sequence.py:150-186).  Layouts, modes (full,
+ * last-row with qpos, q_compact) and limits are rp_seq_attn_fwd's; the differences: every query row attends to every CONTENT
+ * key (mask[b, j] != 0), whatever its position; a masked key is skipped (probability exactly 0, so its dK and dV rows are
+ * exactly 0) instead of taking an additive score; a sample without a content key gets zero ctx rows, lse 0 and zero
+ * gradients; there is no dropout; the backward takes no ctx (its delta comes from the recomputed probabilities).  One launch each way, nothing of size L x L stored, no float atomics, bit-identical runs.
+ * Outside rp_seq_attn_fits: RP_ERR_ARG, nothing is launched. */
+int rp_seq_attn_keypad_fwd(const float *q, int64_t ldq, int q_compact, const float *kv, int64_t ldkv, const float *mask,
+                           const int64_t *qpos, int64_t B, int L, int heads, int dh, float *ctx, float *lse, rp_stream_t stream);
+int rp_seq_attn_keypad_bwd(const float *q, int64_t ldq, int q_compact, const float *kv, int64_t ldkv, const float *mask,
+                           const int64_t *qpos, const float *dctx, const float *lse, int64_t B, int L, int heads, int dh, float *dq,
+                           int64_t lddq, float *dkv, int64_t lddkv, rp_stream_t stream);
+
+/* ---- sequence recall: the in-batch contrastive loss of CLRec and ContraRec (csrc/contrast.hip) -----------------------------------
+ * replaces, with its autograd, rec_pangu/models/sequence/clrec.py:65-102 and contrarec.py:93-144, which materialise the
+ * [n, m] similarity matrix about seven times.  a [n, lda], b [m, ldb] fp32 rows of D columns, la [n], lb [m] int64 labels,
+ * l_ij = (a_i . b_j) / temperature.  b NULL: the symmetric form (b = a, lb = la, m = n; pass lb NULL or la), the only one
+ * that takes exclude_self.  Per row i, N_i = all j (exclude_self: j != i), P_i = { j in N_i : la[i] == lb[j] }, c_i = |P_i|:
+ *   m_i = max_j l_ij over ALL j,  lse_i = m_i + log(sum_{j in N_i} exp(l_ij - m_i) + 1e-10),
+ *   loss = (scale / n) sum_i -(sum_{j in P_i} (l_ij - lse_i)) / (c_i + 1e-10)          (a row with c_i = 0 adds 0).
+ * rp_contrast_fwd writes loss [1], lse [n] (DOUBLE: a float at |lse| ~ 24 would round away log(sum) of a row whose positive
+ * holds nearly all of its probability) and c [n] (the counts as floats): all the backward needs besides the inputs.
+ * rp_contrast_bwd recomputes p_ij = exp(l_ij - lse_i) tile by tile and WRITES, with g = gloss[0] (device) and
+ *   q_ij = [j in N_i] p_ij c_i / (c_i + 1e-10) - [j in P_i] / (c_i + 1e-10):
+ *   da [n, ldda] = g scale / (n T) sum_j q_ij b_j,  db [m, lddb] = g scale / (n T) sum_i q_ij a_i   (either may be NULL);
+ *   symmetric form: the one result da + db in da (db must be NULL).
+ * No [n, m] tensor in either direction; every sum in a fixed order, no float atomics, bit-identical runs.  Products follow
+ * rp_matmul_products (fp32-faithful by default), as rp_softmax_ce_fwd.
+ * Limits: n, m >= 1, 1 <= D <= max_d (rp_contrast_geometry: ta / tb = rows of a / b per tile, max_d = 128, max_splits of m;
+ *   rp_contrast_fits: 1 inside, 0 outside), temperature > 0; outside, a null pointer or a workspace too small: RP_ERR_ARG,
+ *   nothing is launched.  Workspace: rp_contrast_workspace_bytes(n, m, D) bytes (pass the asymmetric m, or n for the
+ *   symmetric form), 16-byte aligned, one size for both directions. */
+int rp_contrast_fits(int D);
+int rp_contrast_geometry(int *ta, int *tb, int *max_d, int *max_splits);
+int rp_contrast_workspace_bytes(int64_t n, int64_t m, int D, size_t *bytes);
+int rp_contrast_fwd(const float *a, int64_t lda, const float *b, int64_t ldb, const int64_t *la, const int64_t *lb, int64_t n,
+                    int64_t m, int D, float temperature, int exclude_self, float scale, double *lse, float *c, float *loss,
+                    void *workspace, size_t workspace_bytes, rp_stream_t stream);
+int rp_contrast_bwd(const float *a, int64_t lda, const float *b, int64_t ldb, const int64_t *la, const int64_t *lb,
+                    const double *lse, const float *c, const float *gloss, int64_t n, int64_t m, int D, float temperature,
+                    int exclude_self, float scale, float *da, int64_t ldda, float *db, int64_t lddb, void *workspace,
+                    size_t workspace_bytes, rp_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2376,11 +2376,45 @@ def interest_pick(interests: torch.Tensor, item_weight: torch.Tensor, target: to
 # the feed-forward activations the GEMM epilogue lacks (trainformer.py:133-145).  Saved between forward and backward: the
 # projected rows, the mask, the output and one float per (b, head, query); no [B, heads, L, L] tensor exists on the HIP path.
 # ----------------------------------------------------------------------------------------------
-def seq_attention_reference(q, kv, mask, heads: int, keep=None, scale: float = 1.0, qpos=None, compact: bool = False):
+def _seq_attention_keypad_reference(q, kv, mask, heads: int, qpos, compact: bool):
+    """seq_attention_reference's key-padding mode: layers/sequence.py MultiHeadAttention.scaled_dot_product_attention of the
+    reference under masked_fill(mask == 0, -inf), with the maximum subtracted per row (the reference subtracts the maximum
+    of the whole batch tensor: equal unless a row's own maximum lies ~87 below it) and its NaN -> 0 for a sample without a
+    content key written as a guarded division, so that such a sample passes zero gradients instead of NaN."""
+    B, L = mask.shape
+    D = kv.shape[1] // 2
+    dh = D // heads
+    content = (mask != 0).view(B, 1, 1, L)
+    key_layer = kv[:, :D].reshape(B, L, heads, dh).permute(0, 2, 3, 1)
+    value_layer = kv[:, D:].reshape(B, L, heads, dh).permute(0, 2, 1, 3)
+    if qpos is None:
+        query_layer = q.reshape(B, L, heads, dh).permute(0, 2, 1, 3)
+    else:
+        q_rows = q if compact else q.reshape(B, L, -1)[torch.arange(B, device=q.device), qpos.clamp(0, L - 1)]
+        query_layer = q_rows[:, :D].reshape(B, 1, heads, dh).permute(0, 2, 1, 3)
+    scores = (torch.matmul(query_layer, key_layer) / (dh ** 0.5)).masked_fill(~content, float("-inf"))
+    top = scores.detach().max(dim=-1, keepdim=True).values
+    e = torch.exp(scores - torch.where(torch.isinf(top), torch.zeros_like(top), top))
+    den = e.sum(dim=-1, keepdim=True)
+    probs = e / torch.where(den > 0, den, torch.ones_like(den))
+    context_layer = torch.matmul(probs, value_layer).permute(0, 2, 1, 3).contiguous()
+    if qpos is None:
+        return context_layer.view(B * L, D)
+    return context_layer.view(B, D) * (qpos >= 0).to(q.dtype).view(B, 1)
+
+
+def seq_attention_reference(q, kv, mask, heads: int, keep=None, scale: float = 1.0, qpos=None, compact: bool = False,
+                            causal: bool = True):
     """The composed formulation, op for op as the reference's MultiHeadAttention.forward between its projections and `dense`,
     in the dtype of its inputs: q [B L, D] (or, with qpos and compact, [B, D]: one row per
     sample), kv [B L, 2 D] (K | V), mask [B, L] -> ctx [B L, D], or [B, D] with qpos (a zero row where qpos[b] < 0).
-    keep: the dropout decisions [B, heads, L, L] (any dtype; None: no dropout), scale: 1 / (1 - p)."""
+    keep: the dropout decisions [B, heads, L, L] (any dtype; None: no dropout), scale: 1 / (1 - p).
+    causal False: the key-padding mode (every query over every content key, a masked key has probability 0, a sample
+    without a content key gives zero rows); no dropout there."""
+    if not causal:
+        if keep is not None:
+            raise ValueError("seq_attention_reference: the key-padding mode has no dropout")
+        return _seq_attention_keypad_reference(q, kv, mask, heads, qpos, compact)
     B, L = mask.shape
     D = kv.shape[1] // 2
     dh = D // heads
@@ -2413,32 +2447,34 @@ class _SeqAttention(torch.autograd.Function):
     """inputs: rows = the stacked [B L, 3 D] buffer (q is None) or the [B L, 2 D] K | V buffer (q [B, D]: one query per sample)"""
 
     @staticmethod
-    def forward(ctx, rows, q, mask, qpos, heads: int, p: float):
+    def forward(ctx, rows, q, mask, qpos, heads: int, p: float, causal: bool = True):
         rows = _unit_inner(rows)
         stacked = q is None
         D = rows.shape[1] // (3 if stacked else 2)
         qv = rows if stacked else _unit_inner(q)
         kv = rows[:, D:] if stacked else rows
         rng = hip.seq_attn_seed_offset(rows.device) if p > 0.0 else None
-        out, lse = hip.seq_attn_fwd(qv, kv, mask, heads, p, rng, qpos, compact=not stacked)
-        ctx.save_for_backward(rows, None if stacked else qv, mask, qpos, out, lse)
-        ctx.cfg = (heads, p, rng, D)
+        out, lse = hip.seq_attn_fwd(qv, kv, mask, heads, p, rng, qpos, compact=not stacked, causal=causal)
+        # (the key-padding backward forms its delta from the recomputed probabilities: the output is not kept)
+        ctx.save_for_backward(rows, None if stacked else qv, mask, qpos, out if causal else None, lse)
+        ctx.cfg = (heads, p, rng, D, causal)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         rows, q, mask, qpos, out, lse = ctx.saved_tensors
-        heads, p, rng, D = ctx.cfg
+        heads, p, rng, D, causal = ctx.cfg
         if q is None:  # dqkv [B L, 3 D]: dQ | dK | dV, written in place by the one launch
             drows = hip._new((rows.shape[0], 3 * D), torch.float32, rows.device)
-            hip.seq_attn_bwd(rows, rows[:, D:], mask, out, dout.contiguous(), lse, heads, p, rng, qpos, dq=drows, dkv=drows[:, D:])
-            return drows, None, None, None, None, None
-        dq, dkv = hip.seq_attn_bwd(q, rows, mask, out, dout.contiguous(), lse, heads, p, rng, qpos, compact=True)
-        return dkv, dq, None, None, None, None
+            hip.seq_attn_bwd(rows, rows[:, D:], mask, out, dout.contiguous(), lse, heads, p, rng, qpos, dq=drows, dkv=drows[:, D:],
+                             causal=causal)
+            return drows, None, None, None, None, None, None
+        dq, dkv = hip.seq_attn_bwd(q, rows, mask, out, dout.contiguous(), lse, heads, p, rng, qpos, compact=True, causal=causal)
+        return dkv, dq, None, None, None, None, None
 
 
 def seq_attention(qkv: torch.Tensor, mask: torch.Tensor, heads: int, p: float = 0.0, training: bool = False,
-                  qpos: torch.Tensor = None, q: torch.Tensor = None):
+                  qpos: torch.Tensor = None, q: torch.Tensor = None, causal: bool = True):
     """The masked multi-head attention core of the reference's TransformerEncoder on already-projected rows:
     qkv [B L, 3 D] (Q | K | V, biases added, head h at columns [h dh, (h + 1) dh) of each), mask [B, L] (non-zero = content, any
     dtype) -> ctx [B L, D], head-interleaved: softmax(Q K^T / sqrt(dh) + m) V per (b, head) with m = 0 where the key is content
@@ -2448,7 +2484,11 @@ def seq_attention(qkv: torch.Tensor, mask: torch.Tensor, heads: int, p: float = 
     On the HIP device one launch each way (rp_seq_attn_*: nothing of size L x L is stored, the backward recomputes the
     probabilities and regenerates the dropout decisions from one offset of the device generator's Philox stream); outside
     rp_seq_attn_fits (L <= 128, dh <= 64) the composed torch formulation on the device, counted; on CPU tensors the same
-    formulation."""
+    formulation.
+    causal False: the key-padding mode of the reference's BERT4RecEncoder (rp_seq_attn_keypad_*): every query row attends to
+    every content key, a masked key has probability exactly 0 (skipped, no additive score), a sample without a content key
+    gets zero rows and passes zero gradients.  That layer has no dropout on the probabilities: p > 0 while training raises
+    ValueError."""
     if q is not None and qpos is None:
         raise ValueError("seq_attention: q (one query row per sample) needs qpos")
     B, L = mask.shape
@@ -2456,6 +2496,8 @@ def seq_attention(qkv: torch.Tensor, mask: torch.Tensor, heads: int, p: float = 
     if D % heads:
         raise ValueError(f"seq_attention: {D} columns do not split into {heads} heads")
     p = float(p) if training else 0.0
+    if not causal and p > 0.0:
+        raise ValueError("seq_attention: the key-padding mode (causal=False) has no attention dropout")
     fits = qkv.is_cuda and qkv.dtype == torch.float32 and (q is None or q.dtype == torch.float32) and \
         hip.seq_attn_fits(L, heads, D // heads)
     if not fits:
@@ -2467,10 +2509,10 @@ def seq_attention(qkv: torch.Tensor, mask: torch.Tensor, heads: int, p: float = 
         keep = None
         if p > 0.0:
             keep = torch.nn.functional.dropout(torch.ones(B, heads, L, L, dtype=qkv.dtype, device=qkv.device), p, True)
-        return seq_attention_reference(qr, kv, mask, heads, keep=keep, scale=1.0, qpos=qpos, compact=q is not None)
+        return seq_attention_reference(qr, kv, mask, heads, keep=keep, scale=1.0, qpos=qpos, compact=q is not None, causal=causal)
     if qpos is not None:
         qpos = qpos.to(torch.int64).contiguous()
-    return _SeqAttention.apply(qkv, q, mask.to(torch.float32).contiguous(), qpos, heads, p)
+    return _SeqAttention.apply(qkv, q, mask.to(torch.float32).contiguous(), qpos, heads, p, bool(causal))
 
 
 SEQ_ACTS = {"gelu": hip.SEQ_ACT_GELU, "swish": hip.SEQ_ACT_SWISH}
@@ -2809,3 +2851,88 @@ def attention_pool(x: torch.Tensor, w1: torch.Tensor, w2: torch.Tensor, valid: t
                             f"{hip.attn_pool_geometry()})")
         return attention_pool_reference(x, w1, w2, valid, bias, act, norm)
     return _AttentionPool.apply(x, valid.to(torch.float32), w1, w2, bias, _ATTN_POOL_ACTS[act], _ATTN_POOL_NORMS[norm])
+
+
+# ----------------------------------------------------------------------------------------------
+# sequence recall: the in-batch contrastive loss of CLRec (models/sequence/clrec.py:65-102 of the reference) and ContraRec
+# (contrarec.py:93-144) as ONE autograd node (csrc/contrast.hip).  Saved between forward and backward: the
+# inputs, lse [n] (float64) and the positive counts c [n]; no [n, m] tensor exists on the HIP path.
+# ----------------------------------------------------------------------------------------------
+def contrastive_loss_reference(a, b, labels_a, labels_b, temperature: float, exclude_self: bool = False, scale: float = 1.0,
+                               return_lse: bool = False):
+    """contrastive_loss in torch ops, op for op as the reference's two ContraLoss modules (any device and dtype):
+    materialises the [n, m] matrix several times.  b None: the symmetric form (b = a, labels_b = labels_a)."""
+    if b is None:
+        b, labels_b = a, labels_a
+    elif exclude_self:
+        raise ValueError("contrastive_loss: exclude_self belongs to the symmetric form (b=None)")
+    n, m = a.shape[0], b.shape[0]
+    dot = torch.matmul(a, b.transpose(0, 1)) / temperature
+    logits_max, _ = torch.max(dot, dim=1, keepdim=True)
+    logits = dot - logits_max.detach()
+    mask = torch.eq(labels_a.view(-1, 1), labels_b.view(1, -1)).to(a.dtype)
+    logits_mask = torch.ones_like(mask)
+    if exclude_self:
+        logits_mask = torch.scatter(logits_mask, 1, torch.arange(n, device=a.device).view(-1, 1), 0)
+    mask = mask * logits_mask
+    exp_logits = torch.exp(logits) * logits_mask
+    log_denominator = torch.log(exp_logits.sum(1, keepdim=True) + 1e-10)
+    log_prob = logits - log_denominator
+    mean_log_prob_pos = (mask * log_prob).sum(1) / (mask.sum(1) + 1e-10)
+    loss = (-scale * mean_log_prob_pos).mean()
+    if return_lse:
+        return loss, (logits_max + log_denominator).view(-1).detach()
+    return loss
+
+
+class _ContrastiveLoss(torch.autograd.Function):
+    """inputs: a, b | None, labels_a, labels_b | None; saved: those, lse and c"""
+
+    @staticmethod
+    def forward(ctx, a, b, la, lb, temperature: float, exclude_self: bool, scale: float):
+        a = _unit_inner(a)
+        b = None if b is None else _unit_inner(b)
+        loss, lse, c = hip.contrast_fwd(a, b, la, lb, temperature, exclude_self, scale)
+        ctx.cfg = (temperature, exclude_self, scale, b is not None)
+        ctx.save_for_backward(a, la, lse, c, *(() if b is None else (b, lb)))
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        temperature, exclude_self, scale, has_b = ctx.cfg
+        a, la, lse, c, *rest = ctx.saved_tensors
+        b, lb = rest if has_b else (None, None)
+        da, db = hip.contrast_bwd(a, b, la, lb, lse, c, g.reshape(1).float().contiguous(), temperature, exclude_self, scale,
+                                  ctx.needs_input_grad[0], has_b and ctx.needs_input_grad[1])
+        return da, db, None, None, None, None, None
+
+
+def contrastive_loss(a: torch.Tensor, b, labels_a: torch.Tensor, labels_b, temperature: float, exclude_self: bool = False,
+                     scale: float = 1.0):
+    """The in-batch contrastive loss: with l_ij = (a_i . b_j) / temperature, N_i = all j (exclude_self: all j != i),
+    P_i = { j in N_i : labels_a[i] == labels_b[j] } and c_i = |P_i|,
+        lse_i = m_i + log(sum_{j in N_i} exp(l_ij - m_i) + 1e-10),  m_i = max_j l_ij over all j,
+        loss  = (scale / n) sum_i -(sum_{j in P_i} (l_ij - lse_i)) / (c_i + 1e-10)      (a row without positives adds 0).
+    a [n, D], b [m, D], labels int64 [n] / [m]; b = None (then labels_b = None too) is the symmetric form over a's own rows,
+    the only one that takes exclude_self.  CLRec: a = user rows, b = target rows, labels arange(B), scale 1; ContraRec:
+    symmetric over cat(view1, view2), labels cat(target, target), exclude_self, scale = temperature.
+    On the HIP device rp_contrast_fwd / _bwd (no [n, m] tensor, the backward recomputes from lse; bit-identical runs) for
+    fp32 rows up to D = 128; outside, the composed torch formulation on the device, counted; on CPU tensors the same
+    formulation (contrastive_loss_reference)."""
+    if b is None:
+        if labels_b is not None:
+            raise ValueError("contrastive_loss: the symmetric form (b=None) takes no labels_b")
+    elif exclude_self:
+        raise ValueError("contrastive_loss: exclude_self belongs to the symmetric form (b=None)")
+    if not (temperature > 0):
+        raise ValueError("contrastive_loss: the temperature must be positive")
+    if not a.is_cuda:
+        return contrastive_loss_reference(a, b, labels_a, labels_b, temperature, exclude_self, scale)
+    D = a.shape[1]
+    if a.dtype != torch.float32 or (b is not None and b.dtype != torch.float32) or not hip.contrast_fits(D):
+        hip.note_torch_path(f"contrastive_loss at D={D}, {a.dtype} (the kernels take fp32 up to "
+                            f"D={hip.contrast_geometry()['max_d']})")
+        return contrastive_loss_reference(a, b, labels_a, labels_b, temperature, exclude_self, scale)
+    la = labels_a.reshape(-1).to(torch.int64).contiguous()
+    lb = None if b is None else labels_b.reshape(-1).to(torch.int64).contiguous()
+    return _ContrastiveLoss.apply(a, b, la, lb, float(temperature), bool(exclude_self), float(scale))

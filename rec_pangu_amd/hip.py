@@ -3242,13 +3242,22 @@ def _seq_attn_args(q, kv, mask, qpos, heads: int, compact: bool):
     return B, L, D, D // heads
 
 
-def seq_attn_fwd(q, kv, mask, heads: int, p: float = 0.0, rng=None, qpos=None, compact: bool = False):
+def seq_attn_fwd(q, kv, mask, heads: int, p: float = 0.0, rng=None, qpos=None, compact: bool = False, causal: bool = True):
     """rp_seq_attn_fwd(_dev) -> (ctx [B L, D] or, with qpos, [B, D]; lse [B, heads, L] or [B, heads]).  rng: (seed, offset,
-    clock) from seq_attn_seed_offset when p > 0; compact: q holds one row per sample, [B, D] (needs qpos)."""
+    clock) from seq_attn_seed_offset when p > 0; compact: q holds one row per sample, [B, D] (needs qpos).  causal False:
+    rp_seq_attn_keypad_fwd, every query over every content key (no dropout there)."""
     B, L, D, dh = _seq_attn_args(q, kv, mask, qpos, heads, compact)
     rows = B if qpos is not None else B * L
     ctx = _new((rows, D), torch.float32, q.device)
     lse = _new((B, heads) if qpos is not None else (B, heads, L), torch.float32, q.device)
+    if not causal:
+        if p > 0.0:
+            raise RuntimeError("seq_attn: the key-padding mode has no dropout")
+        with _Timed("seq_attn_keypad_fwd", f"{B}x{heads}x{L}x{dh}", 4 * (B * L * 3 * D + rows * D), 4 * B * heads * L * L * dh):
+            _check(lib().rp_seq_attn_keypad_fwd(q.data_ptr(), _rowmajor(q, "q"), int(compact), kv.data_ptr(), _rowmajor(kv, "kv"),
+                                                mask.data_ptr(), _ptr(qpos), B, L, heads, dh, ctx.data_ptr(), lse.data_ptr(),
+                                                _stream()), "rp_seq_attn_keypad_fwd")
+        return ctx, lse
     seed, offset, clock = rng if (p > 0.0 and rng is not None) else (0, 0, None)
     head = (q.data_ptr(), _rowmajor(q, "q"), int(compact), kv.data_ptr(), _rowmajor(kv, "kv"), mask.data_ptr(), _ptr(qpos), B, L,
             heads, dh, p, seed, offset)
@@ -3262,11 +3271,15 @@ def seq_attn_fwd(q, kv, mask, heads: int, p: float = 0.0, rng=None, qpos=None, c
 
 
 def seq_attn_bwd(q, kv, mask, ctx, dctx, lse, heads: int, p: float = 0.0, rng=None, qpos=None, compact: bool = False, dq=None,
-                 dkv=None):
+                 dkv=None, causal: bool = True):
     """rp_seq_attn_bwd(_dev) -> (dq with q's rows x D, dkv [B L, 2 D]); dq / dkv: row buffers to write into (the column
-    blocks of one [B L, 3 D] buffer, for instance)"""
+    blocks of one [B L, 3 D] buffer, for instance).  causal False: rp_seq_attn_keypad_bwd, which takes no ctx (pass None)."""
     B, L, D, dh = _seq_attn_args(q, kv, mask, qpos, heads, compact)
     rows = B if qpos is not None else B * L
+    if ctx is None:
+        if causal:
+            raise RuntimeError("seq_attn_bwd: the causal backward needs ctx")
+        ctx = dctx  # (the key-padding backward does not read it: only the checks below see it)
     _rows(ctx, "ctx", D, rows)
     _rows(dctx, "dctx", D, rows)
     if not (ctx.is_contiguous() and dctx.is_contiguous() and lse.is_contiguous()):
@@ -3280,6 +3293,13 @@ def seq_attn_bwd(q, kv, mask, ctx, dctx, lse, heads: int, p: float = 0.0, rng=No
         dkv = _new((B * L, 2 * D), torch.float32, q.device)
     _rows(dq, "dq", D, q.shape[0])
     _rows(dkv, "dkv", 2 * D, B * L)
+    if not causal:
+        with _Timed("seq_attn_keypad_bwd", f"{B}x{heads}x{L}x{dh}", 4 * (B * L * 6 * D + 2 * rows * D), 7 * B * heads * L * L * dh):
+            _check(lib().rp_seq_attn_keypad_bwd(q.data_ptr(), _rowmajor(q, "q"), int(compact), kv.data_ptr(), _rowmajor(kv, "kv"),
+                                                mask.data_ptr(), _ptr(qpos), dctx.data_ptr(), lse.data_ptr(), B, L,
+                                                heads, dh, dq.data_ptr(), _rowmajor(dq, "dq"), dkv.data_ptr(),
+                                                _rowmajor(dkv, "dkv"), _stream()), "rp_seq_attn_keypad_bwd")
+        return dq, dkv
     seed, offset, clock = rng if (p > 0.0 and rng is not None) else (0, 0, None)
     head = (q.data_ptr(), _rowmajor(q, "q"), int(compact), kv.data_ptr(), _rowmajor(kv, "kv"), mask.data_ptr(), _ptr(qpos),
             ctx.data_ptr(), dctx.data_ptr(), lse.data_ptr(), B, L, heads, dh, p, seed, offset)
@@ -3622,3 +3642,78 @@ def attn_pool_bwd(x, valid, w1, w2, c, A, dout, act: int, norm: int):
                                       dout.data_ptr(), B, L, D, Dh, K, act, norm, dx.data_ptr(), dw1.data_ptr(), dw2.data_ptr(),
                                       _ptr(dc), ws.data_ptr(), nbytes, _stream()), "rp_attn_pool_bwd")
     return dx, dw1, dw2, dc
+
+
+# ---- sequence recall: the in-batch contrastive loss of CLRec and ContraRec (csrc/contrast.hip) -------------------------------
+def contrast_geometry() -> dict:
+    """{"TA", "TB": rows of a / b per tile, "max_d": largest D the kernels take, "max_splits": most splits of b's rows}"""
+    v = [_i32(0) for _ in range(4)]
+    _check(lib().rp_contrast_geometry(*[C.byref(x) for x in v]), "rp_contrast_geometry")
+    return dict(zip(("TA", "TB", "max_d", "max_splits"), (x.value for x in v)))
+
+
+def contrast_fits(D: int) -> bool:
+    return bool(lib().rp_contrast_fits(D))
+
+
+def contrast_workspace_bytes(n: int, m: int, D: int) -> int:
+    nb = _sz(0)
+    _check(lib().rp_contrast_workspace_bytes(n, m, D, C.byref(nb)), "rp_contrast_workspace_bytes")
+    return nb.value
+
+
+def _contrast_args(a, b, la, lb):
+    """a [n, D], b [m, D] or None (symmetric form), la int64 [n], lb int64 [m] or None -> (n, m, D, lda, ldb)"""
+    n, D = a.shape
+    lda = _rows(a, "a", D)
+    _req(a, torch.float32, "a")
+    _req(la, torch.int64, "labels_a")
+    if tuple(la.shape) != (n,) or not la.is_contiguous():
+        raise RuntimeError(f"contrast: labels_a must be a contiguous int64 [{n}] tensor")
+    if b is None:
+        if lb is not None:
+            raise RuntimeError("contrast: the symmetric form (b None) takes no labels_b")
+        return n, n, D, lda, 0
+    m = b.shape[0]
+    ldb = _rows(b, "b", D)
+    if b.shape[1] != D:
+        raise RuntimeError(f"contrast: b rows of {b.shape[1]} columns against a's {D}")
+    _req(b, torch.float32, "b")
+    _req(lb, torch.int64, "labels_b")
+    if tuple(lb.shape) != (m,) or not lb.is_contiguous():
+        raise RuntimeError(f"contrast: labels_b must be a contiguous int64 [{m}] tensor")
+    return n, m, D, lda, ldb
+
+
+def contrast_fwd(a, b, la, lb, temperature: float, exclude_self: bool = False, scale: float = 1.0):
+    """rp_contrast_fwd -> (loss float32 [1], lse float64 [n], c float32 [n]); b / lb None: the symmetric form"""
+    n, m, D, lda, ldb = _contrast_args(a, b, la, lb)
+    ws, nbytes = _workspace("contrast", n, m, D, device=a.device)
+    lse = _new((n,), torch.float64, a.device)
+    c, loss = (_new((k,), torch.float32, a.device) for k in (n, 1))
+    with _Timed("contrast_fwd", f"{n}x{m}x{D}", 4 * (n * D + m * D), 2 * n * m * D):
+        _check(lib().rp_contrast_fwd(a.data_ptr(), lda, _ptr(b), ldb, la.data_ptr(), _ptr(lb), n, m, D, temperature,
+                                     int(exclude_self), scale, lse.data_ptr(), c.data_ptr(), loss.data_ptr(), ws.data_ptr(),
+                                     nbytes, _stream()), "rp_contrast_fwd")
+    return loss, lse, c
+
+
+def contrast_bwd(a, b, la, lb, lse, c, gloss, temperature: float, exclude_self: bool = False, scale: float = 1.0,
+                 want_da: bool = True, want_db: bool = True):
+    """rp_contrast_bwd -> (da [n, D] or None, db [m, D] or None); gloss: device float32 [1].  Symmetric form (b None):
+    (da + db, None)."""
+    n, m, D, lda, ldb = _contrast_args(a, b, la, lb)
+    _req(lse, torch.float64, "lse")
+    _req(c, torch.float32, "c")
+    _req(gloss, torch.float32, "gloss")
+    ws, nbytes = _workspace("contrast", n, m, D, device=a.device)
+    sym = b is None
+    da = _new((n, D), torch.float32, a.device) if (want_da or sym) else None
+    db = _new((m, D), torch.float32, a.device) if (want_db and not sym) else None
+    if da is None and db is None:
+        return None, None
+    with _Timed("contrast_bwd", f"{n}x{m}x{D}", 4 * (2 * n * D + 2 * m * D), 8 * n * m * D):
+        _check(lib().rp_contrast_bwd(a.data_ptr(), lda, _ptr(b), ldb, la.data_ptr(), _ptr(lb), lse.data_ptr(), c.data_ptr(),
+                                     gloss.data_ptr(), n, m, D, temperature, int(exclude_self), scale, _ptr(da), D, _ptr(db), D,
+                                     ws.data_ptr(), nbytes, _stream()), "rp_contrast_bwd")
+    return da, db

@@ -6,7 +6,7 @@ from .interaction import (InnerProductLayer, FM_Layer, CrossInteractionLayer, Cr
                           CompressedInteractionNet, MaskBlock, GeneralizedInteractionNet,
                           GeneralizedInteraction, BilinearInteractionLayer, SENET_Layer)
 from .attention import ScaledDotProductAttention, MultiHeadAttention, MultiHeadSelfAttention
-from .sequence import MaskedAveragePooling, MaskedSumPooling, KMaxPooling, GRU4RecEncoder, STAMPLayer
+from .sequence import MaskedAveragePooling, MaskedSumPooling, KMaxPooling, GRU4RecEncoder, STAMPLayer, BERT4RecEncoder
 from .multi_interest import CapsuleNetwork, MultiInterestSelfAttention
 from .transformer import FeedForward, TransformerLayer, TransformerEncoder
 from .conv import NextItNetLayer, ResBlockOneMasked, ResBlockTwoMasked, MaskedConv1d, LayerNorm
@@ -18,4 +18,4 @@ __all__ = ["Dice", "get_activation", "EmbeddingLayer", "MLP", "LR_Layer", "Inner
            "MultiHeadAttention", "MultiHeadSelfAttention", "MaskedAveragePooling", "MaskedSumPooling", "KMaxPooling",
            "GRU4RecEncoder", "CapsuleNetwork", "FeedForward", "TransformerLayer", "TransformerEncoder", "NextItNetLayer",
            "ResBlockOneMasked", "ResBlockTwoMasked", "MaskedConv1d", "LayerNorm", "SRGNNConv", "SRGNNCell", "STAMPLayer",
-           "MultiInterestSelfAttention"]
+           "MultiInterestSelfAttention", "BERT4RecEncoder"]

@@ -1,5 +1,6 @@
-"""Sequence poolings of the reference (rec_pangu/models/layers/sequence.py:13-59), its KMaxPooling (:63-86) and its
-GRU4RecEncoder (:231-251) and its STAMPLayer (:89-144) as drop-in modules.
+"""Sequence poolings of the reference (rec_pangu/models/layers/sequence.py:13-59), its KMaxPooling (:63-86), its
+GRU4RecEncoder (:231-251), its STAMPLayer (:89-144) and its BERT4RecEncoder with the MultiHeadAttention and TransformerLayer
+under it (:150-228, :286-312) as drop-in modules.
 
 On a HIP tensor they run rp_seq_pool_fwd / _bwd (one read of the [B, L, D] tensor); on the CPU the reference's own
 formulas.  When the pooled tensor comes straight from a `_seq` lookup, `EmbeddingLayer.lookup_pooled` fuses lookup and
@@ -127,3 +128,168 @@ class STAMPLayer(nn.Module):
         if on_hip:
             return Fh.linear_act(ma, self.fc_a.weight, self.fc_a.bias) * Fh.linear_act(xt, self.fc_t.weight, self.fc_t.bias)
         return self.fc_a(ma) * self.fc_t(xt)
+
+
+class MultiHeadAttention(nn.Module):
+    """The projections and the attention of the reference's sequence.py:150-197 (no output projection): the same constructor
+    and the parameters `q_linear` (absent with kq_same), `k_linear`, `v_linear` in that order.  Not the class of the same
+    name in layers/transformer.py (SASRec's), as in the reference.
+
+    forward(q, k, v, mask): mask None, anything that broadcasts against the [B, heads, Lq, Lk] scores (the reference's
+    [B, 1, 1, L] key-padding mask) or a [B, L] content mask (non-zero = content).  Self-attention (q, k and v the same
+    tensor) under a [B, L] mask on the HIP device is one stacked Q | K | V GEMM and Fh.seq_attention(causal=False): one
+    launch each way, nothing of size L x L stored; qpos (int64 [B], that path only) selects one query row per sample ->
+    [B, D].  Everything else runs the torch formulas (counted on the HIP device).
+
+    Deliberate difference: the reference subtracts the maximum score of the WHOLE batch tensor before the softmax
+    (`scores - scores.max()`); here the maximum is subtracted per row.  Equal unless a row's own maximum lies about 87 below
+    the batch's, where the reference's row collapses to 0.  A row without a content key is 0 (the reference: NaN -> 0) and
+    passes zero gradients (the reference: NaN)."""
+
+    def __init__(self, d_model, n_heads, kq_same=False, bias=True):
+        super().__init__()
+        self.d_model = d_model
+        self.h = n_heads
+        self.d_k = self.d_model // self.h
+        self.kq_same = kq_same
+
+        if not kq_same:
+            self.q_linear = nn.Linear(d_model, d_model, bias=bias)
+        self.k_linear = nn.Linear(d_model, d_model, bias=bias)
+        self.v_linear = nn.Linear(d_model, d_model, bias=bias)
+
+    def head_split(self, x):  # bs * h * seq_len * d_k
+        new_x_shape = x.size()[:-1] + (self.h, self.d_k)
+        return x.view(*new_x_shape).transpose(-2, -3)
+
+    @staticmethod
+    def scaled_dot_product_attention(q, k, v, d_k, mask=None):
+        scores = torch.matmul(q, k.transpose(-2, -1)) / d_k ** 0.5  # bs, head, q_len, k_len
+        if mask is not None:
+            scores = scores.masked_fill(mask == 0, float("-inf"))
+        top = scores.detach().max(dim=-1, keepdim=True).values
+        e = torch.exp(scores - torch.where(torch.isinf(top), torch.zeros_like(top), top))
+        den = e.sum(dim=-1, keepdim=True)
+        return torch.matmul(e / torch.where(den > 0, den, torch.ones_like(den)), v)
+
+    def _linears(self):
+        return [self.k_linear if self.kq_same else self.q_linear, self.k_linear, self.v_linear]
+
+    def forward(self, q, k, v, mask=None, qpos=None):
+        fused = q.is_cuda and q is k and k is v and mask is not None and mask.dim() == 2 and q.dim() == 3
+        if not fused:
+            if qpos is not None:
+                raise ValueError("MultiHeadAttention: qpos needs self-attention under a [B, L] content mask on the HIP device")
+            if q.is_cuda:
+                Fh.hip.note_torch_path("sequence.MultiHeadAttention outside self-attention under a [B, L] content mask")
+            if mask is not None and mask.dim() == 2 and q.dim() == 3:
+                mask = mask.view(mask.shape[0], 1, 1, mask.shape[1])
+            origin_shape = q.size()
+            q = self.head_split((self.k_linear if self.kq_same else self.q_linear)(q))
+            k = self.head_split(self.k_linear(k))
+            v = self.head_split(self.v_linear(v))
+            output = self.scaled_dot_product_attention(q, k, v, self.d_k, mask)
+            return output.transpose(-2, -3).reshape(origin_shape)
+        B, L, D = q.shape
+        rows = q.reshape(B * L, D)
+        lin = self._linears()
+        has_bias = self.k_linear.bias is not None
+
+        def stacked(ms):
+            return Fh.stack_rows([m.weight for m in ms]), (Fh.stack_rows([m.bias.view(-1, 1) for m in ms]).view(-1) if has_bias
+                                                           else None)
+
+        if qpos is None:
+            qkv = Fh.linear_act(rows, *stacked(lin))
+            return Fh.seq_attention(qkv, mask, self.h, causal=False).reshape(B, L, D)
+        kv = Fh.linear_act(rows, *stacked(lin[1:]))
+        qrow = Fh.linear_act(Fh.seq_take(q, qpos), lin[0].weight, lin[0].bias)
+        return Fh.seq_attention(kv, mask, self.h, qpos=qpos, q=qrow, causal=False)
+
+
+class TransformerLayer(nn.Module):
+    """The block of the reference's sequence.py:200-228: the attention above, residual + LayerNorm, a ReLU feed-forward of
+    width d_ff, residual + LayerNorm; LayerNorm eps is torch's default, dropout defaults to 0.  The same constructor, names
+    and registration order (`masked_attn_head`, `layer_norm1`, `dropout1`, `linear1`, `linear2`, `layer_norm2`, `dropout2`).
+    Not layers/transformer.py's class of the same name.
+
+    forward(seq, mask): mask as MultiHeadAttention's.  Under a [B, L] content mask on the HIP device the attention is the
+    fused one and the rest runs on the library's Linear and LayerNorm; with qpos (int64 [B]) everything after K and V runs
+    for the one selected row per sample -> [B, D]."""
+
+    def __init__(self, d_model, d_ff, n_heads, dropout=0, kq_same=False):
+        super().__init__()
+        self.masked_attn_head = MultiHeadAttention(d_model, n_heads, kq_same=kq_same)
+
+        self.layer_norm1 = nn.LayerNorm(d_model)
+        self.dropout1 = nn.Dropout(dropout)
+
+        self.linear1 = nn.Linear(d_model, d_ff)
+        self.linear2 = nn.Linear(d_ff, d_model)
+
+        self.layer_norm2 = nn.LayerNorm(d_model)
+        self.dropout2 = nn.Dropout(dropout)
+
+    def forward(self, seq, mask=None, qpos=None):
+        if not (seq.is_cuda and mask is not None and mask.dim() == 2):
+            context = self.masked_attn_head(seq, seq, seq, mask)
+            context = self.layer_norm1(self.dropout1(context) + seq)
+            output = self.linear1(context).relu()
+            output = self.linear2(output)
+            return self.layer_norm2(self.dropout2(output) + context)
+        drop = self.training and self.dropout1.p > 0
+        context = self.masked_attn_head(seq, seq, seq, mask, qpos=qpos)
+        residual = seq if qpos is None else Fh.seq_take(seq, qpos)
+        shape = context.shape
+        context, residual = context.reshape(-1, shape[-1]), residual.reshape(-1, shape[-1])
+        if drop:
+            context = Fh.dropout(context, self.dropout1.p)
+        context = Fh.layer_norm(context + residual, self.layer_norm1)
+        output = Fh.linear_act(context, self.linear1.weight, self.linear1.bias, act=Fh.ACT_RELU)
+        output = Fh.linear_act(output, self.linear2.weight, self.linear2.bias)
+        if drop:
+            output = Fh.dropout(output, self.dropout2.p)
+        return Fh.layer_norm(output + context, self.layer_norm2).reshape(shape)
+
+
+class BERT4RecEncoder(nn.Module):
+    """Bidirectional self-attention over the first lengths[b] positions of each row, read at position lengths[b] - 1 —
+    sequence.py:286-312 of the reference: the same constructor, `p_embeddings` then `transformer_block.{i}.*`.  Padded
+    positions take position row 0 (the reference's `len_range * valid_mask`).
+
+    On the HIP device: the position rows as a select between `p_embeddings.weight[:L]` and its row 0, per layer one stacked Q | K | V GEMM and the key-padding
+    attention under mask = arange(L) < lengths; the FINAL layer runs in last-row mode at qpos = lengths - 1.  On the CPU the
+    reference's formulas (with MultiHeadAttention's per-row maximum).  A row of length 0 gives a zero vector on both paths
+    (the reference reads position -1 of the masked output: 0 as well)."""
+
+    def __init__(self, emb_size, max_his, num_layers=2, num_heads=2):
+        super().__init__()
+        self.p_embeddings = nn.Embedding(max_his + 1, emb_size)
+        self.transformer_block = nn.ModuleList([
+            TransformerLayer(d_model=emb_size, d_ff=emb_size, n_heads=num_heads)
+            for _ in range(num_layers)
+        ])
+
+    def forward(self, seq, lengths):
+        batch_size, seq_len = seq.size(0), seq.size(1)
+        lengths = lengths.to(torch.int64)
+        len_range = torch.arange(seq_len, device=seq.device)
+        valid_mask = len_range[None, :] < lengths[:, None]
+        position = len_range[None, :] * valid_mask.long()
+        if not seq.is_cuda or len(self.transformer_block) == 0:
+            seq = seq + self.p_embeddings(position)
+            attn_mask = valid_mask.view(batch_size, 1, 1, seq_len)
+            for block in self.transformer_block:
+                seq = block(seq, attn_mask)
+            seq = seq * valid_mask[:, :, None].to(seq.dtype)
+            return seq[torch.arange(batch_size, device=seq.device), lengths - 1]
+        # position[b, l] is l inside the row and 0 behind it: a select between two broadcasts instead of a lookup, whose
+        # backward would have ONE writer walk the B L / 2 occurrences of row 0 in order (20 ms at B = 4096, L = 20)
+        w = self.p_embeddings.weight
+        seq = seq + torch.where(valid_mask.unsqueeze(-1), w[:seq_len].unsqueeze(0), w[0].view(1, 1, -1))
+        content = valid_mask.to(torch.float32)
+        for block in self.transformer_block[:-1]:
+            seq = block(seq, content)
+        last = lengths - 1
+        out = self.transformer_block[-1](seq, content, qpos=last)
+        return out * (last >= 0).to(out.dtype).view(-1, 1)

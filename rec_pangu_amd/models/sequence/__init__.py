@@ -9,6 +9,8 @@ from .srgnn import SRGNN  # noqa: F401
 from .niser import NISER  # noqa: F401
 from .gcsan import GCSAN  # noqa: F401
 from .stamp import STAMP  # noqa: F401
+from .clrec import CLRec  # noqa: F401
+from .contrarec import ContraRec  # noqa: F401
 
-# (MIND, ComirecDR, ComirecSA, SASRec, NextItNet, SRGNN, NISER, GCSAN and STAMP are importable from here; __all__ keeps the list tests/test_gru_host.py pins)
+# (MIND, ComirecDR, ComirecSA, SASRec, NextItNet, SRGNN, NISER, GCSAN, STAMP, CLRec and ContraRec are importable from here; __all__ keeps the list tests/test_gru_host.py pins)
 __all__ = ["YotubeDNN", "GRU4Rec", "NARM"]
