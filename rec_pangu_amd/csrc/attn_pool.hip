@@ -58,19 +58,6 @@ __global__ __launch_bounds__(256) void ap_pack_kernel(ApArgs a, int backward) {
     }
 }
 
-// acc += A[row, :] . W[col, :] over Kp columns (a multiple of 8); arow NULL or columns >= kvalid (a multiple of 4) read as zero
-__device__ __forceinline__ f32x16 ap_mma(f32x16 acc, const float *arow, int Kp, int kvalid, const float *__restrict__ wrow, int h) {
-    for (int kq = 0; kq < Kp / 8; ++kq) {
-        const int k = kq * 8 + 4 * h;
-        f32x4 a4 = {0.f, 0.f, 0.f, 0.f};
-        if (arow != nullptr && k < kvalid) a4 = *reinterpret_cast<const f32x4 *>(arow + k);
-        const f32x4 b4 = *reinterpret_cast<const f32x4 *>(wrow + k);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[e], b4[e], acc, 0, 0, 0);
-    }
-    return acc;
-}
-
 // the X tile (zero rows behind the workgroup's samples, zero columns [D, Dp)) and the rows' valid flags
 __device__ __forceinline__ void ap_load(const ApArgs &a, int64_t b0, float *XB, float *val) {
     for (int idx = threadIdx.x; idx < a.Mp * a.Dp; idx += blockDim.x) {
@@ -89,7 +76,7 @@ __device__ __forceinline__ void ap_load(const ApArgs &a, int64_t b0, float *XB, 
 __device__ __forceinline__ void ap_hidden(const ApArgs &a, int64_t b0, const float *XB, int rt, int ch, int i, int h, float (&hid)[16]) {
     const int col = ch * 32 + i;
     f32x16 acc = {0};
-    acc = ap_mma(acc, XB + (rt * 32 + i) * a.ld, a.Dp, a.Dp, a.W1T + (int64_t)col * a.Dp, h);
+    acc = rp_mma_f32_rows(acc, XB + (rt * 32 + i) * a.ld, a.Dp, a.Dp, a.W1T + (int64_t)col * a.Dp, h);
 #pragma unroll
     for (int q = 0; q < 16; ++q) {
         const int m = rt * 32 + rp_mfma32_row(q, h);
@@ -121,7 +108,7 @@ __global__ __launch_bounds__(256) void ap_fwd_kernel(ApArgs a) {
         for (int k = 0; k < 8; ++k) sacc[k] = 0.f;
         for (int ch = w / a.nrt; ch < nch; ch += 4 / a.nrt) {
             f32x16 acc = {0};
-            acc = ap_mma(acc, a.W1T + (int64_t)(ch * 32 + i) * a.Dp, a.Dp, a.Dp, XB + m * a.ld, h);
+            acc = rp_mma_f32_rows(acc, a.W1T + (int64_t)(ch * 32 + i) * a.Dp, a.Dp, a.Dp, XB + m * a.ld, h);
             float part[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) part[k] = 0.f;
@@ -283,7 +270,7 @@ __global__ __launch_bounds__(256) void ap_bwd_kernel(ApArgs a) {
                 const int mr = rt * 32 + i;
                 const int64_t br = b0 + mr / L;
                 const float *arow = (mr < a.Mv && br < a.B) ? a.dPre + (br * L + mr % L) * a.Dhs : nullptr;
-                acc = ap_mma(acc, arow, a.Kb, a.Dhs, a.W1P + (int64_t)col * a.Kb, h);
+                acc = rp_mma_f32_rows(acc, arow, a.Kb, a.Dhs, a.W1P + (int64_t)col * a.Kb, h);
 #pragma unroll
                 for (int q = 0; q < 16; ++q) {
                     const int m = rt * 32 + rp_mfma32_row(q, h);

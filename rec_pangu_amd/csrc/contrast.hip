@@ -2,8 +2,8 @@
 // forward and backward, gfx950 — the loss of CLRec (models/sequence/clrec.py:65-102 of the reference) and of ContraRec
 // (contrarec.py:93-144).  The reference materialises the [n, m] matrix about seven times (dot, logits, mask, logits_mask,
 // exp_logits, log_prob, mask * log_prob) and autograd keeps most of them.  Here no [n, m] tensor exists: this is the sibling
-// of softmax_ce.hip, the same 32 x 32 score tiles in the matrix core's accumulators, the same orientations, the same rule
-// that the recomputed tile carries the forward's bits (softmax_ce.hip's header has the -lse seeding finding).
+// of softmax_ce.hip on the one skeleton of score_tile.h — the same 32 x 32 score tiles in the matrix core's accumulators, the
+// same orientations, the same rule that the recomputed tile carries the forward's bits.
 //
 // Notation: a [n, lda >= D], b [m, ldb >= D] fp32, la [n], lb [m] int64 labels, T > 0, l_ij = (a_i . b_j) / T (a division, as
 // the reference's `matmul / temperature`).  Symmetric form: b absent, then b = a, lb = la and exclude_self may be set.
@@ -22,66 +22,21 @@
 //             scores of ONE row i: running maximum, sum (online softmax, the self pair left out of the sum only), the count of
 //             positives and the sum of their l_ij are per-lane registers; lane halves, waves and splits are merged in a fixed
 //             order (ctr_finish_kernel: one thread per row walks the splits in ascending order), which leaves lse [n], c [n]
-//             and per-workgroup sums of the row terms; ctr_mean_kernel adds those in a fixed order.
+//             and per-workgroup sums of the row terms; st_mean_kernel adds those in a fixed order.
 //   da        same grid, orientation and product order: q in registers is the next MFMA's B operand as it is; one [n, D] slab
-//             per split, ctr_da_reduce_kernel adds the slabs in split order (and, symmetric form, the db result) and scales.
+//             per split, st_slab_reduce_kernel adds the slabs in split order (and, symmetric form, the db result) and scales.
 //   db        grid ceil(m / 32): a workgroup owns 32 rows of b and walks all of a; the tile is S[i, j] (the same piece pairs in
 //             the same order), the accumulator is the A operand; every row of db has one writer.
 // No floating-point atomics: loss and gradients are bit-identical from run to run.
 //
 // Saved between forward and backward: lse [n] (float64: m_i + log(sum) added in double and split into hi + lo by the backward,
 // so that p = exp((l - hi) - lo) keeps the digits of log(sum) beside m ~ 24) and c [n] (the count as a float).
-// D: 1 .. CTR_MAX_D = 128, zero-padded to 32 (softmax_ce.hip's register budget); above, RP_ERR_ARG and nothing is launched.
-#include "common.h"
-#include "bfsplit.h"
+// D: 1 .. ST_MAX_D = 128, zero-padded to 32 (score_tile.h's register budget); above, RP_ERR_ARG and nothing is launched.
+#include "score_tile.h"
 
-#define CTR_TA 32
-#define CTR_TB 32
-#define CTR_WAVES 4
-#define CTR_BLOCK 256
-#define CTR_MAX_D 128
-#define CTR_MAX_SPLITS 64
-#define CTR_MIN_TILES 4
-#define CTR_FILL 1024
 #define CTR_EPS 1e-10f
 
 namespace {
-
-// 8 consecutive floats of one row from column c on, zero beyond D / for a row outside the matrix
-__device__ __forceinline__ f32x8 ctr_load8(const float *__restrict__ base, int64_t ld, int64_t row, bool valid, int c, int D,
-                                           bool fast) {
-    f32x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = 0.f;
-    if (valid && c < D) {
-        const float *p = base + row * ld + c;
-        if (fast) {  // D % 16 == 0: c + 8 <= D
-            const f32x4 a = *reinterpret_cast<const f32x4 *>(p), b = *reinterpret_cast<const f32x4 *>(p + 4);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                v[j] = a[j];
-                v[4 + j] = b[j];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (c + j < D) v[j] = p[j];
-        }
-    }
-    return v;
-}
-
-// the operand that meets an accumulator tile used as a fragment (softmax_ce.hip: sce_load_rows)
-__device__ __forceinline__ f32x8 ctr_load_rows(const float *__restrict__ base, int64_t ld, int64_t row0, int64_t nrows, int s,
-                                               int h, int c, int D) {
-    f32x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int64_t row = row0 + rp_mfma32_row(8 * s + j, h);
-        v[j] = (row < nrows && c < D) ? base[row * ld + c] : 0.f;
-    }
-    return v;
-}
 
 // what one row knows of a range of columns: maximum over all of them, sum of exp(l - m) over N_i, |P_i| and the sum of l
 // over P_i; m = -inf marks "nothing yet"
@@ -101,40 +56,38 @@ __device__ __forceinline__ void ctr_merge(CtrStat &x, const CtrStat &y) {
 }
 
 template <int DT, int NPROD>
-__global__ __launch_bounds__(CTR_BLOCK) void ctr_fwd_kernel(const float *__restrict__ A, int64_t lda,
-                                                            const float *__restrict__ Bm, int64_t ldb,
-                                                            const int64_t *__restrict__ la, const int64_t *__restrict__ lb,
-                                                            int64_t n, int64_t m, int D, int64_t tps, int fastA, int fastB,
-                                                            float T, int excl, float *__restrict__ part) {
+__global__ __launch_bounds__(ST_BLOCK) void ctr_fwd_kernel(const float *__restrict__ A, int64_t lda,
+                                                           const float *__restrict__ Bm, int64_t ldb,
+                                                           const int64_t *__restrict__ la, const int64_t *__restrict__ lb,
+                                                           int64_t n, int64_t m, int D, int64_t tps, int fastA, int fastB,
+                                                           float T, int excl, float *__restrict__ part) {
     constexpr int NP = BfProd<NPROD>::NP;
     constexpr int KS = 2 * DT;
-    __shared__ float sm[CTR_WAVES][32], sl[CTR_WAVES][32], sp[CTR_WAVES][32];
-    __shared__ int sc[CTR_WAVES][32];
+    __shared__ float sm[ST_WAVES][32], sl[ST_WAVES][32], sp[ST_WAVES][32];
+    __shared__ int sc[ST_WAVES][32];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int64_t i0 = (int64_t)blockIdx.x * CTR_TA;
-    const int64_t tiles = (m + CTR_TB - 1) / CTR_TB;
-    const int64_t t0 = (int64_t)blockIdx.y * tps;
-    const int64_t t1 = (t0 + tps < tiles) ? t0 + tps : tiles;
+    const int64_t i0 = (int64_t)blockIdx.x * ST_TILE;
+    const StTiles tr = st_split_tiles(m, tps);
     const int64_t row = i0 + r;
     const bool ivalid = row < n;
     bf16x8 af[KS][NP];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(ctr_load8(A, lda, row, ivalid, 16 * ks + 8 * h, D, fastA), af[ks]);
+    for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(st_load8(A, lda, row, ivalid, 16 * ks + 8 * h, D, fastA), af[ks]);
     const int64_t lab = ivalid ? la[row] : 0;
     CtrStat st;
     st.m = -INFINITY;
     st.l = 0.f;
     st.ps = 0.f;
     st.cnt = 0;
-    for (int64_t t = t0 + w; t < t1; t += CTR_WAVES) {
-        const int64_t j0 = t * CTR_TB;
+    for (int64_t t = tr.t0 + w; t < tr.t1; t += ST_WAVES) {
+        const int64_t j0 = t * ST_TILE;
         f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             bf16x8 bf[NP];
-            bf_split8<NP>(ctr_load8(Bm, ldb, j0 + r, j0 + r < m, 16 * ks + 8 * h, D, fastB), bf);
+            bf_split8<NP>(st_load8(Bm, ldb, j0 + r, j0 + r < m, 16 * ks + 8 * h, D, fastB), bf);
 #pragma unroll
             for (int pr = 0; pr < NPROD; ++pr)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[BfProd<NPROD>::pa(pr)], af[ks][BfProd<NPROD>::pb(pr)], acc, 0, 0, 0);
@@ -187,7 +140,7 @@ __global__ __launch_bounds__(CTR_BLOCK) void ctr_fwd_kernel(const float *__restr
         a.ps = sp[0][x];
         a.cnt = sc[0][x];
 #pragma unroll
-        for (int q = 1; q < CTR_WAVES; ++q) {
+        for (int q = 1; q < ST_WAVES; ++q) {
             CtrStat b;
             b.m = sm[q][x];
             b.l = sl[q][x];
@@ -204,11 +157,11 @@ __global__ __launch_bounds__(CTR_BLOCK) void ctr_fwd_kernel(const float *__restr
 }
 
 // lse[i], c[i] and the workgroup's sum of the row terms: one thread per row walks the splits in ascending order
-__global__ __launch_bounds__(CTR_BLOCK) void ctr_finish_kernel(const float *__restrict__ part, int nsplit, int64_t n,
-                                                               double *__restrict__ lse, float *__restrict__ c,
-                                                               float *__restrict__ partial) {
-    __shared__ float sh[CTR_WAVES];
-    const int64_t row = (int64_t)blockIdx.x * CTR_BLOCK + threadIdx.x;
+__global__ __launch_bounds__(ST_BLOCK) void ctr_finish_kernel(const float *__restrict__ part, int nsplit, int64_t n,
+                                                              double *__restrict__ lse, float *__restrict__ c,
+                                                              float *__restrict__ partial) {
+    __shared__ float sh[ST_WAVES];
+    const int64_t row = (int64_t)blockIdx.x * ST_BLOCK + threadIdx.x;
     float term = 0.f;
     if (row < n) {
         CtrStat a;
@@ -241,58 +194,24 @@ __global__ __launch_bounds__(CTR_BLOCK) void ctr_finish_kernel(const float *__re
     if (threadIdx.x == 0) partial[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-__global__ __launch_bounds__(CTR_BLOCK) void ctr_mean_kernel(const float *__restrict__ partial, int64_t nb, float coef,
-                                                             float *__restrict__ loss) {
-    __shared__ float sh[CTR_WAVES];
-    float s = 0.f;
-    for (int64_t i = threadIdx.x; i < nb; i += CTR_BLOCK) s += partial[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[0] = __fmul_rn((sh[0] + sh[1]) + (sh[2] + sh[3]), coef);
-}
-
-// waves 1..3 park their accumulators in LDS, wave 0 adds them in wave order (softmax_ce.hip: sce_add_waves)
-template <int DT>
-__device__ __forceinline__ void ctr_add_waves(f32x16 (&acc)[DT], float *red, int w, int lane) {
-    if (w > 0) {
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) red[(((w - 1) * DT + dt) * 16 + i) * 64 + lane] = acc[dt][i];
-    }
-    __syncthreads();
-    if (w == 0) {
-#pragma unroll
-        for (int q = 0; q < CTR_WAVES - 1; ++q)
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[dt][i] += red[((q * DT + dt) * 16 + i) * 64 + lane];
-    }
-}
-
 template <int DT, int NPROD>
-__global__ __launch_bounds__(CTR_BLOCK) void ctr_da_kernel(const float *__restrict__ A, int64_t lda,
-                                                           const float *__restrict__ Bm, int64_t ldb,
-                                                           const int64_t *__restrict__ la, const int64_t *__restrict__ lb,
-                                                           const double *__restrict__ lse, const float *__restrict__ c, int64_t n,
-                                                           int64_t m, int D, int64_t tps, int fastA, int fastB, float T, int excl,
-                                                           float *__restrict__ dAp) {
+__global__ __launch_bounds__(ST_BLOCK) void ctr_da_kernel(const float *__restrict__ A, int64_t lda,
+                                                          const float *__restrict__ Bm, int64_t ldb,
+                                                          const int64_t *__restrict__ la, const int64_t *__restrict__ lb,
+                                                          const double *__restrict__ lse, const float *__restrict__ c, int64_t n,
+                                                          int64_t m, int D, int64_t tps, int fastA, int fastB, float T, int excl,
+                                                          float *__restrict__ dAp) {
     constexpr int NP = BfProd<NPROD>::NP;
     constexpr int KS = 2 * DT;
-    __shared__ float red[(CTR_WAVES - 1) * DT * 16 * 64];
+    __shared__ float red[(ST_WAVES - 1) * DT * 16 * 64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int64_t i0 = (int64_t)blockIdx.x * CTR_TA;
-    const int64_t tiles = (m + CTR_TB - 1) / CTR_TB;
-    const int64_t t0 = (int64_t)blockIdx.y * tps;
-    const int64_t t1 = (t0 + tps < tiles) ? t0 + tps : tiles;
+    const int64_t i0 = (int64_t)blockIdx.x * ST_TILE;
+    const StTiles tr = st_split_tiles(m, tps);
     const int64_t row = i0 + r;
     const bool ivalid = row < n;
     bf16x8 af[KS][NP];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(ctr_load8(A, lda, row, ivalid, 16 * ks + 8 * h, D, fastA), af[ks]);
+    for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(st_load8(A, lda, row, ivalid, 16 * ks + 8 * h, D, fastA), af[ks]);
     const double lse_d = ivalid ? lse[row] : 0.0;
     const float lse_hi = (float)lse_d, lse_lo = (float)(lse_d - (double)lse_hi);  // l - hi is exact near the maximum
     const float c_i = ivalid ? c[row] : 0.f;
@@ -303,15 +222,15 @@ __global__ __launch_bounds__(CTR_BLOCK) void ctr_da_kernel(const float *__restri
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) dacc[dt][i] = 0.f;
-    for (int64_t t = t0 + w; t < t1; t += CTR_WAVES) {
-        const int64_t j0 = t * CTR_TB;
+    for (int64_t t = tr.t0 + w; t < tr.t1; t += ST_WAVES) {
+        const int64_t j0 = t * ST_TILE;
         f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             bf16x8 bf[NP];
-            bf_split8<NP>(ctr_load8(Bm, ldb, j0 + r, j0 + r < m, 16 * ks + 8 * h, D, fastB), bf);
+            bf_split8<NP>(st_load8(Bm, ldb, j0 + r, j0 + r < m, 16 * ks + 8 * h, D, fastB), bf);
 #pragma unroll
             for (int pr = 0; pr < NPROD; ++pr)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(bf[BfProd<NPROD>::pa(pr)], af[ks][BfProd<NPROD>::pb(pr)], acc, 0, 0, 0);
@@ -337,7 +256,7 @@ __global__ __launch_bounds__(CTR_BLOCK) void ctr_da_kernel(const float *__restri
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
                 bf16x8 xf[NP];  // A operand[row d = 32 dt + r][k] = b[j0 + (row of k), d]
-                bf_split8<NP>(ctr_load_rows(Bm, ldb, j0, m, s, h, 32 * dt + r, D), xf);
+                bf_split8<NP>(st_load_rows(Bm, ldb, j0, m, s, h, 32 * dt + r, D), xf);
 #pragma unroll
                 for (int pr = 0; pr < NPROD; ++pr)
                     dacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(xf[BfProd<NPROD>::pa(pr)], pf[BfProd<NPROD>::pb(pr)], dacc[dt],
@@ -345,7 +264,7 @@ __global__ __launch_bounds__(CTR_BLOCK) void ctr_da_kernel(const float *__restri
             }
         }
     }
-    ctr_add_waves<DT>(dacc, red, w, lane);
+    st_add_waves<DT>(dacc, red, w, lane);
     if (w == 0 && ivalid) {
         float *o = dAp + ((int64_t)blockIdx.y * n + row) * D;
 #pragma unroll
@@ -358,49 +277,33 @@ __global__ __launch_bounds__(CTR_BLOCK) void ctr_da_kernel(const float *__restri
     }
 }
 
-// dA[i, d] = g coef (sum over the splits, in split order, + extra[i, d]); extra: the unscaled db of the symmetric form
-__global__ __launch_bounds__(CTR_BLOCK) void ctr_da_reduce_kernel(const float *__restrict__ dAp, int nsplit, int64_t n, int D,
-                                                                  const float *__restrict__ extra,
-                                                                  const float *__restrict__ gloss, float coef,
-                                                                  float *__restrict__ dA, int64_t ldda) {
-    const float scale = gloss[0] * coef;
-    const int64_t total = n * D;
-    for (int64_t e = (int64_t)blockIdx.x * CTR_BLOCK + threadIdx.x; e < total; e += (int64_t)gridDim.x * CTR_BLOCK) {
-        float s = dAp[e];
-        for (int sp = 1; sp < nsplit; ++sp) s += dAp[(int64_t)sp * total + e];
-        if (extra) s += extra[e];
-        const int64_t i = e / D;
-        dA[i * ldda + (e - i * D)] = s * scale;
-    }
-}
-
-// gloss == nullptr: the unscaled sums (the symmetric form's second half, added by ctr_da_reduce_kernel)
+// gloss == nullptr: the unscaled sums (the symmetric form's second half, added by st_slab_reduce_kernel)
 template <int DT, int NPROD>
-__global__ __launch_bounds__(CTR_BLOCK) void ctr_db_kernel(const float *__restrict__ A, int64_t lda,
-                                                           const float *__restrict__ Bm, int64_t ldb,
-                                                           const int64_t *__restrict__ la, const int64_t *__restrict__ lb,
-                                                           const double *__restrict__ lse, const float *__restrict__ c,
-                                                           const float *__restrict__ gloss, float coef, int64_t n, int64_t m,
-                                                           int D, int fastA, int fastB, float T, int excl,
-                                                           float *__restrict__ dB, int64_t lddb) {
+__global__ __launch_bounds__(ST_BLOCK) void ctr_db_kernel(const float *__restrict__ A, int64_t lda,
+                                                          const float *__restrict__ Bm, int64_t ldb,
+                                                          const int64_t *__restrict__ la, const int64_t *__restrict__ lb,
+                                                          const double *__restrict__ lse, const float *__restrict__ c,
+                                                          const float *__restrict__ gloss, float coef, int64_t n, int64_t m,
+                                                          int D, int fastA, int fastB, float T, int excl,
+                                                          float *__restrict__ dB, int64_t lddb) {
     constexpr int NP = BfProd<NPROD>::NP;
     constexpr int KS = 2 * DT;
-    __shared__ float red[(CTR_WAVES - 1) * DT * 16 * 64];
+    __shared__ float red[(ST_WAVES - 1) * DT * 16 * 64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int64_t j0 = (int64_t)blockIdx.x * CTR_TB;
+    const int64_t j0 = (int64_t)blockIdx.x * ST_TILE;
     const int64_t col = j0 + r;
     const bool jvalid = col < m;
     const int64_t itiles = (n + 31) / 32;
     bf16x8 bf[KS][NP];  // B operand[k][col r] = b[j0 + r, k]
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(ctr_load8(Bm, ldb, col, jvalid, 16 * ks + 8 * h, D, fastB), bf[ks]);
+    for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(st_load8(Bm, ldb, col, jvalid, 16 * ks + 8 * h, D, fastB), bf[ks]);
     const int64_t lab = jvalid ? lb[col] : 0;
     f32x16 zacc[DT];  // dB[j = j0 + rp_mfma32_row(i, h), d = 32 dt + r]
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) zacc[dt][i] = 0.f;
-    for (int64_t it = w; it < itiles; it += CTR_WAVES) {
+    for (int64_t it = w; it < itiles; it += ST_WAVES) {
         const int64_t i0 = it * 32;
         f32x16 acc;
 #pragma unroll
@@ -408,7 +311,7 @@ __global__ __launch_bounds__(CTR_BLOCK) void ctr_db_kernel(const float *__restri
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             bf16x8 af[NP];
-            bf_split8<NP>(ctr_load8(A, lda, i0 + r, i0 + r < n, 16 * ks + 8 * h, D, fastA), af);
+            bf_split8<NP>(st_load8(A, lda, i0 + r, i0 + r < n, 16 * ks + 8 * h, D, fastA), af);
 #pragma unroll
             for (int pr = 0; pr < NPROD; ++pr)
                 // (the forward pairs piece pa of b with piece pb of a: the same pairs in the same order here)
@@ -440,7 +343,7 @@ __global__ __launch_bounds__(CTR_BLOCK) void ctr_db_kernel(const float *__restri
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
                 bf16x8 xf[NP];  // B operand[k][col d = 32 dt + r] = a[i0 + (row of k), d]
-                bf_split8<NP>(ctr_load_rows(A, lda, i0, n, s, h, 32 * dt + r, D), xf);
+                bf_split8<NP>(st_load_rows(A, lda, i0, n, s, h, 32 * dt + r, D), xf);
 #pragma unroll
                 for (int pr = 0; pr < NPROD; ++pr)
                     zacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf[BfProd<NPROD>::pa(pr)], xf[BfProd<NPROD>::pb(pr)], zacc[dt],
@@ -448,7 +351,7 @@ __global__ __launch_bounds__(CTR_BLOCK) void ctr_db_kernel(const float *__restri
             }
         }
     }
-    ctr_add_waves<DT>(zacc, red, w, lane);
+    st_add_waves<DT>(zacc, red, w, lane);
     if (w == 0) {
         const float scale = gloss ? gloss[0] * coef : 1.f;
 #pragma unroll
@@ -463,35 +366,15 @@ __global__ __launch_bounds__(CTR_BLOCK) void ctr_db_kernel(const float *__restri
     }
 }
 
-struct CtrGeom {
-    int64_t row_tiles, tiles, tps;
-    int nsplit;
-};
-
-// the split of m: as many splits as bring the grid to CTR_FILL workgroups, at most CTR_MAX_SPLITS, each of at least
-// CTR_MIN_TILES tiles; the last split may hold fewer
-CtrGeom ctr_geom(int64_t n, int64_t m) {
-    CtrGeom g;
-    g.row_tiles = rp_cdiv(n, CTR_TA);
-    g.tiles = rp_cdiv(m, CTR_TB);
-    int64_t want = rp_cdiv(CTR_FILL, g.row_tiles);
-    if (want > CTR_MAX_SPLITS) want = CTR_MAX_SPLITS;
-    if (want < 1) want = 1;
-    g.tps = rp_cdiv(g.tiles, want);
-    if (g.tps < CTR_MIN_TILES) g.tps = CTR_MIN_TILES;
-    g.nsplit = (int)rp_cdiv(g.tiles, g.tps);
-    return g;
-}
-
 struct CtrWs {
     float *part, *partial, *dap, *dbt;
     size_t bytes;
 };
 
 // part [nsplit, n, 4] | partial [ceil(n / 256)] | dap [nsplit, n, D] | dbt [n, D] (the symmetric form's db, m == n there)
-CtrWs ctr_workspace(void *base, int64_t n, int D, const CtrGeom &g) {
+CtrWs ctr_workspace(void *base, int64_t n, int D, const StPlan &g) {
     CtrWs w;
-    const size_t n_part = (size_t)4 * g.nsplit * n, n_partial = ((size_t)rp_cdiv(n, CTR_BLOCK) + 3) & ~(size_t)3;
+    const size_t n_part = (size_t)4 * g.nsplit * n, n_partial = ((size_t)rp_cdiv(n, ST_BLOCK) + 3) & ~(size_t)3;
     const size_t n_dap = (((size_t)g.nsplit * n * D) + 3) & ~(size_t)3, n_dbt = (size_t)n * D;
     w.part = reinterpret_cast<float *>(base);
     w.partial = w.part + n_part;
@@ -501,48 +384,23 @@ CtrWs ctr_workspace(void *base, int64_t n, int D, const CtrGeom &g) {
     return w;
 }
 
-int ctr_products(int64_t n, int64_t m, int D) {
-    const int np = rp_matmul_products(2.0 * n * m * D, 4.0 * ((double)n * D + (double)m * D + (double)n * m));
-    return np == 0 ? 6 : np;
-}
-
-bool ctr_fast(const float *p, int64_t ld, int D) { return D % 16 == 0 && ld % 4 == 0 && rp_aligned16(p); }
-
 }  // namespace
 
-#define CTR_DISPATCH(DT_, NPROD_, CALL)                          \
-    do {                                                         \
-        switch ((DT_) * 8 + (NPROD_)) {                          \
-            case 1 * 8 + 1: { CALL(1, 1); } break;               \
-            case 1 * 8 + 3: { CALL(1, 3); } break;               \
-            case 1 * 8 + 6: { CALL(1, 6); } break;               \
-            case 2 * 8 + 1: { CALL(2, 1); } break;               \
-            case 2 * 8 + 3: { CALL(2, 3); } break;               \
-            case 2 * 8 + 6: { CALL(2, 6); } break;               \
-            case 3 * 8 + 1: { CALL(3, 1); } break;               \
-            case 3 * 8 + 3: { CALL(3, 3); } break;               \
-            case 3 * 8 + 6: { CALL(3, 6); } break;               \
-            case 4 * 8 + 1: { CALL(4, 1); } break;               \
-            case 4 * 8 + 3: { CALL(4, 3); } break;               \
-            default: { CALL(4, 6); } break;                      \
-        }                                                        \
-    } while (0)
-
-extern "C" int rp_contrast_fits(int D) { return D >= 1 && D <= CTR_MAX_D; }
+extern "C" int rp_contrast_fits(int D) { return D >= 1 && D <= ST_MAX_D; }
 
 extern "C" int rp_contrast_geometry(int *ta, int *tb, int *max_d, int *max_splits) {
     RP_REQUIRE(ta && tb && max_d && max_splits, "contrast_geometry: null pointer");
-    *ta = CTR_TA;
-    *tb = CTR_TB;
-    *max_d = CTR_MAX_D;
-    *max_splits = CTR_MAX_SPLITS;
+    *ta = ST_TILE;
+    *tb = ST_TILE;
+    *max_d = ST_MAX_D;
+    *max_splits = ST_MAX_SPLITS;
     return RP_OK;
 }
 
 extern "C" int rp_contrast_workspace_bytes(int64_t n, int64_t m, int D, size_t *bytes) {
     RP_REQUIRE(bytes, "contrast_workspace_bytes: null pointer");
     RP_REQUIRE(n >= 1 && m >= 1 && D >= 1, "contrast_workspace_bytes: n, m and D must be positive");
-    *bytes = ctr_workspace(nullptr, n, D, ctr_geom(n, m)).bytes;
+    *bytes = ctr_workspace(nullptr, n, D, st_plan(n, m)).bytes;
     return RP_OK;
 }
 
@@ -558,25 +416,25 @@ extern "C" int rp_contrast_fwd(const float *a, int64_t lda, const float *b, int6
         RP_REQUIRE(!exclude_self, "contrast_fwd: exclude_self belongs to the symmetric form (b absent)");
     }
     RP_REQUIRE(n >= 1 && m >= 1 && D >= 1 && lda >= D && ldb >= D, "contrast_fwd: bad n / m / D / lda / ldb");
-    RP_REQUIRE(D <= CTR_MAX_D, "contrast_fwd: D=%d above the %d the register budget takes", D, CTR_MAX_D);
+    RP_REQUIRE(D <= ST_MAX_D, "contrast_fwd: D=%d above the %d the register budget takes", D, ST_MAX_D);
     RP_REQUIRE(temperature > 0.f, "contrast_fwd: the temperature must be positive");
-    const CtrGeom g = ctr_geom(n, m);
+    const StPlan g = st_plan(n, m);
     const CtrWs ws = ctr_workspace(workspace, n, D, g);
     RP_REQUIRE(workspace_bytes >= ws.bytes && rp_aligned16(workspace), "contrast_fwd: workspace too small or misaligned");
-    const int dt = (D + 31) / 32, nprod = ctr_products(n, m, D);
-    const int fa = ctr_fast(a, lda, D), fb = ctr_fast(b, ldb, D);
+    const int dt = (D + 31) / 32, nprod = st_products(n, m, D);
+    const int fa = st_fast(a, lda, D), fb = st_fast(b, ldb, D);
     const int excl = exclude_self ? 1 : 0;
     hipStream_t s = (hipStream_t)stream;
 #define CALL(DT_, NP_)                                                                                                      \
-    hipLaunchKernelGGL((ctr_fwd_kernel<DT_, NP_>), dim3((unsigned)g.row_tiles, (unsigned)g.nsplit), dim3(CTR_BLOCK), 0, s, a, \
+    hipLaunchKernelGGL((ctr_fwd_kernel<DT_, NP_>), dim3((unsigned)g.row_tiles, (unsigned)g.nsplit), dim3(ST_BLOCK), 0, s, a,  \
                        lda, b, ldb, la, lb, n, m, D, g.tps, fa, fb, temperature, excl, ws.part)
-    CTR_DISPATCH(dt, nprod, CALL);
+    ST_DISPATCH(dt, nprod, CALL);
 #undef CALL
     RP_LAUNCH_CHECK("contrast_fwd");
-    const int64_t nb = rp_cdiv(n, CTR_BLOCK);
-    hipLaunchKernelGGL(ctr_finish_kernel, dim3((unsigned)nb), dim3(CTR_BLOCK), 0, s, ws.part, g.nsplit, n, lse, c, ws.partial);
+    const int64_t nb = rp_cdiv(n, ST_BLOCK);
+    hipLaunchKernelGGL(ctr_finish_kernel, dim3((unsigned)nb), dim3(ST_BLOCK), 0, s, ws.part, g.nsplit, n, lse, c, ws.partial);
     RP_LAUNCH_CHECK("contrast_finish");
-    hipLaunchKernelGGL(ctr_mean_kernel, dim3(1), dim3(CTR_BLOCK), 0, s, ws.partial, nb, scale / (float)n, loss);
+    hipLaunchKernelGGL(st_mean_kernel, dim3(1), dim3(ST_BLOCK), 0, s, ws.partial, nb, scale / (float)n, loss);
     RP_LAUNCH_CHECK("contrast_mean");
     return RP_OK;
 }
@@ -598,13 +456,13 @@ extern "C" int rp_contrast_bwd(const float *a, int64_t lda, const float *b, int6
     }
     RP_REQUIRE(n >= 1 && m >= 1 && D >= 1 && lda >= D && ldb >= D && (!da || ldda >= D) && (!db || lddb >= D),
                "contrast_bwd: bad n / m / D / leading dimensions");
-    RP_REQUIRE(D <= CTR_MAX_D, "contrast_bwd: D=%d above the %d the register budget takes", D, CTR_MAX_D);
+    RP_REQUIRE(D <= ST_MAX_D, "contrast_bwd: D=%d above the %d the register budget takes", D, ST_MAX_D);
     RP_REQUIRE(temperature > 0.f, "contrast_bwd: the temperature must be positive");
-    const CtrGeom g = ctr_geom(n, m);
+    const StPlan g = st_plan(n, m);
     const CtrWs ws = ctr_workspace(workspace, n, D, g);
     RP_REQUIRE(workspace_bytes >= ws.bytes && rp_aligned16(workspace), "contrast_bwd: workspace too small or misaligned");
-    const int dt = (D + 31) / 32, nprod = ctr_products(n, m, D);
-    const int fa = ctr_fast(a, lda, D), fb = ctr_fast(b, ldb, D);
+    const int dt = (D + 31) / 32, nprod = st_products(n, m, D);
+    const int fa = st_fast(a, lda, D), fb = st_fast(b, ldb, D);
     const int excl = exclude_self ? 1 : 0;
     const float coef = scale / ((float)n * temperature);
     hipStream_t s = (hipStream_t)stream;
@@ -613,23 +471,23 @@ extern "C" int rp_contrast_bwd(const float *a, int64_t lda, const float *b, int6
         const int64_t ldo = sym ? (int64_t)D : lddb;
         const float *gl = sym ? nullptr : gloss;
 #define CALL(DT_, NP_)                                                                                                       \
-    hipLaunchKernelGGL((ctr_db_kernel<DT_, NP_>), dim3((unsigned)g.tiles), dim3(CTR_BLOCK), 0, s, a, lda, b, ldb, la, lb, lse, c, \
+    hipLaunchKernelGGL((ctr_db_kernel<DT_, NP_>), dim3((unsigned)g.tiles), dim3(ST_BLOCK), 0, s, a, lda, b, ldb, la, lb, lse, c,  \
                        gl, coef, n, m, D, fa, fb, temperature, excl, out, ldo)
-        CTR_DISPATCH(dt, nprod, CALL);
+        ST_DISPATCH(dt, nprod, CALL);
 #undef CALL
         RP_LAUNCH_CHECK("contrast_db");
     }
     if (da) {
 #define CALL(DT_, NP_)                                                                                                     \
-    hipLaunchKernelGGL((ctr_da_kernel<DT_, NP_>), dim3((unsigned)g.row_tiles, (unsigned)g.nsplit), dim3(CTR_BLOCK), 0, s, a, \
+    hipLaunchKernelGGL((ctr_da_kernel<DT_, NP_>), dim3((unsigned)g.row_tiles, (unsigned)g.nsplit), dim3(ST_BLOCK), 0, s, a,  \
                        lda, b, ldb, la, lb, lse, c, n, m, D, g.tps, fa, fb, temperature, excl, ws.dap)
-        CTR_DISPATCH(dt, nprod, CALL);
+        ST_DISPATCH(dt, nprod, CALL);
 #undef CALL
         RP_LAUNCH_CHECK("contrast_da");
-        int64_t nb = rp_cdiv(n * D, CTR_BLOCK);
+        int64_t nb = rp_cdiv(n * D, ST_BLOCK);
         if (nb > 4096) nb = 4096;
         const float *extra = sym ? ws.dbt : nullptr;
-        hipLaunchKernelGGL(ctr_da_reduce_kernel, dim3((unsigned)nb), dim3(CTR_BLOCK), 0, s, ws.dap, g.nsplit, n, D, extra, gloss,
+        hipLaunchKernelGGL(st_slab_reduce_kernel, dim3((unsigned)nb), dim3(ST_BLOCK), 0, s, ws.dap, g.nsplit, n, D, extra, gloss,
                            coef, da, ldda);
         RP_LAUNCH_CHECK("contrast_da_reduce");
     }

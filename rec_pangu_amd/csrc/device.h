@@ -1,5 +1,6 @@
 // Device helpers every kernel file shares (included from common.h): lane reductions, the 256-thread block sum, the Philox
-// generator behind every dropout mask, the MFMA 32x32 accumulator row map, sigmoid and a round-up.  A kernel file uses
+// generator behind every dropout mask, the MFMA 32x32 accumulator row map, the fp32 row-by-row matrix-core product, sigmoid
+// and a round-up.  A kernel file uses
 // these and defines no copy of its own: a correction then reaches every kernel at once.
 #pragma once
 
@@ -72,6 +73,21 @@ static inline uint32_t rp_keep_thresh(float p) {
 
 // row of element i (0..15) of a lane's v_mfma_f32_32x32 accumulator; h = lane / 32, the column is lane % 32
 __device__ __forceinline__ int rp_mfma32_row(int i, int h) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+
+// exact-fp32 matrix core, both operands read by rows (attn_pool.hip, session_graph.hip):
+// acc += A[row, :] . W[col, :] over Kp columns (a multiple of 8); arow NULL or columns >= kvalid (a multiple of 4) read as zero
+__device__ __forceinline__ f32x16 rp_mma_f32_rows(f32x16 acc, const float *arow, int Kp, int kvalid, const float *__restrict__ wrow,
+                                                  int h) {
+    for (int kq = 0; kq < Kp / 8; ++kq) {
+        const int k = kq * 8 + 4 * h;
+        f32x4 a4 = {0.f, 0.f, 0.f, 0.f};
+        if (arow != nullptr && k < kvalid) a4 = *reinterpret_cast<const f32x4 *>(arow + k);
+        const f32x4 b4 = *reinterpret_cast<const f32x4 *>(wrow + k);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[e], b4[e], acc, 0, 0, 0);
+    }
+    return acc;
+}
 
 __device__ __forceinline__ float rp_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
 

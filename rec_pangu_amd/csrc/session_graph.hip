@@ -215,19 +215,6 @@ __device__ __forceinline__ void gg_load_h(const GgArgs &a, const GgTile &t) {
     }
 }
 
-// acc += A[row, :] . W[col, :] over Kp columns (a multiple of 8); arow NULL or columns >= kvalid (a multiple of 4) read as zero
-__device__ __forceinline__ f32x16 gg_mma(f32x16 acc, const float *arow, int Kp, int kvalid, const float *__restrict__ wrow, int h) {
-    for (int kq = 0; kq < Kp / 8; ++kq) {
-        const int k = kq * 8 + 4 * h;
-        f32x4 a4 = {0.f, 0.f, 0.f, 0.f};
-        if (arow != nullptr && k < kvalid) a4 = *reinterpret_cast<const f32x4 *>(arow + k);
-        const f32x4 b4 = *reinterpret_cast<const f32x4 *>(wrow + k);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a4[e], b4[e], acc, 0, 0, 0);
-    }
-    return acc;
-}
-
 // dst [Mp][Wp] (+)= src [Mp][Wp] . W^T (+ bias), W as [Wp][Wp] rows of the output column; tiles of LDS with row stride ld
 __device__ __forceinline__ void gg_linear(const GgArgs &a, const float *src, float *dst, const float *__restrict__ W,
                                           const float *__restrict__ bias, bool accumulate) {
@@ -240,7 +227,7 @@ __device__ __forceinline__ void gg_linear(const GgArgs &a, const float *src, flo
 #pragma unroll
             for (int q = 0; q < 16; ++q) acc[q] = dst[(rt * 32 + rp_mfma32_row(q, h)) * a.ld + col];
         }
-        acc = gg_mma(acc, src + (rt * 32 + i) * a.ld, a.Wp, a.Wp, W + (int64_t)col * a.Wp, h);
+        acc = rp_mma_f32_rows(acc, src + (rt * 32 + i) * a.ld, a.Wp, a.Wp, W + (int64_t)col * a.Wp, h);
         const float bv = (bias != nullptr && col < a.D) ? bias[col] : 0.f;
 #pragma unroll
         for (int q = 0; q < 16; ++q) dst[(rt * 32 + rp_mfma32_row(q, h)) * a.ld + col] = acc[q] + bv;
@@ -297,12 +284,12 @@ __device__ __forceinline__ void gg_gates(const GgArgs &a, const GgTile &t) {
         const int rt = tile % nrt, ct = tile / nrt, col = ct * 32 + i;
         const float *ag = t.AG + (rt * 32 + i) * a.ld2, *hb = t.HB + (rt * 32 + i) * a.ld;
         f32x16 ar = {0}, az = {0}, ani = {0}, anh = {0};
-        ar = gg_mma(ar, ag, 2 * Wp, 2 * Wp, a.wP[2] + (int64_t)(0 * Wp + col) * 2 * Wp, h);
-        az = gg_mma(az, ag, 2 * Wp, 2 * Wp, a.wP[2] + (int64_t)(1 * Wp + col) * 2 * Wp, h);
-        ani = gg_mma(ani, ag, 2 * Wp, 2 * Wp, a.wP[2] + (int64_t)(2 * Wp + col) * 2 * Wp, h);
-        ar = gg_mma(ar, hb, Wp, Wp, a.wP[3] + (int64_t)(0 * Wp + col) * Wp, h);
-        az = gg_mma(az, hb, Wp, Wp, a.wP[3] + (int64_t)(1 * Wp + col) * Wp, h);
-        anh = gg_mma(anh, hb, Wp, Wp, a.wP[3] + (int64_t)(2 * Wp + col) * Wp, h);
+        ar = rp_mma_f32_rows(ar, ag, 2 * Wp, 2 * Wp, a.wP[2] + (int64_t)(0 * Wp + col) * 2 * Wp, h);
+        az = rp_mma_f32_rows(az, ag, 2 * Wp, 2 * Wp, a.wP[2] + (int64_t)(1 * Wp + col) * 2 * Wp, h);
+        ani = rp_mma_f32_rows(ani, ag, 2 * Wp, 2 * Wp, a.wP[2] + (int64_t)(2 * Wp + col) * 2 * Wp, h);
+        ar = rp_mma_f32_rows(ar, hb, Wp, Wp, a.wP[3] + (int64_t)(0 * Wp + col) * Wp, h);
+        az = rp_mma_f32_rows(az, hb, Wp, Wp, a.wP[3] + (int64_t)(1 * Wp + col) * Wp, h);
+        anh = rp_mma_f32_rows(anh, hb, Wp, Wp, a.wP[3] + (int64_t)(2 * Wp + col) * Wp, h);
         const bool cok = col < D;
         const float br = cok ? bih[col] + bhh[col] : 0.f, bz = cok ? bih[D + col] + bhh[D + col] : 0.f;
         const float bni = cok ? bih[2 * D + col] : 0.f, bnh = cok ? bhh[2 * D + col] : 0.f;
@@ -404,7 +391,7 @@ __global__ __launch_bounds__(256) void gg_bwd_kernel(GgArgs a) {
 #pragma unroll
                 for (int q = 0; q < 16; ++q) acc[q] = dst[(rt * 32 + rp_mfma32_row(q, h)) * ldd + col];
             }
-            acc = gg_mma(acc, arow, a.K3p, a.s3, a.wT[to_ag ? 2 : 3] + (int64_t)col * a.K3p, h);
+            acc = rp_mma_f32_rows(acc, arow, a.K3p, a.s3, a.wT[to_ag ? 2 : 3] + (int64_t)col * a.K3p, h);
 #pragma unroll
             for (int q = 0; q < 16; ++q) dst[(rt * 32 + rp_mfma32_row(q, h)) * ldd + col] = acc[q];
         }

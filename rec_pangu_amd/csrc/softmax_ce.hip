@@ -22,14 +22,14 @@
 //             and the four waves are merged in a fixed order at the end, and one (m, l) pair per (row, split) goes to the
 //             workspace.  sce_finish_kernel merges the pairs of a row (4 slices of the splits, each in ascending order, then
 //             the slices in a fixed tree), adds the target's score as a plain fp32 dot product and leaves per-workgroup sums
-//             of lse - s_t; sce_mean_kernel adds those in a fixed order (the two-stage mean of lognet.hip / pair_loss.hip).
+//             of lse - s_t; st_mean_kernel adds those in a fixed order (the two-stage mean of lognet.hip / pair_loss.hip).
 //   dU        same grid, tile orientation and product order, so the recomputed scores carry the forward's bits:
 //             p' = exp(S' - lse) - [v == t_b] in registers.  (Seeding the accumulator with -lse instead rounds the sums at
 //             the magnitude of lse a second, different time: at scores of +-470 the softmax of a peaked row then misses
 //             exp(s_max - lse) = 1 / l by 1e-4 relative, measured, where the forward's own bits leave half an ulp of lse.)
 //             dU^T[d, b] += E_tile^T . P' sums over the tile's ROW index v, so the accumulator registers are the next MFMA's
 //             B operand as they are (no LDS, no lane movement).  The four waves' partial tiles are added in wave order, one
-//             [B, D] slab per split goes to the workspace, sce_du_reduce_kernel adds the slabs in split order and scales by
+//             [B, D] slab per split goes to the workspace, st_slab_reduce_kernel adds the slabs in split order and scales by
 //             g / B.
 //   dE        grid ceil(V / 32): a workgroup owns 32 rows of E (in registers, B fragments) and walks ALL of B, wave w the row
 //             tiles w, w + 4, ...; here the tile is S[b, v] = U_tile . E_tile^T (the same piece pairs in the same order) and
@@ -38,63 +38,19 @@
 // The one-hot is subtracted in the recomputed tile, so the target term needs no scatter and repeated targets no care.
 // No floating-point atomics: all three results are bit-identical from run to run.
 //
-// D: any D >= 1 up to SCE_MAX_D = 128; the contraction is zero-padded to a multiple of 32 (two k-steps of the MFMA; the dU / dE
+// D: any D >= 1 up to ST_MAX_D = 128; the contraction is zero-padded to a multiple of 32 (two k-steps of the MFMA; the dU / dE
 // accumulators are 32 columns of D per tile).  D % 16 == 0 with 16-byte aligned rows loads fragments as two dwordx4.  Above
 // 128 the pieces of the resident operand (3 x 4 registers per k-step) and the D / 32 output accumulators no longer fit beside
 // the score tile without spilling: RP_ERR_ARG.
-#include "common.h"
-#include "bfsplit.h"
+//
+// The tile skeleton (constants, fragment loads, wave add, mean and slab-reduce kernels, split plan, dispatch) is score_tile.h,
+// shared with contrast.hip; this file holds the softmax's own transform, (m, l) merge, finish kernel and workspace.
+#include "score_tile.h"
 
-#define SCE_TB 32          // rows of U per workgroup (forward, dU)
-#define SCE_TV 32          // rows of E per tile
-#define SCE_WAVES 4
-#define SCE_BLOCK 256
-#define SCE_MAX_D 128
-#define SCE_MAX_SPLITS 64
-#define SCE_MIN_TILES 4    // tiles of E per split at least: one per wave
-#define SCE_FILL 1024      // workgroups the split of V aims at
 #define SCE_SLICES 4       // lanes per row in the finishing merge
-#define SCE_FROWS (SCE_BLOCK / SCE_SLICES)
+#define SCE_FROWS (ST_BLOCK / SCE_SLICES)
 
 namespace {
-
-// 8 consecutive floats of one row from column c on, zero beyond D / for a row outside the matrix
-__device__ __forceinline__ f32x8 sce_load8(const float *__restrict__ base, int64_t ld, int64_t row, bool valid, int c, int D,
-                                           bool fast) {
-    f32x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) v[j] = 0.f;
-    if (valid && c < D) {
-        const float *p = base + row * ld + c;
-        if (fast) {  // D % 16 == 0: c + 8 <= D
-            const f32x4 a = *reinterpret_cast<const f32x4 *>(p), b = *reinterpret_cast<const f32x4 *>(p + 4);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                v[j] = a[j];
-                v[4 + j] = b[j];
-            }
-        } else {
-#pragma unroll
-            for (int j = 0; j < 8; ++j)
-                if (c + j < D) v[j] = p[j];
-        }
-    }
-    return v;
-}
-
-// the operand that meets an accumulator tile used as a fragment: element j of k-step s is the tile row
-// rp_mfma32_row(8 s + j, h)
-// (cdna4: registers 8s .. 8s+7 of the accumulator are rows 16 s + 8 (j >> 2) + 4 h + (j & 3)); column c of `base`
-__device__ __forceinline__ f32x8 sce_load_rows(const float *__restrict__ base, int64_t ld, int64_t row0, int64_t nrows, int s,
-                                               int h, int c, int D) {
-    f32x8 v;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        const int64_t row = row0 + rp_mfma32_row(8 * s + j, h);
-        v[j] = (row < nrows && c < D) ? base[row * ld + c] : 0.f;
-    }
-    return v;
-}
 
 // (m, l) <- the pair that stands for both sums; m = -inf marks "nothing yet"
 __device__ __forceinline__ void sce_merge(float &m, float &l, float m2, float l2) {
@@ -111,30 +67,28 @@ __device__ __forceinline__ int64_t sce_target(const int64_t *__restrict__ t, int
 }
 
 template <int DT, int NPROD>
-__global__ __launch_bounds__(SCE_BLOCK) void sce_fwd_kernel(const float *__restrict__ U, int64_t ldu,
-                                                            const float *__restrict__ E, int64_t B, int64_t V, int D,
-                                                            int64_t tps, int fastU, int fastE, float *__restrict__ ml) {
+__global__ __launch_bounds__(ST_BLOCK) void sce_fwd_kernel(const float *__restrict__ U, int64_t ldu,
+                                                           const float *__restrict__ E, int64_t B, int64_t V, int D,
+                                                           int64_t tps, int fastU, int fastE, float *__restrict__ ml) {
     constexpr int NP = BfProd<NPROD>::NP;
     constexpr int KS = 2 * DT;
-    __shared__ float sm[SCE_WAVES][32], sl[SCE_WAVES][32];
+    __shared__ float sm[ST_WAVES][32], sl[ST_WAVES][32];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int64_t b0 = (int64_t)blockIdx.x * SCE_TB;
-    const int64_t tiles = (V + SCE_TV - 1) / SCE_TV;
-    const int64_t t0 = (int64_t)blockIdx.y * tps;
-    const int64_t t1 = (t0 + tps < tiles) ? t0 + tps : tiles;
+    const int64_t b0 = (int64_t)blockIdx.x * ST_TILE;
+    const StTiles tr = st_split_tiles(V, tps);
     bf16x8 uf[KS][NP];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(sce_load8(U, ldu, b0 + r, b0 + r < B, 16 * ks + 8 * h, D, fastU), uf[ks]);
+    for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(st_load8(U, ldu, b0 + r, b0 + r < B, 16 * ks + 8 * h, D, fastU), uf[ks]);
     float m = -INFINITY, l = 0.f;
-    for (int64_t t = t0 + w; t < t1; t += SCE_WAVES) {
-        const int64_t v0 = t * SCE_TV;
+    for (int64_t t = tr.t0 + w; t < tr.t1; t += ST_WAVES) {
+        const int64_t v0 = t * ST_TILE;
         f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             bf16x8 ef[NP];
-            bf_split8<NP>(sce_load8(E, D, v0 + r, v0 + r < V, 16 * ks + 8 * h, D, fastE), ef);
+            bf_split8<NP>(st_load8(E, D, v0 + r, v0 + r < V, 16 * ks + 8 * h, D, fastE), ef);
 #pragma unroll
             for (int pr = 0; pr < NPROD; ++pr)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ef[BfProd<NPROD>::pa(pr)], uf[ks][BfProd<NPROD>::pb(pr)], acc, 0, 0, 0);
@@ -166,7 +120,7 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_fwd_kernel(const float *__restr
     if (threadIdx.x < 32 && b0 + threadIdx.x < B) {
         float mm = sm[0][threadIdx.x], ll = sl[0][threadIdx.x];
 #pragma unroll
-        for (int q = 1; q < SCE_WAVES; ++q) sce_merge(mm, ll, sm[q][threadIdx.x], sl[q][threadIdx.x]);
+        for (int q = 1; q < ST_WAVES; ++q) sce_merge(mm, ll, sm[q][threadIdx.x], sl[q][threadIdx.x]);
         float *o = ml + ((int64_t)blockIdx.y * B + b0 + threadIdx.x) * 2;
         o[0] = mm;
         o[1] = ll;
@@ -175,12 +129,12 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_fwd_kernel(const float *__restr
 
 // lse[b], the target's score and the workgroup's sum of lse - s_t.  SCE_SLICES lanes per row: slice q merges the splits
 // q, q + SCE_SLICES, ... in ascending order, then the slices are merged by a fixed tree; the dot product the same way.
-__global__ __launch_bounds__(SCE_BLOCK) void sce_finish_kernel(const float *__restrict__ ml, int nsplit,
-                                                               const float *__restrict__ U, int64_t ldu,
-                                                               const float *__restrict__ E, const int64_t *__restrict__ tgt,
-                                                               int64_t B, int64_t V, int D, float *__restrict__ lse,
-                                                               float *__restrict__ partial, int32_t *__restrict__ err_flag) {
-    __shared__ float sh[SCE_WAVES];
+__global__ __launch_bounds__(ST_BLOCK) void sce_finish_kernel(const float *__restrict__ ml, int nsplit,
+                                                              const float *__restrict__ U, int64_t ldu,
+                                                              const float *__restrict__ E, const int64_t *__restrict__ tgt,
+                                                              int64_t B, int64_t V, int D, float *__restrict__ lse,
+                                                              float *__restrict__ partial, int32_t *__restrict__ err_flag) {
+    __shared__ float sh[ST_WAVES];
     const int q = threadIdx.x % SCE_SLICES;
     const int64_t b = (int64_t)blockIdx.x * SCE_FROWS + threadIdx.x / SCE_SLICES;
     const bool valid = b < B;
@@ -225,56 +179,21 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_finish_kernel(const float *__re
     if (threadIdx.x == 0) partial[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
 }
 
-__global__ __launch_bounds__(SCE_BLOCK) void sce_mean_kernel(const float *__restrict__ partial, int64_t nb, float inv_b,
-                                                             float *__restrict__ loss) {
-    __shared__ float sh[SCE_WAVES];
-    float s = 0.f;
-    for (int64_t i = threadIdx.x; i < nb; i += SCE_BLOCK) s += partial[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) loss[0] = __fmul_rn((sh[0] + sh[1]) + (sh[2] + sh[3]), inv_b);
-}
-
-// the four waves' accumulators hold the same (register, lane) layout: waves 1..3 park theirs in LDS, wave 0 adds them in
-// wave order
-template <int DT>
-__device__ __forceinline__ void sce_add_waves(f32x16 (&acc)[DT], float *red, int w, int lane) {
-    if (w > 0) {
-#pragma unroll
-        for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) red[(((w - 1) * DT + dt) * 16 + i) * 64 + lane] = acc[dt][i];
-    }
-    __syncthreads();
-    if (w == 0) {
-#pragma unroll
-        for (int q = 0; q < SCE_WAVES - 1; ++q)
-#pragma unroll
-            for (int dt = 0; dt < DT; ++dt)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc[dt][i] += red[((q * DT + dt) * 16 + i) * 64 + lane];
-    }
-}
-
 template <int DT, int NPROD>
-__global__ __launch_bounds__(SCE_BLOCK) void sce_du_kernel(const float *__restrict__ U, int64_t ldu,
-                                                           const float *__restrict__ E, const int64_t *__restrict__ tgt,
-                                                           const float *__restrict__ lse, int64_t B, int64_t V, int D,
-                                                           int64_t tps, int fastU, int fastE, float *__restrict__ dUp) {
+__global__ __launch_bounds__(ST_BLOCK) void sce_du_kernel(const float *__restrict__ U, int64_t ldu,
+                                                          const float *__restrict__ E, const int64_t *__restrict__ tgt,
+                                                          const float *__restrict__ lse, int64_t B, int64_t V, int D,
+                                                          int64_t tps, int fastU, int fastE, float *__restrict__ dUp) {
     constexpr int NP = BfProd<NPROD>::NP;
     constexpr int KS = 2 * DT;
-    __shared__ float red[(SCE_WAVES - 1) * DT * 16 * 64];
+    __shared__ float red[(ST_WAVES - 1) * DT * 16 * 64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int64_t b0 = (int64_t)blockIdx.x * SCE_TB;
-    const int64_t tiles = (V + SCE_TV - 1) / SCE_TV;
-    const int64_t t0 = (int64_t)blockIdx.y * tps;
-    const int64_t t1 = (t0 + tps < tiles) ? t0 + tps : tiles;
+    const int64_t b0 = (int64_t)blockIdx.x * ST_TILE;
+    const StTiles tr = st_split_tiles(V, tps);
     const bool bvalid = b0 + r < B;
     bf16x8 uf[KS][NP];
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(sce_load8(U, ldu, b0 + r, bvalid, 16 * ks + 8 * h, D, fastU), uf[ks]);
+    for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(st_load8(U, ldu, b0 + r, bvalid, 16 * ks + 8 * h, D, fastU), uf[ks]);
     const float lse_b = bvalid ? lse[b0 + r] : 0.f;
     const int64_t tb = bvalid ? sce_target(tgt, b0 + r, V) : -1;
     f32x16 dacc[DT];  // dU^T[d = 32 dt + rp_mfma32_row(i, h), b = b0 + r]
@@ -282,15 +201,15 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_du_kernel(const float *__restri
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) dacc[dt][i] = 0.f;
-    for (int64_t t = t0 + w; t < t1; t += SCE_WAVES) {
-        const int64_t v0 = t * SCE_TV;
+    for (int64_t t = tr.t0 + w; t < tr.t1; t += ST_WAVES) {
+        const int64_t v0 = t * ST_TILE;
         f32x16 acc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) acc[i] = 0.f;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             bf16x8 ef[NP];
-            bf_split8<NP>(sce_load8(E, D, v0 + r, v0 + r < V, 16 * ks + 8 * h, D, fastE), ef);
+            bf_split8<NP>(st_load8(E, D, v0 + r, v0 + r < V, 16 * ks + 8 * h, D, fastE), ef);
 #pragma unroll
             for (int pr = 0; pr < NPROD; ++pr)
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ef[BfProd<NPROD>::pa(pr)], uf[ks][BfProd<NPROD>::pb(pr)], acc, 0, 0, 0);
@@ -311,7 +230,7 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_du_kernel(const float *__restri
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
                 bf16x8 af[NP];  // A[row d = 32 dt + r][k] = E[v0 + (row of k), d]
-                bf_split8<NP>(sce_load_rows(E, D, v0, V, s, h, 32 * dt + r, D), af);
+                bf_split8<NP>(st_load_rows(E, D, v0, V, s, h, 32 * dt + r, D), af);
 #pragma unroll
                 for (int pr = 0; pr < NPROD; ++pr)
                     dacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[BfProd<NPROD>::pa(pr)], pf[BfProd<NPROD>::pb(pr)], dacc[dt],
@@ -319,7 +238,7 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_du_kernel(const float *__restri
             }
         }
     }
-    sce_add_waves<DT>(dacc, red, w, lane);
+    st_add_waves<DT>(dacc, red, w, lane);
     if (w == 0 && bvalid) {
         float *o = dUp + ((int64_t)blockIdx.y * B + b0 + r) * D;
 #pragma unroll
@@ -332,41 +251,27 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_du_kernel(const float *__restri
     }
 }
 
-// dU[b, d] = (g / B) sum over the splits, in split order
-__global__ __launch_bounds__(SCE_BLOCK) void sce_du_reduce_kernel(const float *__restrict__ dUp, int nsplit, int64_t B, int D,
-                                                                  const float *__restrict__ gloss, float inv_b,
-                                                                  float *__restrict__ dU, int64_t lddu) {
-    const float scale = gloss[0] * inv_b;
-    const int64_t total = B * D;
-    for (int64_t e = (int64_t)blockIdx.x * SCE_BLOCK + threadIdx.x; e < total; e += (int64_t)gridDim.x * SCE_BLOCK) {
-        float s = dUp[e];
-        for (int sp = 1; sp < nsplit; ++sp) s += dUp[(int64_t)sp * total + e];
-        const int64_t b = e / D;
-        dU[b * lddu + (e - b * D)] = s * scale;
-    }
-}
-
 template <int DT, int NPROD>
-__global__ __launch_bounds__(SCE_BLOCK) void sce_de_kernel(const float *__restrict__ U, int64_t ldu,
-                                                           const float *__restrict__ E, const int64_t *__restrict__ tgt,
-                                                           const float *__restrict__ lse, const float *__restrict__ gloss,
-                                                           float inv_b, int64_t B, int64_t V, int D, int fastU, int fastE,
-                                                           float *__restrict__ dE) {
+__global__ __launch_bounds__(ST_BLOCK) void sce_de_kernel(const float *__restrict__ U, int64_t ldu,
+                                                          const float *__restrict__ E, const int64_t *__restrict__ tgt,
+                                                          const float *__restrict__ lse, const float *__restrict__ gloss,
+                                                          float inv_b, int64_t B, int64_t V, int D, int fastU, int fastE,
+                                                          float *__restrict__ dE) {
     constexpr int NP = BfProd<NPROD>::NP;
     constexpr int KS = 2 * DT;
-    __shared__ float red[(SCE_WAVES - 1) * DT * 16 * 64];
+    __shared__ float red[(ST_WAVES - 1) * DT * 16 * 64];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, r = lane & 31, h = lane >> 5;
-    const int64_t v0 = (int64_t)blockIdx.x * SCE_TV;
+    const int64_t v0 = (int64_t)blockIdx.x * ST_TILE;
     const int64_t btiles = (B + 31) / 32;
     bf16x8 ef[KS][NP];  // B[k][col r] = E[v0 + r, k]
 #pragma unroll
-    for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(sce_load8(E, D, v0 + r, v0 + r < V, 16 * ks + 8 * h, D, fastE), ef[ks]);
+    for (int ks = 0; ks < KS; ++ks) bf_split8<NP>(st_load8(E, D, v0 + r, v0 + r < V, 16 * ks + 8 * h, D, fastE), ef[ks]);
     f32x16 zacc[DT];  // dE[v = v0 + rp_mfma32_row(i, h), d = 32 dt + r]
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
         for (int i = 0; i < 16; ++i) zacc[dt][i] = 0.f;
-    for (int64_t bt = w; bt < btiles; bt += SCE_WAVES) {
+    for (int64_t bt = w; bt < btiles; bt += ST_WAVES) {
         const int64_t b0 = bt * 32;
         f32x16 acc;
         float lse_r[16], hit[16];  // lse[b] and [v0 + r == t_b] of register row b; hit = -1 marks a row beyond B
@@ -381,7 +286,7 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_de_kernel(const float *__restri
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             bf16x8 uf[NP];
-            bf_split8<NP>(sce_load8(U, ldu, b0 + r, b0 + r < B, 16 * ks + 8 * h, D, fastU), uf);
+            bf_split8<NP>(st_load8(U, ldu, b0 + r, b0 + r < B, 16 * ks + 8 * h, D, fastU), uf);
 #pragma unroll
             for (int pr = 0; pr < NPROD; ++pr)
                 // (the forward pairs piece pa of E with piece pb of U: the same pairs in the same order here)
@@ -400,7 +305,7 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_de_kernel(const float *__restri
 #pragma unroll
             for (int dt = 0; dt < DT; ++dt) {
                 bf16x8 bf[NP];  // B[k][col d = 32 dt + r] = U[b0 + (row of k), d]
-                bf_split8<NP>(sce_load_rows(U, ldu, b0, B, s, h, 32 * dt + r, D), bf);
+                bf_split8<NP>(st_load_rows(U, ldu, b0, B, s, h, 32 * dt + r, D), bf);
 #pragma unroll
                 for (int pr = 0; pr < NPROD; ++pr)
                     zacc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pf[BfProd<NPROD>::pa(pr)], bf[BfProd<NPROD>::pb(pr)], zacc[dt],
@@ -408,7 +313,7 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_de_kernel(const float *__restri
             }
         }
     }
-    sce_add_waves<DT>(zacc, red, w, lane);
+    st_add_waves<DT>(zacc, red, w, lane);
     if (w == 0) {
         const float scale = gloss[0] * inv_b;
 #pragma unroll
@@ -423,32 +328,12 @@ __global__ __launch_bounds__(SCE_BLOCK) void sce_de_kernel(const float *__restri
     }
 }
 
-struct SceGeom {
-    int64_t row_tiles, tiles, tps;
-    int nsplit;
-};
-
-// the split of V: as many splits as bring the grid to SCE_FILL workgroups, at most SCE_MAX_SPLITS, each of at least
-// SCE_MIN_TILES tiles; the last split may hold fewer
-SceGeom sce_geom(int64_t B, int64_t V) {
-    SceGeom g;
-    g.row_tiles = rp_cdiv(B, SCE_TB);
-    g.tiles = rp_cdiv(V, SCE_TV);
-    int64_t want = rp_cdiv(SCE_FILL, g.row_tiles);
-    if (want > SCE_MAX_SPLITS) want = SCE_MAX_SPLITS;
-    if (want < 1) want = 1;
-    g.tps = rp_cdiv(g.tiles, want);
-    if (g.tps < SCE_MIN_TILES) g.tps = SCE_MIN_TILES;
-    g.nsplit = (int)rp_cdiv(g.tiles, g.tps);
-    return g;
-}
-
 struct SceWs {
     float *ml, *partial, *dup;
     size_t bytes;
 };
 
-SceWs sce_workspace(void *base, int64_t B, int D, const SceGeom &g) {
+SceWs sce_workspace(void *base, int64_t B, int D, const StPlan &g) {
     SceWs w;
     const size_t n_ml = (size_t)2 * g.nsplit * B, n_part = (size_t)rp_cdiv(B, SCE_FROWS);
     const size_t n_dup = (size_t)g.nsplit * B * D;
@@ -459,38 +344,13 @@ SceWs sce_workspace(void *base, int64_t B, int D, const SceGeom &g) {
     return w;
 }
 
-int sce_products(int64_t B, int64_t V, int D) {
-    const int np = rp_matmul_products(2.0 * B * V * D, 4.0 * ((double)B * D + (double)V * D + (double)B * V));
-    return np == 0 ? 6 : np;
-}
-
-bool sce_fast(const float *p, int64_t ld, int D) { return D % 16 == 0 && ld % 4 == 0 && rp_aligned16(p); }
-
 }  // namespace
-
-#define SCE_DISPATCH(DT_, NPROD_, CALL)                          \
-    do {                                                         \
-        switch ((DT_) * 8 + (NPROD_)) {                          \
-            case 1 * 8 + 1: { CALL(1, 1); } break;               \
-            case 1 * 8 + 3: { CALL(1, 3); } break;               \
-            case 1 * 8 + 6: { CALL(1, 6); } break;               \
-            case 2 * 8 + 1: { CALL(2, 1); } break;               \
-            case 2 * 8 + 3: { CALL(2, 3); } break;               \
-            case 2 * 8 + 6: { CALL(2, 6); } break;               \
-            case 3 * 8 + 1: { CALL(3, 1); } break;               \
-            case 3 * 8 + 3: { CALL(3, 3); } break;               \
-            case 3 * 8 + 6: { CALL(3, 6); } break;               \
-            case 4 * 8 + 1: { CALL(4, 1); } break;               \
-            case 4 * 8 + 3: { CALL(4, 3); } break;               \
-            default: { CALL(4, 6); } break;                      \
-        }                                                        \
-    } while (0)
 
 extern "C" int rp_softmax_ce_geometry(int *tb, int *tv, int *max_d, int *slices) {
     RP_REQUIRE(tb && tv && max_d && slices, "softmax_ce_geometry: null pointer");
-    *tb = SCE_TB;
-    *tv = SCE_TV;
-    *max_d = SCE_MAX_D;
+    *tb = ST_TILE;
+    *tv = ST_TILE;
+    *max_d = ST_MAX_D;
     *slices = SCE_SLICES;
     return RP_OK;
 }
@@ -498,7 +358,7 @@ extern "C" int rp_softmax_ce_geometry(int *tb, int *tv, int *max_d, int *slices)
 extern "C" int rp_softmax_ce_splits(int64_t B, int64_t V, int *nsplit, int64_t *tiles_per_split) {
     RP_REQUIRE(nsplit && tiles_per_split, "softmax_ce_splits: null pointer");
     RP_REQUIRE(B >= 1 && V >= 1, "softmax_ce_splits: B and V must be positive");
-    const SceGeom g = sce_geom(B, V);
+    const StPlan g = st_plan(B, V);
     *nsplit = g.nsplit;
     *tiles_per_split = g.tps;
     return RP_OK;
@@ -507,7 +367,7 @@ extern "C" int rp_softmax_ce_splits(int64_t B, int64_t V, int *nsplit, int64_t *
 extern "C" int rp_softmax_ce_workspace_bytes(int64_t B, int64_t V, int D, size_t *bytes) {
     RP_REQUIRE(bytes, "softmax_ce_workspace_bytes: null pointer");
     RP_REQUIRE(B >= 1 && V >= 1 && D >= 1, "softmax_ce_workspace_bytes: B, V and D must be positive");
-    *bytes = sce_workspace(nullptr, B, D, sce_geom(B, V)).bytes;
+    *bytes = sce_workspace(nullptr, B, D, st_plan(B, V)).bytes;
     return RP_OK;
 }
 
@@ -516,24 +376,24 @@ extern "C" int rp_softmax_ce_fwd(const float *U, int64_t ldu, const float *E, co
                                  rp_stream_t stream) {
     RP_REQUIRE(U && E && target && lse && loss && err_flag && workspace, "softmax_ce_fwd: null pointer");
     RP_REQUIRE(B >= 1 && V >= 1 && D >= 1 && ldu >= D, "softmax_ce_fwd: bad B / V / D / ldu");
-    RP_REQUIRE(D <= SCE_MAX_D, "softmax_ce_fwd: D=%d above the %d the register budget takes", D, SCE_MAX_D);
-    const SceGeom g = sce_geom(B, V);
+    RP_REQUIRE(D <= ST_MAX_D, "softmax_ce_fwd: D=%d above the %d the register budget takes", D, ST_MAX_D);
+    const StPlan g = st_plan(B, V);
     const SceWs ws = sce_workspace(workspace, B, D, g);
     RP_REQUIRE(workspace_bytes >= ws.bytes && rp_aligned16(workspace), "softmax_ce_fwd: workspace too small or misaligned");
-    const int dt = (D + 31) / 32, nprod = sce_products(B, V, D);
-    const int fu = sce_fast(U, ldu, D), fe = sce_fast(E, D, D);
+    const int dt = (D + 31) / 32, nprod = st_products(B, V, D);
+    const int fu = st_fast(U, ldu, D), fe = st_fast(E, D, D);
     hipStream_t s = (hipStream_t)stream;
 #define CALL(DT_, NP_)                                                                                                      \
-    hipLaunchKernelGGL((sce_fwd_kernel<DT_, NP_>), dim3((unsigned)g.row_tiles, (unsigned)g.nsplit), dim3(SCE_BLOCK), 0, s, U, \
+    hipLaunchKernelGGL((sce_fwd_kernel<DT_, NP_>), dim3((unsigned)g.row_tiles, (unsigned)g.nsplit), dim3(ST_BLOCK), 0, s, U,  \
                        ldu, E, B, V, D, g.tps, fu, fe, ws.ml)
-    SCE_DISPATCH(dt, nprod, CALL);
+    ST_DISPATCH(dt, nprod, CALL);
 #undef CALL
     RP_LAUNCH_CHECK("softmax_ce_fwd");
     const int64_t nb = rp_cdiv(B, SCE_FROWS);
-    hipLaunchKernelGGL(sce_finish_kernel, dim3((unsigned)nb), dim3(SCE_BLOCK), 0, s, ws.ml, g.nsplit, U, ldu, E, target, B, V, D,
+    hipLaunchKernelGGL(sce_finish_kernel, dim3((unsigned)nb), dim3(ST_BLOCK), 0, s, ws.ml, g.nsplit, U, ldu, E, target, B, V, D,
                        lse, ws.partial, err_flag);
     RP_LAUNCH_CHECK("softmax_ce_finish");
-    hipLaunchKernelGGL(sce_mean_kernel, dim3(1), dim3(SCE_BLOCK), 0, s, ws.partial, nb, 1.f / (float)B, loss);
+    hipLaunchKernelGGL(st_mean_kernel, dim3(1), dim3(ST_BLOCK), 0, s, ws.partial, nb, 1.f / (float)B, loss);
     RP_LAUNCH_CHECK("softmax_ce_mean");
     return RP_OK;
 }
@@ -544,32 +404,32 @@ extern "C" int rp_softmax_ce_bwd(const float *U, int64_t ldu, const float *E, co
     RP_REQUIRE(U && E && target && lse && gloss && workspace, "softmax_ce_bwd: null pointer");
     RP_REQUIRE(dU || dE, "softmax_ce_bwd: neither gradient asked for");
     RP_REQUIRE(B >= 1 && V >= 1 && D >= 1 && ldu >= D && (!dU || lddu >= D), "softmax_ce_bwd: bad B / V / D / ldu / lddu");
-    RP_REQUIRE(D <= SCE_MAX_D, "softmax_ce_bwd: D=%d above the %d the register budget takes", D, SCE_MAX_D);
-    const SceGeom g = sce_geom(B, V);
+    RP_REQUIRE(D <= ST_MAX_D, "softmax_ce_bwd: D=%d above the %d the register budget takes", D, ST_MAX_D);
+    const StPlan g = st_plan(B, V);
     const SceWs ws = sce_workspace(workspace, B, D, g);
     RP_REQUIRE(workspace_bytes >= ws.bytes && rp_aligned16(workspace), "softmax_ce_bwd: workspace too small or misaligned");
-    const int dt = (D + 31) / 32, nprod = sce_products(B, V, D);
-    const int fu = sce_fast(U, ldu, D), fe = sce_fast(E, D, D);
+    const int dt = (D + 31) / 32, nprod = st_products(B, V, D);
+    const int fu = st_fast(U, ldu, D), fe = st_fast(E, D, D);
     const float inv_b = 1.f / (float)B;
     hipStream_t s = (hipStream_t)stream;
     if (dU) {
 #define CALL(DT_, NP_)                                                                                                     \
-    hipLaunchKernelGGL((sce_du_kernel<DT_, NP_>), dim3((unsigned)g.row_tiles, (unsigned)g.nsplit), dim3(SCE_BLOCK), 0, s, U, \
+    hipLaunchKernelGGL((sce_du_kernel<DT_, NP_>), dim3((unsigned)g.row_tiles, (unsigned)g.nsplit), dim3(ST_BLOCK), 0, s, U,  \
                        ldu, E, target, lse, B, V, D, g.tps, fu, fe, ws.dup)
-        SCE_DISPATCH(dt, nprod, CALL);
+        ST_DISPATCH(dt, nprod, CALL);
 #undef CALL
         RP_LAUNCH_CHECK("softmax_ce_du");
-        int64_t nb = rp_cdiv(B * D, SCE_BLOCK);
+        int64_t nb = rp_cdiv(B * D, ST_BLOCK);
         if (nb > 4096) nb = 4096;
-        hipLaunchKernelGGL(sce_du_reduce_kernel, dim3((unsigned)nb), dim3(SCE_BLOCK), 0, s, ws.dup, g.nsplit, B, D, gloss, inv_b,
-                           dU, lddu);
+        hipLaunchKernelGGL(st_slab_reduce_kernel, dim3((unsigned)nb), dim3(ST_BLOCK), 0, s, ws.dup, g.nsplit, B, D, nullptr,
+                           gloss, inv_b, dU, lddu);
         RP_LAUNCH_CHECK("softmax_ce_du_reduce");
     }
     if (dE) {
 #define CALL(DT_, NP_)                                                                                                    \
-    hipLaunchKernelGGL((sce_de_kernel<DT_, NP_>), dim3((unsigned)g.tiles), dim3(SCE_BLOCK), 0, s, U, ldu, E, target, lse, gloss, \
+    hipLaunchKernelGGL((sce_de_kernel<DT_, NP_>), dim3((unsigned)g.tiles), dim3(ST_BLOCK), 0, s, U, ldu, E, target, lse, gloss,  \
                        inv_b, B, V, D, fu, fe, dE)
-        SCE_DISPATCH(dt, nprod, CALL);
+        ST_DISPATCH(dt, nprod, CALL);
 #undef CALL
         RP_LAUNCH_CHECK("softmax_ce_de");
     }

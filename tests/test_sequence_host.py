@@ -405,6 +405,28 @@ def test_softmax_ce_geometry_and_split_rule():
     assert hip.softmax_ce_splits(1, g["TV"])[0] == 1
 
 
+def test_score_tile_split_plan_and_workspaces_keep_their_values():
+    """the host side of the two score-tile losses (split plan and workspace layouts), which no device listing covers: the
+    values of the build before the plan moved into csrc/score_tile.h.  (1, 32) and (5, 129) sit on the MIN_TILES floor,
+    (33, 70000) under the MAX_SPLITS cap, (4096, 131072) at the FILL target, (65536, 131072) needs no split."""
+    from rec_pangu_amd import hip
+    # (rows, cols): (splits, tiles per split), {D: (softmax-CE workspace bytes, contrastive workspace bytes)}
+    pinned = {
+        (1, 32): ((1, 4), {12: (72, 128), 128: (536, 1056)}),
+        (5, 129): ((2, 4), {12: (576, 896), 128: (5216, 7856)}),
+        (33, 70000): ((63, 35), {12: (116440, 134656), 128: (1081096, 1114624)}),
+        (4096, 131072): ((8, 512), {12: (1835264, 2293824), 128: (17039616, 19398720)}),
+        (65536, 131072): ((1, 4096), {12: (3674112, 7341056), 128: (34082816, 68158464)}),
+    }
+    for (rows, cols), (splits, ws) in pinned.items():
+        assert tuple(hip.softmax_ce_splits(rows, cols)) == splits, (rows, cols)
+        for Dd, (sce, ctr) in ws.items():
+            assert hip.softmax_ce_workspace_bytes(rows, cols, Dd) == sce, (rows, cols, Dd)
+            assert hip.contrast_workspace_bytes(rows, cols, Dd) == ctr, (rows, cols, Dd)
+    assert hip.softmax_ce_geometry() == {"TB": 32, "TV": 32, "max_d": 128, "slices": 4}
+    assert hip.contrast_geometry() == {"TA": 32, "TB": 32, "max_d": 128, "max_splits": 64}
+
+
 def test_softmax_ce_workspace_does_not_hold_the_logits():
     """a condition on the design: at B = 4096, V = 2^20, D = 64 the workspace is below 1/16 of the 16 GiB logits, and what
     grows with B alone is linear in B"""
