@@ -9,16 +9,58 @@
 //   * weights of one layer at a time in LDS as split-bf16 pieces (six products: fp32-faithful, as every HBM-bound GEMM);
 //   * a wave owns 32 rows; the activation tile never leaves the CU between layers: the MFMA C layout (lane = column) is
 //     turned into the A layout of the next layer (lane = row) through a 32 x 64 fp32 LDS tile;
-//   * backward: dgrads in the same A-stationary form on W^T (transposed while staged: no host-side transposes), weight
-//     gradients as TN products over the workgroup's 128 rows with the 64 x 64 output split over the four waves
-//     (32 x 32 each, 16 accumulator registers per layer), per-workgroup partials summed in a fixed order by a second
-//     small launch (deterministic); bias / head gradients as column sums of the same tiles.
+//   * backward: dgrads in the same A-stationary form on W^T (its fragments read from global memory with the
+//     transposition in the addressing: no host-side transposes, no LDS), weight gradients as TN products over the
+//     workgroup's 128 rows with the 64 x 64 output split over the four waves (32 x 32 each, ONE accumulator per layer
+//     that walks the 128 rows in order), per-workgroup partials summed in a fixed order by a second small launch
+//     (deterministic); bias / head gradients as column sums of the same tiles.
+//     Both LDS tiles of the backward are TRANSPOSED, [column][128 rows]: a wave writes its own 32 rows of dpre_l and
+//     a_{l-1} once (four-byte writes, 32 consecutive floats per half wave), and everything that reads them reads 16
+//     bytes: the wgrad's fragments (the 8 consecutive rows of a column that a lane holds per k-step), the dgrad's ReLU
+//     mask (four rows of a column per read, in the C layout's order), the head's dw_out walk.  The masked dgrad result
+//     goes from the C layout straight into the wave's rows of the dpre tile (16-byte writes) — it IS the next layer's
+//     dpre^T — so the tile is written once per layer and two workgroup barriers per layer remain, both ordering waves
+//     against each other's rows (tiles complete / tiles free); L = 2: 5 barriers.
+//     The other decomposition — each wave forming all of dW_l over its own 32 rows, operands wave-private, the four waves'
+//     tiles added afterwards — was built and measured (27.6-29.3 us alone, runs not kept, against 29.3-29.8 for this
+//     form and 32.5-33.5 before) and is not what is here, for one observed reason: it sums dW_l, db_l and dw_out in another order, and in
+//     the one comparison made (the benchmark's dumped outputs after its 1000 + 25 Adam steps on random labels,
+//     profiles/r07_tail_rowsplit_outputs.txt) the two runs' dense weights had drifted apart entirely, while two runs of
+//     one build are equal in every bit.  Its gradients passed every kernel test at 2e-5 of scale, so this is most likely
+//     the run's own sensitivity to last-bit changes, not an error of that build; it says nothing about model quality.
+//     But a change whose benchmark outputs differ cannot be told from a wrong one by that comparison, so this form keeps
+//     every sum's order and all outputs keep their bits.  The price: each dpre / a value is still split into bf16 pieces
+//     by the two waves whose tiles use it.  Splitting once remains open; it needs either that decomposition, with the
+//     output comparison made tolerant of reordered sums, or the pieces themselves in LDS (6 bytes per value: 96 KB).
 #include "common.h"
 #include "bfsplit.h"
 
 #define MT_LD 72   // bf16 row of 64 + 8 pad (144 B, odd multiple of 16 B): conflict-free ds_read_b128 fragment reads
 #define MT_CT 68   // fp32 row of an activation tile
 #define MT_MAXL 3  // hidden 64 x 64 layers in the tail
+#define MT_TW 132  // fp32 row of a TRANSPOSED backward tile: a column's 128 rows + 4 pad (528 B, odd multiple of 16 B)
+
+// a lane's half of a 64-float row in the A layout: v[ks][e] = src[16 ks + e], e = 0..7 (src already points at column 8 h)
+__device__ __forceinline__ void mt_load_row(const float *__restrict__ src, f32x8 (&v)[4]) {
+#pragma unroll
+    for (int ks = 0; ks < 4; ++ks) {
+        const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src + ks * 16), v1 = *reinterpret_cast<const f32x4 *>(src + ks * 16 + 4);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            v[ks][e] = v0[e];
+            v[ks][4 + e] = v1[e];
+        }
+    }
+}
+
+// Orders a wave's LDS writes before its own later LDS reads of what OTHER lanes of the wave wrote (and reads before later
+// overwrites).  The LDS serves one wave's instructions in issue order, so only the compiler has to be told: no instruction
+// results, and no other wave is waited for.
+__device__ __forceinline__ void mt_wave_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
 
 struct TailFwdArgs {
     const float *W[MT_MAXL];  // [64, 64] row-major (out, in), row stride ldw
@@ -145,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void mlp_tail_fwd_kernel(const float *__res
                 if (m < M) hout[m * 64 + n] = v;
             }
         }
-        __syncthreads();  // (a wave-level barrier would do: the tile is private to the wave)
+        mt_wave_sync();  // the tile is private to the wave
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const f32x4 v0 = *reinterpret_cast<const f32x4 *>(&Ct[wv][i][ks * 16 + 8 * h]);
@@ -285,7 +327,7 @@ struct TailBwdArgs {
 // (round 4: the W_l^T operand of the dgrad lives in REGISTERS — 24 fragments per lane, read from global memory with the
 //  transposition in the addressing (8 coalesced 128-byte row segments per fragment), split in place — instead of in 27 KB
 //  of LDS written with 48 two-byte stores per thread and layer: the two activation tiles are then all the LDS a workgroup
-//  holds (70 KB), TWO workgroups fit a CU and all 512 of a 65536-row launch are resident at once.  With one workgroup per
+//  holds (68 KB), TWO workgroups fit a CU and all 512 of a 65536-row launch are resident at once.  With one workgroup per
 //  CU — one wave per SIMD — nothing hid the kernel's chains of LDS round trips: 67 us for ~6 us of matrix work.)
 // the loss head's backward folded into the tail's (rp_mlp_tail_bwd_bce): dz[row] is formed from (pred, label, the loss
 // gradient) with rp_sigmoid_bce_bwd's arithmetic instead of being read, and written out for the other logit addends
@@ -299,17 +341,17 @@ template <int L>
 __global__ __launch_bounds__(256, 2) void mlp_tail_bwd_kernel(const float *__restrict__ dz, TailBwdArgs a,
                                                               const float *__restrict__ wout, float *__restrict__ dhin,
                                                               int64_t lddh, float *__restrict__ P, int64_t M, int nwg, TailDz tz) {
-    __shared__ __attribute__((aligned(16))) float T0[4][32][MT_CT];      // dpre_l  (rows of the four waves back to back)
-    __shared__ __attribute__((aligned(16))) float T1[4][32][MT_CT];      // a_{l-1}
-    __shared__ float dzs[128];                                           // dz of the workgroup's rows (0 beyond M)
+    // Both tiles TRANSPOSED, [column][the workgroup's 128 rows]: wave w owns rows 32 w .. 32 w + 31 of every column
+    __shared__ __attribute__((aligned(16))) float Dt[64][MT_TW];  // dpre_l^T
+    __shared__ __attribute__((aligned(16))) float At[64][MT_TW];  // a_{l-1}^T (before the first layer: (dz * a_L)^T)
+    __shared__ float dzs[128];                                    // dz of the workgroup's rows (0 beyond M)
     const int wv = threadIdx.x >> 6, l = threadIdx.x & 63, i = l & 31, h = l >> 5;
     const int64_t row0 = (int64_t)blockIdx.x * 128;
     const int64_t row = row0 + 32 * wv + i;
     const bool rok = row < M;
     const int64_t rowc = rok ? row : M - 1;
     const int mt = wv & 1, ntw = wv >> 1;  // this wave's 32 x 32 tile of every dW_l: out rows mt*32.., in columns ntw*32..
-    float (*T0f)[MT_CT] = reinterpret_cast<float (*)[MT_CT]>(&T0[0][0][0]);  // [128][MT_CT]
-    float (*T1f)[MT_CT] = reinterpret_cast<float (*)[MT_CT]>(&T1[0][0][0]);
+    const int ri = 32 * wv + i;            // this lane's row of the workgroup
     float *Pg = P + (int64_t)blockIdx.x * ((int64_t)L * 64 * 64 + (int64_t)L * 64 + 64 + 1);
     // ---- head: dpre_L = dz * wout, masked by a_L > 0; dw_out, db_out partials
     float dzr = 0.f;
@@ -322,7 +364,12 @@ __global__ __launch_bounds__(256, 2) void mlp_tail_bwd_kernel(const float *__res
         dzr *= p * (1.f - p);
         if (h == 0 && tz.dz_out != nullptr) tz.dz_out[row] = dzr;
     }
-    if (h == 0) dzs[32 * wv + i] = dzr;
+    if (h == 0) dzs[ri] = dzr;
+    // a_{l-1}, this lane's row as it was read: fetched one layer ahead (a_{L-1} beside a_L here, a_{l-2} behind layer l's
+    // matrix work) where the registers allow it; with three layers unrolled the rows are fetched at the top of their layer
+    constexpr bool kAhead = L <= 2;
+    f32x8 ap[4];
+    if (kAhead) mt_load_row((L - 1 == 0 ? a.act[0] + rowc * a.ldact0 : a.act[L - 1] + rowc * 64) + 8 * h, ap);
     f32x8 dp[4];  // dpre of the current layer, A layout (lane = row, k = 16 ks + 8 h ..)
     {
         const float *src = a.act[L] + rowc * 64 + 8 * h;
@@ -333,14 +380,22 @@ __global__ __launch_bounds__(256, 2) void mlp_tail_bwd_kernel(const float *__res
             for (int e = 0; e < 8; ++e) {
                 const float av = e < 4 ? v0[e] : v1[e - 4];
                 dp[ks][e] = av > 0.f ? dzr * wout[ks * 16 + 8 * h + e] : 0.f;
-                T1[wv][i][ks * 16 + 8 * h + e] = rok ? dzr * av : 0.f;  // dz * a_L: its column sums are dw_out
+                Dt[ks * 16 + 8 * h + e][ri] = dp[ks][e];
+                At[ks * 16 + 8 * h + e][ri] = rok ? dzr * av : 0.f;  // dz * a_L: its column sums are dw_out
             }
         }
     }
     __syncthreads();
-    if (threadIdx.x < 64) {  // dw_out[k] partial = sum over the workgroup's 128 rows, fixed order
+    if (threadIdx.x < 64) {  // dw_out[k] partial = sum over the workgroup's 128 rows in row order
         float s = 0.f;
-        for (int r = 0; r < 128; ++r) s += T1f[r][threadIdx.x];
+#pragma unroll 8
+        for (int j = 0; j < 32; ++j) {
+            const f32x4 v = *reinterpret_cast<const f32x4 *>(&At[threadIdx.x][4 * j]);
+            s += v[0];
+            s += v[1];
+            s += v[2];
+            s += v[3];
+        }
         Pg[(int64_t)L * 64 * 64 + (int64_t)L * 64 + threadIdx.x] = s;
     } else if (threadIdx.x == 64) {
         float s = 0.f;
@@ -349,20 +404,51 @@ __global__ __launch_bounds__(256, 2) void mlp_tail_bwd_kernel(const float *__res
     }
 #pragma unroll
     for (int ly = L; ly >= 1; --ly) {
-        __syncthreads();  // T0 / T1 / Wt of the previous layer are free
-        // dpre_ly -> T0 (row-major = the A layout), a_{ly-1} -> T1, W_ly^T -> Wt
+        if (!kAhead) mt_load_row((ly - 1 == 0 ? a.act[0] + rowc * a.ldact0 : a.act[ly - 1] + rowc * 64) + 8 * h, ap);
+        if (ly == L) __syncthreads();  // dw_out has been read out of At (below the first layer the barrier behind the
+                                       // dgrad has already freed both tiles)
+        // a_{ly-1} -> At (0 beyond M), transposed: a lane writes its row's 64 values one by one (the 32 lanes of a half write
+        // 32 consecutive floats).  Dt holds dpre_ly already: the head / the layer above wrote it transposed
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
-            for (int e = 0; e < 8; ++e) T0[wv][i][ks * 16 + 8 * h + e] = dp[ks][e];
-        {
-            const float *src = (ly - 1 == 0 ? a.act[0] + rowc * a.ldact0 : a.act[ly - 1] + rowc * 64) + 8 * h;
+            for (int e = 0; e < 8; ++e) At[ks * 16 + 8 * h + e][ri] = rok ? ap[ks][e] : 0.f;
+        __syncthreads();  // both tiles hold all 128 rows
+        // ---- weight gradient tile of this wave: dW[out = mt*32 + .., in = ntw*32 + ..] = sum over 128 rows in ONE
+        //      accumulator, k-steps of 16 rows in row order.  A = dpre^T (lane = out column), B = a^T (lane = in column): the
+        //      8 consecutive rows of a column a lane holds per k-step are two 16-byte reads
+        f32x16 wacc;
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const f32x4 v0 = *reinterpret_cast<const f32x4 *>(src + ks * 16), v1 = *reinterpret_cast<const f32x4 *>(src + ks * 16 + 4);
-                *reinterpret_cast<f32x4 *>(&T1[wv][i][ks * 16 + 8 * h]) = rok ? v0 : f32x4{0.f, 0.f, 0.f, 0.f};
-                *reinterpret_cast<f32x4 *>(&T1[wv][i][ks * 16 + 8 * h + 4]) = rok ? v1 : f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int r = 0; r < 16; ++r) wacc[r] = 0.f;
+        float bsum = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < 8; ++ks) {
+            const f32x4 a0 = *reinterpret_cast<const f32x4 *>(&Dt[mt * 32 + i][ks * 16 + 8 * h]);
+            const f32x4 a1 = *reinterpret_cast<const f32x4 *>(&Dt[mt * 32 + i][ks * 16 + 8 * h + 4]);
+            const f32x4 b0 = *reinterpret_cast<const f32x4 *>(&At[ntw * 32 + i][ks * 16 + 8 * h]);
+            const f32x4 b1 = *reinterpret_cast<const f32x4 *>(&At[ntw * 32 + i][ks * 16 + 8 * h + 4]);
+            f32x8 va, vb;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                va[e] = a0[e];
+                va[4 + e] = a1[e];
+                vb[e] = b0[e];
+                vb[4 + e] = b1[e];
             }
+            bsum += ((va[0] + va[1]) + (va[2] + va[3])) + ((va[4] + va[5]) + (va[6] + va[7]));
+            bf16x8 pa_[3], pb_[3];
+            bf_split8<3>(va, pa_);
+            bf_split8<3>(vb, pb_);
+#pragma unroll
+            for (int pr = 0; pr < 6; ++pr)
+                wacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa_[BfProd<6>::pa(pr)], pb_[BfProd<6>::pb(pr)], wacc, 0, 0, 0);
+        }
+        {   // partials: C layout col (in) = ntw*32 + i, row (out) = mt*32 + (r&3) + 8*(r>>2) + 4*h
+            float *Pw = Pg + (int64_t)(ly - 1) * 64 * 64;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) Pw[(mt * 32 + rp_mfma32_row(r, h)) * 64 + ntw * 32 + i] = wacc[r];
+            bsum += __shfl_xor(bsum, 32, 64);  // the two row halves
+            if (ntw == 0 && h == 0) Pg[(int64_t)L * 64 * 64 + (int64_t)(ly - 1) * 64 + mt * 32 + i] = bsum;
         }
         // W_ly^T fragments: lane (i, h) of fragment (nt, ks) holds W[out = 16 ks + 8 h + e][in = 32 nt + i], e = 0..7
         bf16x8 wf[2][4][3];
@@ -378,36 +464,6 @@ __global__ __launch_bounds__(256, 2) void mlp_tail_bwd_kernel(const float *__res
                     for (int e = 0; e < 8; ++e) v[e] = Wl[(int64_t)(ks * 16 + 8 * h + e) * ldw + nt * 32 + i];
                     bf_split8<3>(v, wf[nt][ks]);
                 }
-        }
-        __syncthreads();
-        // ---- weight gradient tile of this wave: dW[out = mt*32 + .., in = ntw*32 + ..] = sum over 128 rows
-        //      A = dpre^T (lane = out column, 8 consecutive rows per k-step), B = a^T (lane = in column)
-        f32x16 wacc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) wacc[r] = 0.f;
-        float bsum = 0.f;
-#pragma unroll
-        for (int ks = 0; ks < 8; ++ks) {
-            f32x8 va, vb;
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                va[e] = T0f[ks * 16 + 8 * h + e][mt * 32 + i];
-                vb[e] = T1f[ks * 16 + 8 * h + e][ntw * 32 + i];
-            }
-            bsum += ((va[0] + va[1]) + (va[2] + va[3])) + ((va[4] + va[5]) + (va[6] + va[7]));
-            bf16x8 pa_[3], pb_[3];
-            bf_split8<3>(va, pa_);
-            bf_split8<3>(vb, pb_);
-#pragma unroll
-            for (int pr = 0; pr < 6; ++pr)
-                wacc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pa_[BfProd<6>::pa(pr)], pb_[BfProd<6>::pb(pr)], wacc, 0, 0, 0);
-        }
-        {   // partials: C layout col (in) = ntw*32 + i, row (out) = mt*32 + (r&3) + 8*(r>>2) + 4*h
-            float *Pw = Pg + (int64_t)(ly - 1) * 64 * 64;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) Pw[(mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * h) * 64 + ntw * 32 + i] = wacc[r];
-            bsum += __shfl_xor(bsum, 32, 64);  // the two row halves
-            if (ntw == 0 && h == 0) Pg[(int64_t)L * 64 * 64 + (int64_t)(ly - 1) * 64 + mt * 32 + i] = bsum;
         }
         // ---- dgrad: da_{ly-1} = dpre_ly . W_ly  (contraction over the output index), masked by a_{ly-1} > 0
         f32x16 acc[2];
@@ -426,46 +482,74 @@ __global__ __launch_bounds__(256, 2) void mlp_tail_bwd_kernel(const float *__res
                     acc[nt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(af[BfProd<6>::pa(pr)], wf[nt][ks][BfProd<6>::pb(pr)], acc[nt], 0, 0, 0);
             }
         }
-        __syncthreads();  // every wave has finished reading T0 (wgrad): it now takes the masked gradient
+        if (kAhead && ly - 1 > 0) {
+            mt_load_row((ly - 2 == 0 ? a.act[0] + rowc * a.ldact0 : a.act[ly - 2] + rowc * 64) + 8 * h, ap);
+            __builtin_amdgcn_sched_barrier(0);  // issued HERE, not where the compiler finds their first use
+        }
+        // the mask in the C layout (col n = nt*32 + i, the wave's rows 8 g + 4 h + 0..3 in registers 4 g + 0..3): four rows
+        // of a column of At per read.  The last layer's result leaves for dhin here
 #pragma unroll
         for (int nt = 0; nt < 2; ++nt) {
             const int n = nt * 32 + i;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int rl = rp_mfma32_row(r, h);
-                const float v = T1[wv][rl][n] > 0.f ? acc[nt][r] : 0.f;
-                if (ly - 1 == 0) {
-                    const int64_t m = row0 + 32 * wv + rl;
-                    if (m < M) dhin[m * lddh + n] = v;
-                } else {
-                    T0[wv][rl][n] = v;
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 m4 = *reinterpret_cast<const f32x4 *>(&At[n][32 * wv + 8 * g + 4 * h]);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float v = m4[e] > 0.f ? acc[nt][4 * g + e] : 0.f;
+                    acc[nt][4 * g + e] = v;
+                    if (ly - 1 == 0) {
+                        const int64_t m = row0 + 32 * wv + 8 * g + 4 * h + e;
+                        if (m < M) dhin[m * lddh + n] = v;
+                    }
                 }
             }
         }
         if (ly - 1 > 0) {
-            __syncthreads();
+            __syncthreads();  // every wave has finished reading Dt and At
+            // the masked gradient is dpre_{ly-1}: from the C layout straight into the wave's rows of Dt (four rows of a
+            // column are 16 bytes), where the next layer's wgrad reads it, and back in the A layout for its dgrad
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                const f32x4 v0 = *reinterpret_cast<const f32x4 *>(&T0[wv][i][ks * 16 + 8 * h]);
-                const f32x4 v1 = *reinterpret_cast<const f32x4 *>(&T0[wv][i][ks * 16 + 8 * h + 4]);
+            for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    dp[ks][e] = v0[e];
-                    dp[ks][4 + e] = v1[e];
+                for (int g = 0; g < 4; ++g) {
+                    f32x4 v;
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) v[e] = acc[nt][4 * g + e];
+                    *reinterpret_cast<f32x4 *>(&Dt[nt * 32 + i][32 * wv + 8 * g + 4 * h]) = v;
                 }
-            }
+            mt_wave_sync();
+#pragma unroll
+            for (int ks = 0; ks < 4; ++ks)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) dp[ks][e] = Dt[ks * 16 + 8 * h + e][ri];
         }
     }
 }
 
-// out[e] = sum over workgroups of P[g][e], fixed order (16 slices x 16 elements per block, as the wgrad second stage)
-__global__ __launch_bounds__(256) void mlp_tail_reduce_kernel(const float *__restrict__ P, int nwg, int64_t per, float *__restrict__ out) {
-    __shared__ float red[16][17];
-    const int c = threadIdx.x & 15, q = threadIdx.x >> 4;
-    const int64_t e = (int64_t)blockIdx.x * 16 + c;
+// out[e] = sum over workgroups of P[g][e] in a fixed order: 16 interleaved slices (slice q adds g = q, q + 16, .. in that
+// order), then the 16 slice sums in order.  A block takes 64 consecutive elements and a wave one slice of them, so a wave
+// reads 256 contiguous bytes per workgroup (`per` is odd: nothing wider than 4 bytes per lane stays aligned), eight
+// workgroups in flight per lane.
+#define MT_RED_E 64
+__global__ __launch_bounds__(1024) void mlp_tail_reduce_kernel(const float *__restrict__ P, int nwg, int64_t per, float *__restrict__ out) {
+    __shared__ float red[16][MT_RED_E];
+    const int c = threadIdx.x & (MT_RED_E - 1), q = threadIdx.x / MT_RED_E;
+    const int64_t e = (int64_t)blockIdx.x * MT_RED_E + c;
     float s = 0.f;
-    if (e < per)
-        for (int g = q; g < nwg; g += 16) s += P[(int64_t)g * per + e];
+    if (e < per) {
+        const float *p = P + (int64_t)q * per + e;
+        const int64_t st = 16 * per;
+        int g = q;
+        for (; g + 16 * 7 < nwg; g += 16 * 8, p += 8 * st) {
+            float x[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) x[u] = p[u * st];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) s += x[u];
+        }
+        for (; g < nwg; g += 16, p += st) s += p[0];
+    }
     red[q][c] = s;
     __syncthreads();
     if (q != 0 || e >= per) return;
@@ -525,7 +609,7 @@ static int tail_bwd_launch(const float *dz, const TailDz &tz, int n_hidden, cons
         RP_LAUNCH_CHECK("mlp_tail_bwd");
     }
     if (parts & 2) {
-        hipLaunchKernelGGL(mlp_tail_reduce_kernel, dim3((unsigned)rp_cdiv(per, 16)), dim3(256), 0, s, P, nwg, per, grads);
+        hipLaunchKernelGGL(mlp_tail_reduce_kernel, dim3((unsigned)rp_cdiv(per, MT_RED_E)), dim3(16 * MT_RED_E), 0, s, P, nwg, per, grads);
         RP_LAUNCH_CHECK("mlp_tail_bwd (partials)");
     }
     return RP_OK;
