@@ -287,10 +287,57 @@ int rp_linear_wgrad(const float *dy, int64_t lddy, const float *x, int64_t ldx, 
                     float *db, int64_t M, int N, int K, int accumulate, void *workspace,
                     size_t workspace_bytes, rp_stream_t stream);
 /* the same with the activation stored as bf16 (x_bf16 [M, ldx] bf16, ldx even, 4-byte aligned; the bf16-storage training
- * mode): half the bytes of the dominant operand; bf16 matrix-core modes and N <= 128 only (RP_ERR_UNSUPPORTED otherwise) */
+ * mode): half the bytes of the dominant operand; bf16 matrix-core modes and N < 128 only (RP_ERR_UNSUPPORTED otherwise) */
 int rp_linear_wgrad_xbf16(const float *dy, int64_t lddy, const void *x_bf16, int64_t ldx, float *dw, int64_t lddw,
                           float *db, int64_t M, int N, int K, int accumulate, void *workspace, size_t workspace_bytes,
                           rp_stream_t stream);
+/* Which launch form the three entry points above choose for a shape, under the matmul precision in force.  Pure host
+ * functions (no device call): the entry points switch on the same result.  `out` receives RP_GEMM_FORM_INTS ints, indexed
+ * by the slots below; slots a family does not use are 0.
+ *   rp_linear_fwd_form:   a_aligned16 / w_aligned16 = the pointer is 16-byte aligned.  RP_GEMM_FWD_COLSPLIT issues
+ *     rp_linear_fwd on [M, SPLIT_NB] and on [M, N - SPLIT_NB] (same strides and alignment), each with a form of its own.
+ *   rp_linear_wgrad_form: x_align_bytes = the largest power of two (<= 16) dividing the address of x; x_is_bf16 = 1 asks
+ *     for rp_linear_wgrad_xbf16 and returns RP_ERR_UNSUPPORTED exactly where that entry point does. */
+#define RP_GEMM_FORM_INTS 16
+#define RP_GEMM_FAMILY 0 /* RP_GEMM_FWD_* / RP_GEMM_WGRAD_* */
+#define RP_GEMM_NPROD 1  /* matrix-core products per flop: 0 (an f32 kernel), 1, 3, 6 */
+#define RP_GEMM_FWD_TILE 2        /* tiled: RP_GEMM_TILE_* */
+#define RP_GEMM_FWD_VEC_A 3       /* rows of a fetched as 16-byte vectors (lda % 4 == 0, aligned pointer) */
+#define RP_GEMM_FWD_VEC_W 4
+#define RP_GEMM_FWD_SK_LAUNCHES 5 /* short K: RP_GEMM_SK_* bits, the launches issued */
+#define RP_GEMM_FWD_SK_PER 6      /* short K: column tiles per workgroup of the first launch */
+#define RP_GEMM_FWD_GRID_X 7      /* grid of the (first) launch */
+#define RP_GEMM_FWD_GRID_Y 8
+#define RP_GEMM_FWD_POST_ACT 9    /* an rp_act_fwd launch follows in place (tanh / sigmoid / leaky behind short K) */
+#define RP_GEMM_FWD_SPLIT_NB 10   /* column split: the columns of the first launch */
+#define RP_GEMM_WGRAD_NA 2        /* 64-column output tiles per workgroup (bf16 kernels) */
+#define RP_GEMM_WGRAD_VEC_X 3     /* f32 kernel: 16-byte rows of x; bf16 kernels: 8-byte rows (1 for a bf16 activation) */
+#define RP_GEMM_WGRAD_VEC_Y 4     /* f32 kernel only */
+#define RP_GEMM_WGRAD_S 5         /* batch splits = partial results in the workspace */
+#define RP_GEMM_WGRAD_ROWS 6      /* batch rows per split */
+#define RP_GEMM_WGRAD_GRID_X 7
+#define RP_GEMM_WGRAD_GRID_Y 8
+#define RP_GEMM_WGRAD_GRID_Z 9
+#define RP_GEMM_FWD_F32 0
+#define RP_GEMM_FWD_SHORTK 1
+#define RP_GEMM_FWD_COLSPLIT 2
+#define RP_GEMM_FWD_WIDE 3  /* 256 x 128 tiles */
+#define RP_GEMM_FWD_TILED 4
+#define RP_GEMM_TILE_128X128 0   /* eight waves */
+#define RP_GEMM_TILE_128X64_8W 1 /* eight waves */
+#define RP_GEMM_TILE_128X64_4W 2 /* four waves */
+#define RP_GEMM_SK_INTERIOR 1 /* the straight-line kernel over the whole 128 x 64 tiles */
+#define RP_GEMM_SK_RIGHT 2    /* guarded: all rows, the last partial column tile */
+#define RP_GEMM_SK_BOTTOM 4   /* guarded: the last rows over the interior columns */
+#define RP_GEMM_SK_GUARDED 8  /* no interior: one guarded launch over everything */
+#define RP_GEMM_WGRAD_F32 0
+#define RP_GEMM_WGRAD_NARROW 1 /* 64 x 128 output tiles */
+#define RP_GEMM_WGRAD_WIDE 2   /* 128 x 128 output tiles, XCD-local 1-D grid */
+#define RP_GEMM_WGRAD_XBF16 3
+int rp_linear_fwd_form(int64_t M, int N, int K, int64_t lda, int64_t ldw, int a_aligned16, int w_aligned16, int act,
+                       int *out);
+int rp_linear_wgrad_form(int64_t M, int N, int K, int64_t lddy, int64_t ldx, int dy_aligned16, int x_align_bytes,
+                         int x_is_bf16, int *out);
 /* out[C,R] = in[R,C]^T (weights for the dgrad GEMM); rows C .. C_out-1 of out (C_out >= C) are written as zeros */
 int rp_transpose(const float *in, int64_t ldin, float *out, int64_t ldout, int R, int C, int C_out, rp_stream_t stream);
 /* rp_transpose and rp_copy_rows of the same matrix in ONE launch: out = in^T as rp_transpose, copy[r, 0:C] = in[r, 0:C] with

@@ -762,18 +762,25 @@ __global__ __launch_bounds__(256) void linear_fwd_bf16_smallk_kernel(const float
     }
 }
 
-template <int NPROD>
-static void launch_smallk(bool full, const float *a, int64_t lda, const float *w, int64_t ldw, const float *bias,
-                          float *out, int64_t ldo, int64_t M, int N, int K, int act, const float *aux, int64_t ldaux,
-                          hipStream_t s) {
-    // split the column tiles over gridDim.y only as far as needed to fill the chip (each split re-reads the A tile)
+// split the column tiles over gridDim.y only as far as needed to fill the chip (each split re-reads the A tile)
+static void smallk_grid(int64_t M, int N, int *per, int *gx, int *gy) {
     const int64_t mb = rp_cdiv(M, 128);
     const int tiles = (int)rp_cdiv(N, BN);
     int64_t ysplit = rp_cdiv(768, mb);
     if (ysplit > tiles) ysplit = tiles;
     if (ysplit < 1) ysplit = 1;
-    const int per = (int)rp_cdiv(tiles, ysplit);
-    dim3 grid((unsigned)mb, (unsigned)rp_cdiv(tiles, per));
+    *per = (int)rp_cdiv(tiles, ysplit);
+    *gx = (int)mb;
+    *gy = (int)rp_cdiv(tiles, *per);
+}
+
+template <int NPROD>
+static void launch_smallk(bool full, const float *a, int64_t lda, const float *w, int64_t ldw, const float *bias,
+                          float *out, int64_t ldo, int64_t M, int N, int K, int act, const float *aux, int64_t ldaux,
+                          hipStream_t s) {
+    int per, gx, gy;
+    smallk_grid(M, N, &per, &gx, &gy);
+    dim3 grid((unsigned)gx, (unsigned)gy);
 #define SK(ACT, FULL)                                                                                                  \
     hipLaunchKernelGGL((linear_fwd_bf16_smallk_kernel<NPROD, ACT, FULL>), grid, dim3(256), 0, s, a, lda, w, ldw, bias, \
                        out, ldo, M, N, K, aux, ldaux, per)
@@ -789,13 +796,12 @@ static void launch_smallk(bool full, const float *a, int64_t lda, const float *w
 #undef SK
 }
 
-// interior region with the straight-line kernel, the right / bottom edges with the guarded one
+// interior region (Mf x Nf, chosen by linear_fwd_form) with the straight-line kernel, the right / bottom edges with the
+// guarded one; Mf = 0: one guarded launch over everything
 template <int NPROD>
-static void run_smallk(const float *a, int64_t lda, const float *w, int64_t ldw, const float *bias, float *out,
-                       int64_t ldo, int64_t M, int N, int K, int act, const float *aux, int64_t ldaux, hipStream_t s) {
-    const bool aligned = (lda % 4 == 0) && (ldw % 4 == 0) && rp_aligned16(a) && rp_aligned16(w) && (K % 4 == 0);
-    const int64_t Mf = aligned ? (M / 128) * 128 : 0;
-    const int Nf = aligned ? (N / BN) * BN : 0;
+static void run_smallk(int64_t Mf, int Nf, const float *a, int64_t lda, const float *w, int64_t ldw, const float *bias,
+                       float *out, int64_t ldo, int64_t M, int N, int K, int act, const float *aux, int64_t ldaux,
+                       hipStream_t s) {
     if (Mf > 0 && Nf > 0)
         launch_smallk<NPROD>(true, a, lda, w, ldw, bias, out, ldo, Mf, Nf, K, act, aux, ldaux, s);
     else {
@@ -1109,13 +1115,9 @@ template <int NPROD>
 static void launch_smallk_rowadd(const float *a, int64_t lda, const float *w, int64_t ldw, float *out, int64_t ldo,
                                  int64_t M, int N, int K, const float *rs, const float *radd, int64_t ldadd, int nadd,
                                  hipStream_t s) {
-    const int64_t mb = M / 128;
-    const int tiles = N / BN;
-    int64_t ysplit = rp_cdiv(768, mb);
-    if (ysplit > tiles) ysplit = tiles;
-    if (ysplit < 1) ysplit = 1;
-    const int per = (int)rp_cdiv(tiles, ysplit);
-    dim3 grid((unsigned)mb, (unsigned)rp_cdiv(tiles, per));
+    int per, gx, gy;
+    smallk_grid(M, N, &per, &gx, &gy);  // (M % 128 == 0, N % 64 == 0)
+    dim3 grid((unsigned)gx, (unsigned)gy);
     hipLaunchKernelGGL((linear_fwd_bf16_smallk_kernel<NPROD, RP_ACT_NONE, true, true>), grid, dim3(256), 0, s, a, lda, w, ldw,
                        nullptr, out, ldo, M, N, K, nullptr, 0, per, rs, radd, ldadd, nadd);
 }
@@ -1172,6 +1174,107 @@ extern "C" int rp_linear_fwd_rowadd(const float *a, int64_t lda, const float *w,
     return RP_OK;
 }
 
+// ---- which launch form serves a shape -------------------------------------------------------------------------------
+// Decided here, once, by pure host functions (no device call): the entry points below switch on the result, and
+// rp_linear_fwd_form / rp_linear_wgrad_form hand the same result to a caller (a test asks which instantiation a shape
+// reaches before it judges the numbers).  The fields are the RP_GEMM_* slots of include/rec_pangu_hip.h.
+struct FwdForm {
+    int family = 0;    // RP_GEMM_FWD_*
+    int nprod = 0;     // matrix-core products per flop: 0 (the f32 kernel), 1, 3, 6
+    int tile = 0;      // tiled: RP_GEMM_TILE_*
+    int va = 0, vw = 0;
+    int launches = 0;  // short-K: RP_GEMM_SK_* bits
+    int per = 0;       // short-K: column tiles per workgroup of the first launch
+    int gx = 0, gy = 0;  // grid of the (first) launch
+    int post = 0;      // an rp_act_fwd launch follows in place
+    int nb = 0;        // column split: the columns of the first launch
+    int64_t mf = 0;    // short-K: the interior is mf x nf
+    int nf = 0;
+    int act_k = 0;     // short-K: the epilogue the kernel is instantiated with
+};
+
+static FwdForm linear_fwd_form(int64_t M, int N, int K, int64_t lda, int64_t ldw, bool a16, bool w16, int act) {
+    FwdForm f;
+    f.va = (lda % 4 == 0) && a16;
+    f.vw = (ldw % 4 == 0) && w16;
+    const int mode = linear_mode(M, N, K);
+    if (mode == RP_MATMUL_FP32) {
+        f.family = RP_GEMM_FWD_F32;
+        f.gx = (int)rp_cdiv(M, BM);
+        f.gy = (int)rp_cdiv(N, BN);
+        return f;
+    }
+    f.nprod = mode == RP_MATMUL_BF16X6 ? 6 : mode == RP_MATMUL_BF16X3 ? 3 : 1;
+    if (K <= 64) {  // A-stationary walk over the output columns
+        // (its epilogue is a template parameter: tanh / sigmoid / leaky ReLU follow as one elementwise launch in place)
+        f.family = RP_GEMM_FWD_SHORTK;
+        f.post = act == RP_ACT_TANH || act == RP_ACT_SIGMOID || act == RP_ACT_LEAKY;
+        f.act_k = f.post ? RP_ACT_NONE : act;
+        const bool aligned = f.va && f.vw && (K % 4 == 0);
+        f.mf = aligned ? (M / 128) * 128 : 0;
+        f.nf = aligned ? (N / BN) * BN : 0;
+        if (f.mf > 0 && f.nf > 0) {
+            f.launches = RP_GEMM_SK_INTERIOR | (N > f.nf ? RP_GEMM_SK_RIGHT : 0) | (M > f.mf ? RP_GEMM_SK_BOTTOM : 0);
+            smallk_grid(f.mf, f.nf, &f.per, &f.gx, &f.gy);
+        } else {
+            f.mf = 0;
+            f.nf = 0;
+            f.launches = RP_GEMM_SK_GUARDED;
+            smallk_grid(M, N, &f.per, &f.gx, &f.gy);
+        }
+        return f;
+    }
+    // a wide output that is not a multiple of 128 columns (the MMOE expert + gate GEMM: 520): the whole 128-column
+    // tiles go to the 128 x 128 kernel, the few columns left to a second launch (463 -> 377 us at M = 65536,
+    // K = 649: otherwise either a fifth, almost empty 128-wide tile or nine LDS-bound 64-wide tiles)
+    const int Nb = (N / 128) * 128;
+    if (N >= 256 && Nb < N && rp_cdiv(M, 128) * (Nb / 128) >= 1024) {
+        f.family = RP_GEMM_FWD_COLSPLIT;  // (each of the two launches has a form of its own: [M, Nb] and [M, N - Nb])
+        f.nb = Nb;
+        return f;
+    }
+    // wide, matrix-core-bound layers in a two-piece mode: 256 x 128 tiles, 64 x 64 wave tiles, double-buffered LDS
+    if ((mode == RP_MATMUL_BF16X3 || mode == RP_MATMUL_BF16) && N >= 256 && N % 32 == 0 && M % 256 == 0 && K >= 192 &&
+        f.va && f.vw && rp_cdiv(N, 128) * (M / 256) >= 512) {
+        f.family = RP_GEMM_FWD_WIDE;
+        f.gx = (int)(rp_cdiv(M / 256, 8) * 8 * rp_cdiv(N, 128));
+        f.gy = 1;
+        return f;
+    }
+    // tile shape: 128 x 128 (eight waves of 32 x 64) for wide outputs; 128 x 64 otherwise — with eight waves when that grid
+    // would give the 256 CUs fewer than ~4 workgroups each
+    f.family = RP_GEMM_FWD_TILED;
+    const int64_t n128 = rp_cdiv(N, 128) * 128;
+    const bool big = N >= 256 && (n128 - N) * 8 <= N && rp_cdiv(M, 128) * (n128 / 128) >= 1024;
+    const bool small = !big && rp_cdiv(M, 128) * rp_cdiv(N, BN) < 1024 && M > 64;
+    f.tile = big ? RP_GEMM_TILE_128X128 : small ? RP_GEMM_TILE_128X64_8W : RP_GEMM_TILE_128X64_4W;
+    f.gx = (int)rp_cdiv(M, 128);
+    f.gy = (int)rp_cdiv(N, big ? 128 : BN);
+    return f;
+}
+
+extern "C" int rp_linear_fwd_form(int64_t M, int N, int K, int64_t lda, int64_t ldw, int a_aligned16, int w_aligned16,
+                                  int act, int *out) {
+    RP_REQUIRE(out, "linear_fwd_form: null pointer");
+    RP_REQUIRE(M >= 1 && N >= 1 && K >= 1, "linear_fwd_form: bad M/N/K");
+    RP_REQUIRE(lda >= K && ldw >= K, "linear_fwd_form: leading dimension too small");
+    RP_REQUIRE(act >= RP_ACT_NONE && act <= RP_ACT_LEAKY, "linear_fwd_form: bad act");
+    const FwdForm f = linear_fwd_form(M, N, K, lda, ldw, a_aligned16 != 0, w_aligned16 != 0, act);
+    for (int i = 0; i < RP_GEMM_FORM_INTS; ++i) out[i] = 0;
+    out[RP_GEMM_FAMILY] = f.family;
+    out[RP_GEMM_NPROD] = f.nprod;
+    out[RP_GEMM_FWD_TILE] = f.tile;
+    out[RP_GEMM_FWD_VEC_A] = f.va;
+    out[RP_GEMM_FWD_VEC_W] = f.vw;
+    out[RP_GEMM_FWD_SK_LAUNCHES] = f.launches;
+    out[RP_GEMM_FWD_SK_PER] = f.per;
+    out[RP_GEMM_FWD_GRID_X] = f.gx;
+    out[RP_GEMM_FWD_GRID_Y] = f.gy;
+    out[RP_GEMM_FWD_POST_ACT] = f.post;
+    out[RP_GEMM_FWD_SPLIT_NB] = f.nb;
+    return RP_OK;
+}
+
 extern "C" int rp_linear_fwd(const float *a, int64_t lda, const float *w, int64_t ldw, const float *bias, float *out,
                              int64_t ldo, int64_t M, int N, int K, int act, const float *aux, int64_t ldaux,
                              rp_stream_t stream) {
@@ -1182,39 +1285,29 @@ extern "C" int rp_linear_fwd(const float *a, int64_t lda, const float *w, int64_
                    act == RP_ACT_TANH || act == RP_ACT_SIGMOID || act == RP_ACT_LEAKY,
                "linear_fwd: bad act/aux");
     if (M == 0) return RP_OK;
-    const bool va = (lda % 4 == 0) && rp_aligned16(a);
-    const bool vw = (ldw % 4 == 0) && rp_aligned16(w);
+    const FwdForm f = linear_fwd_form(M, N, K, lda, ldw, rp_aligned16(a), rp_aligned16(w), act);
+    const bool va = f.va, vw = f.vw;
     hipStream_t s = (hipStream_t)stream;
-    const int mode = linear_mode(M, N, K);
-    if (mode != RP_MATMUL_FP32) {
-        if (K <= 64) {  // A-stationary walk over the output columns
-            // (its epilogue is a template parameter: tanh / sigmoid / leaky ReLU follow as one elementwise launch in place)
-            const bool post = act == RP_ACT_TANH || act == RP_ACT_SIGMOID || act == RP_ACT_LEAKY;
-            const int act_k = post ? RP_ACT_NONE : act;
-            if (mode == RP_MATMUL_BF16X6) run_smallk<6>(a, lda, w, ldw, bias, out, ldo, M, N, K, act_k, aux, ldaux, s);
-            else if (mode == RP_MATMUL_BF16X3) run_smallk<3>(a, lda, w, ldw, bias, out, ldo, M, N, K, act_k, aux, ldaux, s);
-            else run_smallk<1>(a, lda, w, ldw, bias, out, ldo, M, N, K, act_k, aux, ldaux, s);
+    if (f.family != RP_GEMM_FWD_F32) {
+        if (f.family == RP_GEMM_FWD_SHORTK) {
+            if (f.nprod == 6) run_smallk<6>(f.mf, f.nf, a, lda, w, ldw, bias, out, ldo, M, N, K, f.act_k, aux, ldaux, s);
+            else if (f.nprod == 3) run_smallk<3>(f.mf, f.nf, a, lda, w, ldw, bias, out, ldo, M, N, K, f.act_k, aux, ldaux, s);
+            else run_smallk<1>(f.mf, f.nf, a, lda, w, ldw, bias, out, ldo, M, N, K, f.act_k, aux, ldaux, s);
             RP_LAUNCH_CHECK("linear_fwd (bf16 split, short K)");
-            if (post) return rp_act_fwd(out, ldo, out, ldo, M, N, act, stream);
+            if (f.post) return rp_act_fwd(out, ldo, out, ldo, M, N, act, stream);
             return RP_OK;
         }
-        // a wide output that is not a multiple of 128 columns (the MMOE expert + gate GEMM: 520): the whole 128-column
-        // tiles go to the 128 x 128 kernel, the few columns left to a second launch (463 -> 377 us at M = 65536,
-        // K = 649: otherwise either a fifth, almost empty 128-wide tile or nine LDS-bound 64-wide tiles)
-        const int Nb = (N / 128) * 128;
-        if (N >= 256 && Nb < N && rp_cdiv(M, 128) * (Nb / 128) >= 1024) {
+        if (f.family == RP_GEMM_FWD_COLSPLIT) {
+            const int Nb = f.nb;
             int rc = rp_linear_fwd(a, lda, w, ldw, bias, out, ldo, M, Nb, K, act, aux, ldaux, stream);
             if (rc != RP_OK) return rc;
             return rp_linear_fwd(a, lda, w + (int64_t)Nb * ldw, ldw, bias ? bias + Nb : nullptr, out + Nb, ldo, M, N - Nb, K,
                                  act, aux ? aux + Nb : nullptr, ldaux, stream);
         }
-        // wide, matrix-core-bound layers in a two-piece mode: 256 x 128 tiles, 64 x 64 wave tiles, double-buffered LDS
-        if ((mode == RP_MATMUL_BF16X3 || mode == RP_MATMUL_BF16) && N >= 256 && N % 32 == 0 && M % 256 == 0 &&
-            K >= 192 && va && vw && rp_cdiv(N, 128) * (M / 256) >= 512) {
+        if (f.family == RP_GEMM_FWD_WIDE) {
             const int mblocks = (int)(M / 256), nblocks = (int)rp_cdiv(N, 128);
-            const int groups = (int)rp_cdiv(mblocks, 8);
-            dim3 gridw((unsigned)(groups * 8 * nblocks));
-            if (mode == RP_MATMUL_BF16X3)
+            dim3 gridw((unsigned)f.gx);
+            if (f.nprod == 3)
                 hipLaunchKernelGGL((linear_fwd_bf16_wide_kernel<3>), gridw, dim3(512), 0, s, a, lda, w, ldw, bias, out, ldo, M, N, K,
                                    act, aux, ldaux, mblocks, nblocks);
             else
@@ -1223,12 +1316,8 @@ extern "C" int rp_linear_fwd(const float *a, int64_t lda, const float *w, int64_
             RP_LAUNCH_CHECK("linear_fwd (bf16 split, wide)");
             return RP_OK;
         }
-        // tile shape: 128 x 128 (eight waves of 32 x 64) for wide outputs; 128 x 64 otherwise — with eight waves when that grid
-        // would give the 256 CUs fewer than ~4 workgroups each
-        const int64_t n128 = rp_cdiv(N, 128) * 128;
-        const bool big = N >= 256 && (n128 - N) * 8 <= N && rp_cdiv(M, 128) * (n128 / 128) >= 1024;
-        const bool small = !big && rp_cdiv(M, 128) * rp_cdiv(N, BN) < 1024 && M > 64;
-        dim3 grid((unsigned)rp_cdiv(M, 128), (unsigned)rp_cdiv(N, big ? 128 : BN));
+        const bool big = f.tile == RP_GEMM_TILE_128X128, small = f.tile == RP_GEMM_TILE_128X64_8W;
+        dim3 grid((unsigned)f.gx, (unsigned)f.gy);
 #define CALLB(NPROD, WM, WN, MI, NI, PF, VA, VW)                                                                      \
     hipLaunchKernelGGL((linear_fwd_bf16_kernel<NPROD, WM, WN, MI, NI, PF, VA, VW>), grid, dim3(64 * WM * WN), 0, s, a, lda, w, \
                        ldw, bias, out, ldo, M, N, K, act, aux, ldaux)
@@ -1245,8 +1334,8 @@ extern "C" int rp_linear_fwd(const float *a, int64_t lda, const float *w, int64_
         else if (small) CALLV(NPROD, 4, 2, 1, 1, 2); \
         else CALLV(NPROD, 4, 1, 1, 2, 2);         \
     } while (0)
-        if (mode == RP_MATMUL_BF16X6) CALLP(6);
-        else if (mode == RP_MATMUL_BF16X3) CALLP(3);
+        if (f.nprod == 6) CALLP(6);
+        else if (f.nprod == 3) CALLP(3);
         else CALLP(1);
 #undef CALLP
 #undef CALLV
@@ -1254,7 +1343,7 @@ extern "C" int rp_linear_fwd(const float *a, int64_t lda, const float *w, int64_
         RP_LAUNCH_CHECK("linear_fwd (bf16 split)");
         return RP_OK;
     }
-    dim3 grid((unsigned)rp_cdiv(M, BM), (unsigned)rp_cdiv(N, BN));
+    dim3 grid((unsigned)f.gx, (unsigned)f.gy);
 #define CALL(VA, VW)                                                                                              \
     hipLaunchKernelGGL((linear_fwd_kernel<VA, VW>), grid, dim3(256), 0, s, a, lda, w, ldw, bias, out, ldo, M, N, K, \
                        act, aux, ldaux)
@@ -1311,6 +1400,84 @@ extern "C" int rp_linear_wgrad_workspace_bytes(int64_t M, int N, int K, size_t *
     return RP_OK;
 }
 
+struct WgradForm {
+    int family = 0;  // RP_GEMM_WGRAD_*
+    int nprod = 0;   // 0 (the f32 partial kernel), 1, 3, 6
+    int na = 0;      // 64-column output tiles per workgroup (bf16 kernels)
+    int vx = 0;      // VEC_X: f32 kernel 16-byte rows of x, bf16 kernels 8-byte rows (always set for a bf16 activation)
+    int vy = 0;      // VEC_Y (f32 kernel only)
+    int S = 0;       // batch splits
+    int64_t rows = 0;  // batch rows per split
+    int gx = 0, gy = 0, gz = 0;
+    int xcd_tiles = 0;  // wide: output tiles per split of the XCD-local 1-D grid
+};
+
+static int ptr_align_bytes(const void *p) {  // the largest power of two <= 16 that divides the address
+    const uintptr_t a = reinterpret_cast<uintptr_t>(p);
+    return a % 16 == 0 ? 16 : a % 8 == 0 ? 8 : a % 4 == 0 ? 4 : a % 2 == 0 ? 2 : 1;
+}
+
+#define WGRAD_XBF16_REFUSAL "linear_wgrad_xbf16: bf16 matrix-core modes, N < 128, ldx even, 4-byte aligned x only"
+
+// false: rp_linear_wgrad_xbf16 refuses the shape (RP_ERR_UNSUPPORTED); rp_linear_wgrad serves every shape
+static bool linear_wgrad_form(int64_t M, int N, int K, int64_t lddy, int64_t ldx, bool dy16, int x_align, bool x_bf16,
+                              WgradForm *f) {
+    const int mode = linear_mode(M, N, K);
+    if (x_bf16 && (mode == RP_MATMUL_FP32 || wgrad_wide(N) || ldx % 2 != 0 || x_align < 4)) return false;
+    wgrad_plan(M, N, K, &f->S, &f->rows);
+    f->gx = (int)rp_cdiv(K, TN_BK);
+    f->gy = (int)rp_cdiv(N, TN_BN);
+    f->gz = f->S;
+    if (mode == RP_MATMUL_FP32) {
+        f->family = RP_GEMM_WGRAD_F32;
+        f->vy = (lddy % 4 == 0) && dy16;
+        f->vx = (ldx % 4 == 0) && x_align >= 16;
+        return true;
+    }
+    f->nprod = mode == RP_MATMUL_BF16X6 ? 6 : mode == RP_MATMUL_BF16X3 ? 3 : 1;
+    if (x_bf16) {
+        f->family = RP_GEMM_WGRAD_XBF16;
+        f->na = 1;
+        f->vx = 1;
+        return true;
+    }
+    f->vx = (ldx % 2 == 0) && x_align >= 8;
+    const bool wide = wgrad_wide(N);
+    f->family = wide ? RP_GEMM_WGRAD_WIDE : RP_GEMM_WGRAD_NARROW;
+    f->na = wide ? 2 : 1;
+    if (wide) {  // the XCD-local 1-D grid: whole groups of eight splits, the blocks past S return at once
+        f->gy = (int)rp_cdiv(N, 2 * TN_BN);
+        f->xcd_tiles = f->gx * f->gy;
+        f->gx = (int)(8 * rp_cdiv(f->S, 8) * f->xcd_tiles);
+        f->gy = 1;
+        f->gz = 1;
+    }
+    return true;
+}
+
+extern "C" int rp_linear_wgrad_form(int64_t M, int N, int K, int64_t lddy, int64_t ldx, int dy_aligned16, int x_align_bytes,
+                                    int x_is_bf16, int *out) {
+    RP_REQUIRE(out, "linear_wgrad_form: null pointer");
+    RP_REQUIRE(M >= 1 && N >= 1 && K >= 1, "linear_wgrad_form: bad M/N/K");
+    RP_REQUIRE(lddy >= N && ldx >= K, "linear_wgrad_form: leading dimension too small");
+    WgradForm f;
+    if (!linear_wgrad_form(M, N, K, lddy, ldx, dy_aligned16 != 0, x_align_bytes, x_is_bf16 != 0, &f))
+        return rp_fail(RP_ERR_UNSUPPORTED, WGRAD_XBF16_REFUSAL);
+    RP_REQUIRE(f.rows <= INT32_MAX, "linear_wgrad_form: %lld rows per split do not fit an int", (long long)f.rows);
+    for (int i = 0; i < RP_GEMM_FORM_INTS; ++i) out[i] = 0;
+    out[RP_GEMM_FAMILY] = f.family;
+    out[RP_GEMM_NPROD] = f.nprod;
+    out[RP_GEMM_WGRAD_NA] = f.na;
+    out[RP_GEMM_WGRAD_VEC_X] = f.vx;
+    out[RP_GEMM_WGRAD_VEC_Y] = f.vy;
+    out[RP_GEMM_WGRAD_S] = f.S;
+    out[RP_GEMM_WGRAD_ROWS] = (int)f.rows;
+    out[RP_GEMM_WGRAD_GRID_X] = f.gx;
+    out[RP_GEMM_WGRAD_GRID_Y] = f.gy;
+    out[RP_GEMM_WGRAD_GRID_Z] = f.gz;
+    return RP_OK;
+}
+
 extern "C" int rp_linear_wgrad(const float *dy, int64_t lddy, const float *x, int64_t ldx, float *dw, int64_t lddw,
                                float *db, int64_t M, int N, int K, int accumulate, void *workspace,
                                size_t workspace_bytes, rp_stream_t stream) {
@@ -1320,22 +1487,19 @@ extern "C" int rp_linear_wgrad(const float *dy, int64_t lddy, const float *x, in
     size_t need = 0;
     rp_linear_wgrad_workspace_bytes(M, N, K, &need);
     RP_REQUIRE(workspace_bytes >= need, "linear_wgrad: workspace %zu < %zu bytes", workspace_bytes, need);
-    int S;
-    int64_t rows;
-    wgrad_plan(M, N, K, &S, &rows);
+    WgradForm f;
+    linear_wgrad_form(M, N, K, lddy, ldx, rp_aligned16(dy), ptr_align_bytes(x), false, &f);
+    const int S = f.S;
+    const int64_t rows = f.rows;
     float *P = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
     float *Pb = P + (size_t)S * N * K;
-    const bool vy = (lddy % 4 == 0) && rp_aligned16(dy);
-    const bool vx = (ldx % 4 == 0) && rp_aligned16(x);
-    dim3 grid((unsigned)rp_cdiv(K, TN_BK), (unsigned)rp_cdiv(N, TN_BN), (unsigned)S);
+    const bool vy = f.vy, vx = f.vx;
+    dim3 grid((unsigned)f.gx, (unsigned)f.gy, (unsigned)f.gz);
     hipStream_t s = (hipStream_t)stream;
-    const int mode = linear_mode(M, N, K);
-    if (mode != RP_MATMUL_FP32) {
-        const bool vx2 = (ldx % 2 == 0) && (reinterpret_cast<uintptr_t>(x) % 8 == 0);
-        const bool wide = wgrad_wide(N);
-        dim3 gridb((unsigned)rp_cdiv(K, TN_BK), (unsigned)rp_cdiv(N, wide ? 2 * TN_BN : TN_BN), (unsigned)S);
-        const int xt = wide ? (int)(gridb.x * gridb.y) : 0, xk = (int)gridb.x;  // (wide: the XCD-local 1-D grid)
-        if (wide) gridb = dim3((unsigned)(8 * rp_cdiv(S, 8) * xt), 1u, 1u);
+    if (f.family != RP_GEMM_WGRAD_F32) {
+        const bool vx2 = f.vx, wide = f.family == RP_GEMM_WGRAD_WIDE;
+        const dim3 gridb = grid;
+        const int xt = f.xcd_tiles, xk = (int)rp_cdiv(K, TN_BK);  // (wide: the XCD-local 1-D grid)
 #define CALLW(NPROD, NA, PF, VX)                                                                                        \
     hipLaunchKernelGGL((linear_wgrad_bf16_kernel<NPROD, NA, PF, VX>), gridb, dim3(256), 0, s, dy, lddy, x, ldx, P, Pb, M, \
                        N, K, rows, xt, xk, S)
@@ -1346,8 +1510,8 @@ extern "C" int rp_linear_wgrad(const float *dy, int64_t lddy, const float *x, in
         else if (vx2) CALLW(NPROD, 1, 1, true);      \
         else CALLW(NPROD, 1, 1, false);              \
     } while (0)
-        if (mode == RP_MATMUL_BF16X6) CALLB(6);
-        else if (mode == RP_MATMUL_BF16X3) CALLB(3);
+        if (f.nprod == 6) CALLB(6);
+        else if (f.nprod == 3) CALLB(3);
         else CALLB(1);
 #undef CALLB
 #undef CALLW
@@ -1376,25 +1540,24 @@ extern "C" int rp_linear_wgrad_xbf16(const float *dy, int64_t lddy, const void *
     RP_REQUIRE(dy && x_bf16 && dw && workspace, "linear_wgrad_xbf16: null pointer");
     RP_REQUIRE(M >= 1 && N >= 1 && K >= 1, "linear_wgrad_xbf16: bad M/N/K");
     RP_REQUIRE(lddy >= N && ldx >= K && lddw >= K, "linear_wgrad_xbf16: leading dimension too small");
-    const int mode = linear_mode(M, N, K);
-    if (mode == RP_MATMUL_FP32 || wgrad_wide(N) || ldx % 2 != 0 || (reinterpret_cast<uintptr_t>(x_bf16) & 3u) != 0)
-        return rp_fail(RP_ERR_UNSUPPORTED, "linear_wgrad_xbf16: bf16 matrix-core modes, N <= 128, ldx even, 4-byte aligned x only");
+    WgradForm f;
+    if (!linear_wgrad_form(M, N, K, lddy, ldx, rp_aligned16(dy), ptr_align_bytes(x_bf16), true, &f))
+        return rp_fail(RP_ERR_UNSUPPORTED, WGRAD_XBF16_REFUSAL);
     size_t need = 0;
     rp_linear_wgrad_workspace_bytes(M, N, K, &need);
     RP_REQUIRE(workspace_bytes >= need, "linear_wgrad_xbf16: workspace %zu < %zu bytes", workspace_bytes, need);
-    int S;
-    int64_t rows;
-    wgrad_plan(M, N, K, &S, &rows);
+    const int S = f.S;
+    const int64_t rows = f.rows;
     float *P = reinterpret_cast<float *>((reinterpret_cast<uintptr_t>(workspace) + 255) & ~(uintptr_t)255);
     float *Pb = P + (size_t)S * N * K;
-    dim3 gridb((unsigned)rp_cdiv(K, TN_BK), (unsigned)rp_cdiv(N, TN_BN), (unsigned)S);
+    dim3 gridb((unsigned)f.gx, (unsigned)f.gy, (unsigned)f.gz);
     hipStream_t s = (hipStream_t)stream;
     const float *xf = reinterpret_cast<const float *>(x_bf16);
 #define CALLX(NPROD)                                                                                                       \
     hipLaunchKernelGGL((linear_wgrad_bf16_kernel<NPROD, 1, 1, true, true>), gridb, dim3(256), 0, s, dy, lddy, xf, ldx, P, Pb, M, \
                        N, K, rows, 0, 0, S)
-    if (mode == RP_MATMUL_BF16X6) CALLX(6);
-    else if (mode == RP_MATMUL_BF16X3) CALLX(3);
+    if (f.nprod == 6) CALLX(6);
+    else if (f.nprod == 3) CALLX(3);
     else CALLX(1);
 #undef CALLX
     RP_LAUNCH_CHECK("linear_wgrad_xbf16 partial");

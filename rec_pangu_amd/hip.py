@@ -823,6 +823,45 @@ def linear_wgrad_xbf16(dy, x16, K: int, want_bias: bool = True):
     return dw, db
 
 
+GEMM_FWD_FAMILIES = {_RP["RP_GEMM_FWD_" + n.upper()]: n for n in ("f32", "shortk", "colsplit", "wide", "tiled")}
+GEMM_TILES = {_RP["RP_GEMM_TILE_128X128"]: "128x128", _RP["RP_GEMM_TILE_128X64_8W"]: "128x64x8w",
+              _RP["RP_GEMM_TILE_128X64_4W"]: "128x64x4w"}
+GEMM_SK_LAUNCHES = {_RP["RP_GEMM_SK_" + n.upper()]: n for n in ("interior", "right", "bottom", "guarded")}
+GEMM_WGRAD_FAMILIES = {_RP["RP_GEMM_WGRAD_" + n.upper()]: n for n in ("f32", "narrow", "wide", "xbf16")}
+
+
+def linear_fwd_form(M: int, N: int, K: int, lda: int, ldw: int, a_aligned16: bool = True, w_aligned16: bool = True,
+                    act: int = ACT_NONE) -> dict:
+    """The launch form rp_linear_fwd chooses for this shape under the matmul precision in force (rp_linear_fwd_form: a host
+    function, no GPU): family, nprod, tile, vec_a, vec_w, sk (the short-K launches, a tuple of names), per, grid, post_act,
+    split_nb."""
+    o = (C.c_int * _RP["RP_GEMM_FORM_INTS"])()
+    _check(lib().rp_linear_fwd_form(M, N, K, lda, ldw, int(a_aligned16), int(w_aligned16), act, o), "rp_linear_fwd_form")
+    family = GEMM_FWD_FAMILIES[o[_RP["RP_GEMM_FAMILY"]]]
+    bits = o[_RP["RP_GEMM_FWD_SK_LAUNCHES"]]
+    return {"family": family, "nprod": o[_RP["RP_GEMM_NPROD"]],
+            "tile": GEMM_TILES[o[_RP["RP_GEMM_FWD_TILE"]]] if family == "tiled" else None,
+            "vec_a": bool(o[_RP["RP_GEMM_FWD_VEC_A"]]), "vec_w": bool(o[_RP["RP_GEMM_FWD_VEC_W"]]),
+            "sk": tuple(n for b, n in sorted(GEMM_SK_LAUNCHES.items()) if bits & b), "per": o[_RP["RP_GEMM_FWD_SK_PER"]],
+            "grid": (o[_RP["RP_GEMM_FWD_GRID_X"]], o[_RP["RP_GEMM_FWD_GRID_Y"]]),
+            "post_act": bool(o[_RP["RP_GEMM_FWD_POST_ACT"]]), "split_nb": o[_RP["RP_GEMM_FWD_SPLIT_NB"]]}
+
+
+def linear_wgrad_form(M: int, N: int, K: int, lddy: int, ldx: int, dy_aligned16: bool = True, x_align_bytes: int = 16,
+                      x_is_bf16: bool = False) -> Optional[dict]:
+    """The launch form rp_linear_wgrad (x_is_bf16: rp_linear_wgrad_xbf16) chooses (rp_linear_wgrad_form: a host function, no
+    GPU): family, nprod, na, vec_x, vec_y, S, rows, grid; None where rp_linear_wgrad_xbf16 refuses the shape."""
+    o = (C.c_int * _RP["RP_GEMM_FORM_INTS"])()
+    rc = lib().rp_linear_wgrad_form(M, N, K, lddy, ldx, int(dy_aligned16), x_align_bytes, int(x_is_bf16), o)
+    if rc == _RP["RP_ERR_UNSUPPORTED"]:
+        return None
+    _check(rc, "rp_linear_wgrad_form")
+    return {"family": GEMM_WGRAD_FAMILIES[o[_RP["RP_GEMM_FAMILY"]]], "nprod": o[_RP["RP_GEMM_NPROD"]],
+            "na": o[_RP["RP_GEMM_WGRAD_NA"]], "vec_x": bool(o[_RP["RP_GEMM_WGRAD_VEC_X"]]),
+            "vec_y": bool(o[_RP["RP_GEMM_WGRAD_VEC_Y"]]), "S": o[_RP["RP_GEMM_WGRAD_S"]], "rows": o[_RP["RP_GEMM_WGRAD_ROWS"]],
+            "grid": (o[_RP["RP_GEMM_WGRAD_GRID_X"]], o[_RP["RP_GEMM_WGRAD_GRID_Y"]], o[_RP["RP_GEMM_WGRAD_GRID_Z"]])}
+
+
 def transpose(w, rows_out: Optional[int] = None):
     """w [R, C] -> [C, R]; with rows_out > C the result has rows_out rows, the extra ones zero (a dgrad GEMM on it
     then writes exact zeros into the padding columns of a padded activation gradient)."""
