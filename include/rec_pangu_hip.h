@@ -186,7 +186,9 @@ int rp_embed_grad_gemm(const int32_t *sorted_keys, const int32_t *sorted_pos, in
  * field * B + sample (rp_embed_keys / the gather's keys_out).  Host arrays: tiny_field (field index), tiny_base (first arena
  * row), tiny_rows.  rp_embed_grad_gemm(skip_fields = bits of those fields) then covers the other fields.  dw != NULL
  * (round 5): also  dw[:, f*64:(f+1)*64] = sum over the table's rows of  (sum_b dH[b])^T (x) v_r  — the tiny tables' columns
- * of the first layer's weight gradient (see rp_embed_grad_seg). */
+ * of the first layer's weight gradient (see rp_embed_grad_seg); a table row nobody looked up in this batch contributes
+ * nothing, whatever it holds (like the sorted forms, which never read it).  Needs arena and lddw >= (field + 1) * 64 for
+ * every table.  Every argument is checked in front of the first launch: a refused call has written nothing. */
 int rp_embed_grad_tiny_workspace_bytes(int64_t B, size_t *bytes);
 int rp_embed_grad_tiny(const int32_t *keys, int64_t B, const int32_t *tiny_field, const int64_t *tiny_base,
                        const int32_t *tiny_rows, int n_tiny, const float *dh, int64_t lddh, const float *wt, int64_t ldwt,

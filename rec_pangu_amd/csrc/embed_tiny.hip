@@ -178,6 +178,7 @@ __global__ __launch_bounds__(ET_COLS * ET_FIN_PARTS) void embed_grad_tiny_finish
     if (threadIdx.x < ET_COLS) S[c] = (Sp[0][c] + Sp[1][c]) + (Sp[2][c] + Sp[3][c]);
     __syncthreads();
     if (hs_out != nullptr && threadIdx.x >= 64 && threadIdx.x < 128) hs_out[m * 64 + (threadIdx.x - 64)] = S[threadIdx.x - 64];
+    if (hs_out != nullptr && threadIdx.x == 128) hs_out[ET_ROWS * 64 + m] = S[129];  // the row's lookups, for the dw launch
     if (threadIdx.x < 64) {
         const int d = threadIdx.x;
         const float *w = wt + ((int64_t)tt.field[slot] * 64 + d) * ldwt;  // row f 64 + d of W1^T = column of W1
@@ -195,13 +196,16 @@ __global__ __launch_bounds__(ET_COLS * ET_FIN_PARTS) void embed_grad_tiny_finish
 
 // The tiny tables' share of the first layer's WEIGHT gradient (round 5, the companion of rp_embed_grad_seg: the forward
 // stores no activation):  dw[hidden, f*64 + d] = sum over the table's rows r of  Sh[r, hidden] v_r[d]  with the dH row sums
-// Sh the finish launch left in the workspace — a few hundred rows in all: fp32 FMAs in row order.
+// Sh the finish launch left in the workspace — a few hundred rows in all: fp32 FMAs in row order.  A row nobody looked up in
+// this batch has Sh = 0 exactly; its v_r is not part of the gathered input and must not reach dw (0 x inf = NaN): its term
+// is formed as 0 x 0 from the lookup counts behind Sh ([ET_ROWS] floats), which leaves every other sum's bits as they were.
 __global__ __launch_bounds__(256) void embed_grad_tiny_dw_kernel(const float *__restrict__ hs, TinyTables tt,
                                                                  const float *__restrict__ arena, float *__restrict__ dw,
                                                                  int64_t lddw) {
     const int slot = (int)blockIdx.x;
     const int e = (int)blockIdx.y * 256 + (int)threadIdx.x, d = e & 63, hh = e >> 6;  // (d fastest: coalesced row reads)
     const float *hrow = hs + (int64_t)tt.acc0[slot] * 64 + hh;
+    const float *cnt = hs + ET_ROWS * 64 + tt.acc0[slot];
     const float *vrow = arena + (int64_t)tt.base[slot] * 64 + d;
     float a = 0.f;
     const int nr = tt.rows[slot];
@@ -211,12 +215,12 @@ __global__ __launch_bounds__(256) void embed_grad_tiny_dw_kernel(const float *__
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             hv[u] = hrow[(int64_t)(r + u) * 64];
-            vv[u] = vrow[(int64_t)(r + u) * 64];
+            vv[u] = cnt[r + u] > 0.f ? vrow[(int64_t)(r + u) * 64] : 0.f;
         }
 #pragma unroll
         for (int u = 0; u < 8; ++u) a = __builtin_fmaf(hv[u], vv[u], a);
     }
-    for (; r < nr; ++r) a = __builtin_fmaf(hrow[(int64_t)r * 64], vrow[(int64_t)r * 64], a);
+    for (; r < nr; ++r) a = __builtin_fmaf(hrow[(int64_t)r * 64], cnt[r] > 0.f ? vrow[(int64_t)r * 64] : 0.f, a);
     dw[(int64_t)hh * lddw + (int64_t)tt.field[slot] * 64 + d] = a;
 }
 
@@ -227,7 +231,7 @@ static int64_t tiny_per_block(int64_t B) {
 
 extern "C" int rp_embed_grad_tiny_workspace_bytes(int64_t B, size_t *bytes) {
     RP_REQUIRE(bytes && B >= 1, "embed_grad_tiny_workspace_bytes: bad argument");
-    *bytes = (size_t)rp_cdiv(B, tiny_per_block(B)) * ET_ROWS * ET_COLS * sizeof(float) + (size_t)ET_ROWS * 64 * sizeof(float) + 256;
+    *bytes = (size_t)rp_cdiv(B, tiny_per_block(B)) * ET_ROWS * ET_COLS * sizeof(float) + (size_t)ET_ROWS * (64 + 1) * sizeof(float) + 256;
     return RP_OK;
 }
 
@@ -258,6 +262,10 @@ extern "C" int rp_embed_grad_tiny(const int32_t *keys, int64_t B, const int32_t 
         total += tiny_rows[j];
     }
     RP_REQUIRE(total <= ET_ROWS, "embed_grad_tiny: %d rows together (<= %d)", total, ET_ROWS);
+    // (every check stands in front of the first launch: a refused call has written nothing)
+    RP_REQUIRE(dw == nullptr || arena != nullptr, "embed_grad_tiny: the weight gradient needs the arena");
+    for (int j = 0; dw != nullptr && j < n_tiny; ++j)
+        RP_REQUIRE(lddw >= ((int64_t)tt.field[j] + 1) * 64, "embed_grad_tiny: dw rows shorter than field %d's columns", tt.field[j]);
     tt.total = total;
     const int64_t per = tiny_per_block(B);
     const int64_t nblk = rp_cdiv(B, per);
@@ -269,14 +277,11 @@ extern "C" int rp_embed_grad_tiny(const int32_t *keys, int64_t B, const int32_t 
     hipLaunchKernelGGL(embed_grad_tiny_partial_kernel, dim3((unsigned)nblk, 2), dim3(256), 0, s, keys, B, tt, dh, lddh, sum_in, gfm, per,
                        partial);
     RP_LAUNCH_CHECK("embed_grad_tiny (partial sums)");
-    RP_REQUIRE(dw == nullptr || arena != nullptr, "embed_grad_tiny: the weight gradient needs the arena");
-    float *hs = dw ? partial + (size_t)nblk * ET_ROWS * ET_COLS : nullptr;  // [total][64]: the rows' dH sums
+    float *hs = dw ? partial + (size_t)nblk * ET_ROWS * ET_COLS : nullptr;  // [ET_ROWS][64]: the rows' dH sums, then [ET_ROWS]: their lookup counts
     hipLaunchKernelGGL(embed_grad_tiny_finish_kernel, dim3((unsigned)total), dim3(ET_COLS * ET_FIN_PARTS), 0, s, partial, (int)nblk, tt, wt, ldwt, arena,
                        grad_arena, accumulate, gfm != nullptr ? 1 : 0, hs);
     RP_LAUNCH_CHECK("embed_grad_tiny (finish)");
     if (dw != nullptr) {
-        for (int j = 0; j < n_tiny; ++j)
-            RP_REQUIRE(lddw >= ((int64_t)tt.field[j] + 1) * 64, "embed_grad_tiny: dw rows shorter than field %d's columns", tt.field[j]);
         hipLaunchKernelGGL(embed_grad_tiny_dw_kernel, dim3((unsigned)n_tiny, 16), dim3(256), 0, s, hs, tt, arena, dw, lddw);
         RP_LAUNCH_CHECK("embed_grad_tiny (weight gradient)");
     }
